@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- ICP iterations/s (+ kNN correspondences/s) on the BASELINE.json workloads.
 
-    python bench.py                          # C4, 1 GPU, 20 steps, 3 warm-up steps
+    python bench.py                          # C4, 1 GPU, 20 steps, 3 warm-up steps: the headline only
+    python bench.py --full                   # ... and every other leg listed below (repeats, roofline, parity, CPU baseline, ...)
+    python bench.py --dump-outputs DIR       # also write what the last timed step computed, DIR/<name>.npy
     python bench.py --config C3              # C1 | C2 | C3 | C4 | C5size | T
     python bench.py --gpus 2                 # spawns the ranks itself when not started by torchrun
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -22,15 +24,23 @@ Marquardt solve of the reference's objective).  Both clouds, the selected points
 in HBM before the timed region.  The timed region is K consecutive iterations of a run that starts COLD at the
 initial pose (`sicp_icp_setup` was just called: no search bound from an earlier match; min_change = 0 so no step
 is skipped), bracketed by barrier + device synchronisation, MAX over ranks, with kernel timing events OFF.  It
-is repeated `--repeats` times (same start state every time); `value` is K / median(elapsed), the spread is in
-`repeat_stats`.  Kernel splits and the roofline object come from a separate, instrumented pass of the same K
-steps (HIP events on the library's own stream).
+is repeated `--repeats` times (same start state every time; default 1, with --full 50); `value` is K / median(elapsed),
+`ms_per_step` = median(elapsed) / K, the spread is in `repeat_stats`.  Kernel splits and the roofline object come from a
+separate, instrumented pass of the same K steps (HIP events on the library's own stream) -- with --full.
+
+A plain run (no --full) does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the
+line.  Everything below the contract fields is measured with --full only.
+
+--dump-outputs DIR: after the timed region, what its last step handed its caller (sicp_icp_run's last IterResult and the
+per-correspondence state sicp_icp_get_state reads back), float64: x.npy (the 6 parameters), H.npy (4 x 4), stats.npy
+(STATS_FIELDS), pc2_idx.npy / distances.npy / keep.npy / residuals.npy (one row per correspondence; above DUMP_MAX_ROWS a
+fixed, seeded sample of rows, whose indices are in rows.npy).  The inputs are seeded: the same arguments give the same inputs.
 
 N > 1: STRONG scaling -- the same movable cloud is sharded by index range over the ranks (one process per GPU),
 one all-gather exchange per iteration.
 
 One JSON line on stdout (rank 0) -- compact (about 5 KB: every field and number, no explanatory strings); the unabridged record
-goes to --out FILE (profiles/r3/bench_*.json are such files).  Extra objects on the same line:
+goes to --out FILE (profiles/r3/bench_*.json are such files).  Extra objects on the same line (--full):
   roofline             the kernel with the largest share of the step's GPU time; `achieved` = algorithmic bytes per
                        launch / average launch duration
   roofline_match       the 1-NN kernel of the default path (pruned grid search), priced on the bytes the pruned
@@ -249,7 +259,13 @@ def parse_args(argv=None):
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C4")
     ap.add_argument("--points", type=int, default=None, help="override the synthetic cloud size")
     ap.add_argument("--correspondences", type=int, default=None)
-    ap.add_argument("--repeats", type=int, default=50, help="repetitions of the K-step timed run (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: 50 repeats, steady state, instrumented and work passes, "
+                         "roofline, parity, comm, throughput legs, end-to-end run, brute-force leg, CPU baseline / reference")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the K-step timed run (median reported); default 1, with --full 50")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-bruteforce-leg", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -269,7 +285,10 @@ def parse_args(argv=None):
     ap.add_argument("--throughput-repeats", type=int, default=7)
     ap.add_argument("--out", type=str, default=None, help="also write the UNABRIDGED record to this file")
     ap.add_argument("--verbose-line", action="store_true", help="print the unabridged record on stdout as well")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 50 if args.full else 1
+    return args
 
 
 def _spawn_entry(local_rank, world, port, argv):
@@ -395,45 +414,48 @@ def run(args):
         times.append(el)
     times = np.array(times)
     elapsed = float(np.median(times))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), ctx, last)
 
     # steady state (a run's iterations from about its tenth on: the estimate has stopped moving, one LM step per iteration): 30 more
     # iterations from where the K timed ones ended, events off, wall clock -- what the latency model below is held against
     steady_us = None
-    if world == 1:
+    if world == 1 and args.full:
         xs, _, _ = iterate(ctx, 12, x.copy(), obs, ow)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         iterate(ctx, 30, xs, obs, ow)
         torch.cuda.synchronize()
         steady_us = (time.perf_counter() - t0) / 30 * 1e6
-    tail_cycles = ctx.tail_cycles() if len(sel) <= 2048 else None
+    tail_cycles = ctx.tail_cycles() if args.full and len(sel) <= 2048 else None
 
-    # instrumented pass: the same K steps with HIP events around every kernel class (perturbs the step, so it is
-    # not the timed run)
-    ctx.timing_enable(True)
-    ctx.timing_reset()
-    cold()
-    iterate(ctx, args.steps, obs.copy(), obs, ow)
-    timing = ctx.timing()
-    match_kernel = ctx.last_match_kernel()
-    # ... and one more with the grid search tallying the candidates / rows it touches (the bytes its roofline is priced on)
-    work = None
-    if match_kernel in GRID_KERNELS and not args.no_work_pass:
-        ctx.timing_enable(True, count_work=True)
+    timing, match_kernel, work = None, None, None
+    if args.full:
+        # instrumented pass: the same K steps with HIP events around every kernel class (perturbs the step, so it is
+        # not the timed run)
+        ctx.timing_enable(True)
         ctx.timing_reset()
         cold()
         iterate(ctx, args.steps, obs.copy(), obs, ow)
-        work = ctx.match_work()
-    ctx.timing_enable(False)
+        timing = ctx.timing()
+        match_kernel = ctx.last_match_kernel()
+        # ... and one more with the grid search tallying the candidates / rows it touches (the bytes its roofline is priced on)
+        if match_kernel in GRID_KERNELS and not args.no_work_pass:
+            ctx.timing_enable(True, count_work=True)
+            ctx.timing_reset()
+            cold()
+            iterate(ctx, args.steps, obs.copy(), obs, ow)
+            work = ctx.match_work()
+        ctx.timing_enable(False)
 
     # parity leg, device side (every rank takes part in the exchange; only rank 0 consults the oracle)
-    parity_rec = None if args.no_parity else parity_device(ctx, sel, normals, planarity, obs, ow)
-    comm = comm_record(ctx, exchange, transport, qshard, world, hi - lo, len(sel), timing, args.steps)
+    parity_rec = None if args.no_parity or not args.full else parity_device(ctx, sel, normals, planarity, obs, ow)
+    comm = comm_record(ctx, exchange, transport, qshard, world, hi - lo, len(sel), timing, args.steps) if args.full else None
 
     # throughput legs ("additionally Q = 100 k for a throughput point"): same clouds, Q large enough that the
     # machine is full; N > 1: query shards (the whole cloud on every rank, Q / N queries each)
     tps = []
-    tq = [int(v) for v in args.throughput_q.split(",") if v.strip() and int(v) > 0] if H_true is not None else []
+    tq = [int(v) for v in args.throughput_q.split(",") if v.strip() and int(v) > 0] if H_true is not None and args.full else []
     for Qt in tq:
         if Qt == len(sel) or Qt > Nf:
             continue
@@ -451,66 +473,67 @@ def run(args):
         nq_local = (nq + world - 1) // world                     # queries this rank's match launch handles
     else:
         nq_local = nq
-    avg = {kname: v["ms"] / max(1, v["launches"]) for kname, v in timing.items()}
-    match_ms, solve_ms, select_ms = avg["match"], avg["solve"], avg["reject_select"]
     fused = nq <= 2048
     evals_per_it = ne_evals / args.steps
-    bytes_bruteforce = n_local * 24 + nq * (24 + 16)        # read the searched cloud once + queries + (idx, d2)
-    # 72 B per kept correspondence and evaluation + the median / MAD passes (n * 8 B x 3) when they are in the launch
-    bytes_solve = int(last.n_kept) * 72 * evals_per_it + (nq * 8 * 3 if fused else 0)
-    pmc, pmc_src = load_pmc()
+    if args.full:
+        avg = {kname: v["ms"] / max(1, v["launches"]) for kname, v in timing.items()}
+        match_ms, solve_ms, select_ms = avg["match"], avg["solve"], avg["reject_select"]
+        bytes_bruteforce = n_local * 24 + nq * (24 + 16)        # read the searched cloud once + queries + (idx, d2)
+        # 72 B per kept correspondence and evaluation + the median / MAD passes (n * 8 B x 3) when they are in the launch
+        bytes_solve = int(last.n_kept) * 72 * evals_per_it + (nq * 8 * 3 if fused else 0)
+        pmc, pmc_src = load_pmc()
 
-    def roof(kernel, ms, bytes_alg, note, extra=None):
-        if bytes_alg is None:                    # nothing to price this launch on in this run (no tallies, no counters): say so
-            d = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
-                 "traffic_source": None, "kernel": kernel, "avg_ms": ms, "bytes_alg_per_launch": None, "note": note}
-            d.update(extra or {})
+        def roof(kernel, ms, bytes_alg, note, extra=None):
+            if bytes_alg is None:                    # nothing to price this launch on in this run (no tallies, no counters): say so
+                d = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
+                     "traffic_source": None, "kernel": kernel, "avg_ms": ms, "bytes_alg_per_launch": None, "note": note}
+                d.update(extra or {})
+                return d
+            ach = bytes_alg / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            # counters are keyed by kernel for the default line and "<kernel>@<config>" for the other configurations' own passes
+            traffic = pmc.get(f"{kernel}@{args.config}") if args.config != "C4" else pmc.get(kernel)
+            d = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                 "traffic": traffic, "traffic_source": pmc_src if (traffic is not None or not pmc) else None,
+                 "kernel": kernel, "avg_ms": ms, "bytes_alg_per_launch": int(bytes_alg), "note": note}
+            if traffic is not None and ms > 0:
+                d["frac_on_pmc_traffic"] = traffic / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS        # the counters' bytes over the same time
+            if extra:
+                d.update(extra)
             return d
-        ach = bytes_alg / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-        # counters are keyed by kernel for the default line and "<kernel>@<config>" for the other configurations' own passes
-        traffic = pmc.get(f"{kernel}@{args.config}") if args.config != "C4" else pmc.get(kernel)
-        d = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-             "traffic": traffic, "traffic_source": pmc_src if (traffic is not None or not pmc) else None,
-             "kernel": kernel, "avg_ms": ms, "bytes_alg_per_launch": int(bytes_alg), "note": note}
-        if traffic is not None and ms > 0:
-            d["frac_on_pmc_traffic"] = traffic / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS        # the counters' bytes over the same time
-        if extra:
-            d.update(extra)
-        return d
 
-    if match_kernel in GRID_KERNELS:
-        # the pruned search's OWN bytes: every candidate it evaluates is one packed 32-B record (x, y, z, index),
-        # every non-empty grid row two 4-B offsets, every query its coordinates, the previous match (bound) and the
-        # 48-B result -- tallied by the kernel itself in a separate pass
-        if work and work["launches"]:
-            per = {kk: v / max(1, work["launches"]) for kk, v in work.items() if kk != "launches"}
-            bytes_match = match_bytes(match_kernel, per, nq)
-            extra = {"candidates_per_query": per["candidates"] / nq, "grid_rows_per_query": per["rows"] / nq}
+        if match_kernel in GRID_KERNELS:
+            # the pruned search's OWN bytes: every candidate it evaluates is one packed 32-B record (x, y, z, index),
+            # every non-empty grid row two 4-B offsets, every query its coordinates, the previous match (bound) and the
+            # 48-B result -- tallied by the kernel itself in a separate pass
+            if work and work["launches"]:
+                per = {kk: v / max(1, work["launches"]) for kk, v in work.items() if kk != "launches"}
+                bytes_match = match_bytes(match_kernel, per, nq)
+                extra = {"candidates_per_query": per["candidates"] / nq, "grid_rows_per_query": per["rows"] / nq}
+            else:
+                # --no-work-pass (the kernel-trace run of scripts/gpu_profile.sh): the counters' bytes if this tree has them -- never the
+                # brute-force figure, which a pruned search does not read (it would price the launch above the HBM peak)
+                bytes_match = pmc.get(match_kernel)
+                extra = {"bytes_alg_source": "PMC traffic (no in-kernel tallies in this run)" if bytes_match else
+                         "none: no in-kernel tallies in this run (--no-work-pass) and no counter summary of this tree"}
+            extra["pruning_ratio"] = bytes_bruteforce / max(1.0, bytes_match) if bytes_match else None
+            extra["bytes_bruteforce_per_launch"] = int(bytes_bruteforce)
+            r_match = roof(match_kernel, match_ms, bytes_match,
+                           ("exact 1-NN on a static uniform grid, one wave per query: reads only the cells the bound ball touches "
+                            "(pruning_ratio = brute-force algorithmic bytes / these); ~4 dependent memory round trips per "
+                            "query, i.e. latency-bound, not bandwidth-bound") if match_kernel == "k_grid_nn" else
+                           ("exact 1-NN on a static uniform grid, four cell-ordered queries per wave: reads only the cells the bound "
+                            "ball touches (pruning_ratio = brute-force algorithmic bytes / these); VALU-issue- and latency-bound"), extra)
         else:
-            # --no-work-pass (the kernel-trace run of scripts/gpu_profile.sh): the counters' bytes if this tree has them -- never the
-            # brute-force figure, which a pruned search does not read (it would price the launch above the HBM peak)
-            bytes_match = pmc.get(match_kernel)
-            extra = {"bytes_alg_source": "PMC traffic (no in-kernel tallies in this run)" if bytes_match else
-                     "none: no in-kernel tallies in this run (--no-work-pass) and no counter summary of this tree"}
-        extra["pruning_ratio"] = bytes_bruteforce / max(1.0, bytes_match) if bytes_match else None
-        extra["bytes_bruteforce_per_launch"] = int(bytes_bruteforce)
-        r_match = roof(match_kernel, match_ms, bytes_match,
-                       ("exact 1-NN on a static uniform grid, one wave per query: reads only the cells the bound ball touches "
-                        "(pruning_ratio = brute-force algorithmic bytes / these); ~4 dependent memory round trips per "
-                        "query, i.e. latency-bound, not bandwidth-bound") if match_kernel == "k_grid_nn" else
-                       ("exact 1-NN on a static uniform grid, four cell-ordered queries per wave: reads only the cells the bound "
-                        "ball touches (pruning_ratio = brute-force algorithmic bytes / these); VALU-issue- and latency-bound"), extra)
-    else:
-        r_match = roof(match_kernel, match_ms, bytes_bruteforce,
-                       "brute-force Q x N scan: VALU-bound by construction (SURVEY 8d), cloud read once")
-    tail_kernel = "k_icp_tail" if fused else ("k_lm_eval" if exchange else "k_lm_all")
-    r_solve = roof(tail_kernel, solve_ms, bytes_solve,
-                   "everything after the match in ONE single-workgroup launch (distances, MAD rejection, LM with "
-                   "device-side 6x6 solves): ~1000 correspondences = latency-bound on one CU by design, not bandwidth"
-                   if fused else "the iteration's solver launches together (enqueued evaluations + finish): residual + Jacobian rows + 8x8 "
-                   "Gram on the FP64 matrix pipe, 72 B/correspondence/evaluation; the last block of an evaluation advances the solver")
-    solve_total = solve_ms
-    dominant = r_solve if solve_total >= match_ms else r_match
+            r_match = roof(match_kernel, match_ms, bytes_bruteforce,
+                           "brute-force Q x N scan: VALU-bound by construction (SURVEY 8d), cloud read once")
+        tail_kernel = "k_icp_tail" if fused else ("k_lm_eval" if exchange else "k_lm_all")
+        r_solve = roof(tail_kernel, solve_ms, bytes_solve,
+                       "everything after the match in ONE single-workgroup launch (distances, MAD rejection, LM with "
+                       "device-side 6x6 solves): ~1000 correspondences = latency-bound on one CU by design, not bandwidth"
+                       if fused else "the iteration's solver launches together (enqueued evaluations + finish): residual + Jacobian rows + 8x8 "
+                       "Gram on the FP64 matrix pipe, 72 B/correspondence/evaluation; the last block of an evaluation advances the solver")
+        solve_total = solve_ms
+        dominant = r_solve if solve_total >= match_ms else r_match
 
     out = {
         "metric": "ICP iterations/sec (kNN correspondences/sec in `correspondences_per_s`), 10M-vs-10M pts",
@@ -537,10 +560,6 @@ def run(args):
                          "ms_per_step_min": float(times.min()) / args.steps * 1e3,
                          "ms_per_step_first": float(times[0]) / args.steps * 1e3,
                          "timed_region": "K steps from the cold state (icp_setup just called), min_change=0, events off"},
-        "roofline": dominant,
-        "roofline_match": r_match,
-        "kernels_instrumented": {name: {"avg_ms": avg[name], "launches": timing[name]["launches"]} for name in timing},
-        "gpu_ms_per_step_instrumented": match_ms + solve_total + select_ms,
         "setup": {**setup, "normals_knn_kernel_ms": knnk["ms"],
                   # the normals' k-NN as Q * k neighbours per second of its search kernel
                   "normals_knn_neighbours_per_s": (nq * k / (knnk["ms"] * 1e-3)) if knnk["ms"] > 0 else None,
@@ -550,6 +569,11 @@ def run(args):
                    "final_res_std": last.res_std},
         "device": ctx.device_name(),
     }
+    if args.full:
+        out["roofline"] = dominant
+        out["roofline_match"] = r_match
+        out["kernels_instrumented"] = {name: {"avg_ms": avg[name], "launches": timing[name]["launches"]} for name in timing}
+        out["gpu_ms_per_step_instrumented"] = match_ms + solve_total + select_ms
     if H_true is not None:
         out["accuracy"] = {"max_abs_H_minus_H_true": float(np.abs(H - H_true).max())}
     if steady_us is not None:
@@ -577,14 +601,14 @@ def run(args):
                                              + ("query shards" if world > 1 else "1 GPU"),
                                    "value": big["correspondences_per_s"], "unit": "correspondences/s", "n_gpus": world,
                                    "ms_per_step": big["ms_per_step"]}
-    if world == 1 and not args.no_end_to_end:
+    if world == 1 and args.full and not args.no_end_to_end:
         out["run_end_to_end"] = end_to_end(Xf, Xm, Q, k, kw)
-    if world == 1 and not args.no_bruteforce_leg and Nm * nq <= 2e11:
+    if world == 1 and args.full and not args.no_bruteforce_leg and Nm * nq <= 2e11:
         out["roofline_bruteforce"] = bruteforce_leg(local_rank, Xf, Xm, sel, normals, planarity, pmc, pmc_src)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(Xf, Xm, sel, normals, planarity, args.cpu_iterations)
     ref_file = ROOT / "profiles" / "cpu_reference.json"
-    if ref_file.exists():
+    if args.full and ref_file.exists():
         ref = json.loads(ref_file.read_text())
         if args.config in ref.get("configs", {}):
             out["cpu_reference"] = {**ref["configs"][args.config], "measured_on": ref.get("measured_on"),
@@ -611,6 +635,30 @@ def run(args):
     print(json.dumps(out if args.verbose_line else compact_line(out)), flush=True)
 
 
+STATS_FIELDS = ("n_queries", "n_planar", "n_kept", "median", "mad", "dist_mean", "dist_std", "res_mean", "res_std", "weight_used",
+                "cost", "lm_steps", "ne_evals")
+DUMP_MAX_ROWS = 1 << 20          # 4 row arrays x 8 B x 1 Mi rows = 32 MB: the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, ctx, last):
+    """--dump-outputs: the last timed step's result record and per-correspondence state, float64 .npy files."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    idx, dist, keep, res = ctx.icp_state()
+    rows = None
+    if len(idx) > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(len(idx), DUMP_MAX_ROWS, replace=False))
+    arrays = {"x": np.array(last.x[:]), "H": np.array(last.H[:]).reshape(4, 4),
+              "stats": np.array([getattr(last, f) for f in STATS_FIELDS], dtype=np.float64),
+              "pc2_idx": idx, "distances": dist, "keep": keep, "residuals": res}
+    for name in ("pc2_idx", "distances", "keep", "residuals"):
+        if rows is not None:
+            arrays[name] = arrays[name][rows]
+    if rows is not None:
+        arrays["rows"] = rows
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
 def compact_line(out):
     """The stdout line: same objects, explanatory strings and second-order detail dropped."""
     drop = {"note", "traffic_source", "timed_region", "scope", "oracle", "source", "measured_on", "bytes_alg_source", "repeat_stats",
@@ -624,7 +672,8 @@ def compact_line(out):
         return v
     line = strip(out)
     line["repeat_stats"] = {k: out["repeat_stats"][k] for k in ("repeats", "ms_per_step_p10", "ms_per_step_p90")}
-    line["kernels_instrumented"] = {k: round(v["avg_ms"], 6) for k, v in out["kernels_instrumented"].items() if v["launches"]}
+    if "kernels_instrumented" in out:
+        line["kernels_instrumented"] = {k: round(v["avg_ms"], 6) for k, v in out["kernels_instrumented"].items() if v["launches"]}
     line["setup"] = {k: round(v, 3) for k, v in out["setup"].items() if isinstance(v, float)}
     line["solver"] = out["solver"]
     for k in list(line):

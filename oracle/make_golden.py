@@ -201,7 +201,7 @@ def check_readme_kat(H, rbp, text):
 
 def main():
     global GOLD, DATA
-    if len(sys.argv) > 2 and sys.argv[1] == "--out":          # regenerate somewhere else (tests/test_fixtures_regenerate.py)
+    if len(sys.argv) > 2 and sys.argv[1] == "--out":          # regenerate somewhere else (to compare with the committed files)
         GOLD = Path(sys.argv[2]).resolve()
         DATA = GOLD / "data"
     os.chdir(ROOT)

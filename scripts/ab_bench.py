@@ -33,7 +33,7 @@ def main():
             k, _, v = kv.partition("=")
             env[k] = v
         f = out / f"{name}.json"
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", a.config, "--repeats", str(a.repeats), "--steps",
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--config", a.config, "--repeats", str(a.repeats), "--steps",
                             str(a.steps), "--no-cpu-baseline", "--no-end-to-end", "--no-bruteforce-leg", "--out", str(f)],
                            env=env, capture_output=True, text=True)
         if r.returncode != 0 or not f.exists():

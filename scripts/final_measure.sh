@@ -18,20 +18,20 @@ if has profiles; then
   python scripts/summarize_profile.py $TAG > "$OUT/summarize_profile.txt" 2>&1; stamp "summarize rc=$?"
 fi
 if has bench; then
-  timeout 600 python bench.py --out "$OUT/bench_C4.json" > /dev/null 2> "$OUT/bench_C4.err"; stamp "bench C4 rc=$?"
+  timeout 600 python bench.py --full --out "$OUT/bench_C4.json" > /dev/null 2> "$OUT/bench_C4.err"; stamp "bench C4 rc=$?"
 fi
 if has configs; then
   for C in C1 C2 C3 T; do
-    timeout 600 python bench.py --config $C --out "$OUT/bench_$C.json" > /dev/null 2> "$OUT/bench_$C.err"; stamp "bench $C rc=$?"
+    timeout 600 python bench.py --full --config $C --out "$OUT/bench_$C.json" > /dev/null 2> "$OUT/bench_$C.err"; stamp "bench $C rc=$?"
   done
 fi
 if has exchange; then
-  timeout 600 python bench.py --force-exchange --partition cloud --no-cpu-baseline --no-end-to-end --no-bruteforce-leg --throughput-q 100000 --out "$OUT/bench_C4_exchange_cloud.json" > /dev/null 2> "$OUT/bench_x1.err"; stamp "exchange cloud rc=$?"
+  timeout 600 python bench.py --full --force-exchange --partition cloud --no-cpu-baseline --no-end-to-end --no-bruteforce-leg --throughput-q 100000 --out "$OUT/bench_C4_exchange_cloud.json" > /dev/null 2> "$OUT/bench_x1.err"; stamp "exchange cloud rc=$?"
 fi
 if has exchange; then
   # two ranks sharing the one GPU (gloo group, collectives staged through host memory): cloud shards, the throughput legs' winners by the
   # three reductions on 8-byte keys over the callback (ABI 6)
-  SICP_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --partition cloud --no-cpu-baseline --no-end-to-end --no-bruteforce-leg --throughput-q 100000,1000000 --repeats 10 --throughput-repeats 3 --out "$OUT/bench_C4_two_ranks_one_gpu_cloud.json" > /dev/null 2> "$OUT/bench_x2.err"; stamp "two ranks, cloud shards rc=$?"
+  SICP_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus 2 --partition cloud --no-cpu-baseline --no-end-to-end --no-bruteforce-leg --throughput-q 100000,1000000 --repeats 10 --throughput-repeats 3 --out "$OUT/bench_C4_two_ranks_one_gpu_cloud.json" > /dev/null 2> "$OUT/bench_x2.err"; stamp "two ranks, cloud shards rc=$?"
 fi
 if has sweeps; then
   timeout 600 python scripts/q_sweep.py 1e7 1000 2048 2049 4096 8192 10000 16384 32768 100000 196608 1000000 > "$OUT/q_sweep.txt" 2>&1; stamp "q_sweep rc=$?"
@@ -46,7 +46,7 @@ if has traces; then
   python scripts/iter_timeline.py gpurun_out/kt_c4_$TAG > "$OUT/iter_timeline.txt" 2>&1; stamp "iter timeline"
 fi
 if has c5; then
-  timeout 1200 python bench.py --config C5size --repeats 5 --no-cpu-baseline --no-end-to-end --no-bruteforce-leg --throughput-q 0 --out "$OUT/bench_C5size.json" > /dev/null 2> "$OUT/bench_C5size.err"; stamp "C5size rc=$?"
+  timeout 1200 python bench.py --full --config C5size --repeats 5 --no-cpu-baseline --no-end-to-end --no-bruteforce-leg --throughput-q 0 --out "$OUT/bench_C5size.json" > /dev/null 2> "$OUT/bench_C5size.err"; stamp "C5size rc=$?"
 fi
 if has tests; then
   # what the driver runs (the full-size legs marked `slow` are skipped there), then those legs on their own

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CTRS --output-format csv -d "$OUT" -- python $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/err.txt"
+rocprofv3 --pmc $CTRS --output-format csv -d "$OUT" -- python $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/err.txt"
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]

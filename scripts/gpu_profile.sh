@@ -13,7 +13,7 @@ PASSES=${PASSES:-"trace fetch write sq1 sq2"}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 ( cd "$REPO" && python -c "import bench; print(bench.csrc_hash())" ) > "$OUT/csrc_hash.txt"
-BENCH="python $REPO/bench.py --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --no-parity --no-end-to-end --throughput-q 0 $*"
+BENCH="python $REPO/bench.py --full --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --no-parity --no-end-to-end --throughput-q 0 $*"
 for P in $PASSES; do
   case $P in
     trace) rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $BENCH --no-work-pass > "$OUT/bench_trace.json" 2> "$OUT/trace.err" ;;

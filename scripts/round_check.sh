@@ -14,7 +14,7 @@ timeout ${T_OPS:-240} python -m pytest tests/test_gpu_operators.py tests/test_ho
 stamp "operator tests rc=$?"
 timeout ${T_SUITE:-420} python -m pytest tests -m gpu -q --durations=15 --ignore=tests/test_gpu_operators.py > "$OUT/suite.log" 2>&1
 stamp "suite rc=$?"
-timeout ${T_BENCH:-240} python bench.py --out "$OUT/bench_C4.json" > "$OUT/bench.log" 2> "$OUT/bench.err"
+timeout ${T_BENCH:-240} python bench.py --full --out "$OUT/bench_C4.json" > "$OUT/bench.log" 2> "$OUT/bench.err"
 stamp "bench rc=$?"
 if [ "${EXTRAS:-0}" = "1" ]; then      # the two small records of profiles/r2 (operator_cost.txt, host_enqueue.txt)
   timeout ${T_OPCOST:-120} python scripts/operator_cost.py > "$OUT/operator_cost.txt" 2>&1

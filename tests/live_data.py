@@ -1,4 +1,4 @@
-"""Seeded random cloud pairs for the tests that run the unmodified reference live (tests/test_live_*.py)."""
+"""Seeded random cloud pairs of tests/test_live_*.py (the reference's runs on them: oracle/record_reference.py)."""
 import numpy as np
 
 from oracle import orc

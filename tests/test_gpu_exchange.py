@@ -191,7 +191,7 @@ def test_bench_two_ranks_self_launched(partition, launcher):
     import json
     import socket
     env = dict(os.environ, SICP_BENCH_SHARE_GPU="1")
-    args = [str(ROOT / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--repeats", "2", "--points", "300000",
+    args = [str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "1", "--repeats", "2", "--points", "300000",
             "--partition", partition, "--no-cpu-baseline", "--no-end-to-end", "--no-bruteforce-leg", "--throughput-q", "40000",
             "--throughput-repeats", "2"]
     if launcher == "torchrun":

@@ -1,23 +1,16 @@
-"""Fresh data every time instead of the nine committed fixtures: the UNMODIFIED reference (imported; build container
-only) and this package's SimpleICP.run (its host logic on the oracle-backed stand-in context, tests/oracle_backend.py)
-register the same seeded random cloud pairs with the same keyword arguments -- partial overlap, fixed and observed
-parameters, an automatic weight, few iterations.  The reference's own normals are handed over (its LAPACK signs are
-arbitrary and its result depends on them), as the fixtures do.  Then: the same iteration count, the same
-correspondence counts up to a cKDTree tie pick, H to the reference's solver tolerance.  CPU only; skipped where
-/root/reference does not exist."""
-import sys
-from pathlib import Path
-
+"""Other data than the nine committed fixtures: the UNMODIFIED reference and this package's SimpleICP.run (its host logic on
+the oracle-backed stand-in context, tests/oracle_backend.py) register the same seeded random cloud pairs with the same keyword
+arguments -- partial overlap, fixed and observed parameters, an automatic weight, few iterations.  The reference's own normals
+are handed over (its LAPACK signs are arbitrary and its result depends on them), as the fixtures do.  Then:
+the same iteration count, the same correspondence counts up to a cKDTree tie pick, H to the reference's solver tolerance.
+The reference's runs are stored in tests/golden/live/runs.npz (oracle/record_reference.py, which runs these CASES).  CPU only."""
 import numpy as np
 import pandas as pd
 import pytest
 
 import oracle_backend
-from conftest import ROOT
+from conftest import GOLDEN
 from live_data import cloud_pair as _pair
-
-REF = Path("/root/reference/python")
-pytestmark = pytest.mark.skipif(not (REF / "simpleicp").exists(), reason="the reference package is not on this machine")
 
 CASES = [
     (0, {}),
@@ -30,24 +23,19 @@ CASES = [
 
 @pytest.mark.parametrize("seed,kwargs", CASES)
 def test_reference_and_mirror_agree_on_fresh_data(seed, kwargs, monkeypatch):
-    for p in (str(ROOT / "oracle" / "shim"), str(REF)):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import simpleicp as ref
     from simpleicp_amd import PointCloud, SimpleICP
     P, M = _pair(seed)
-    a_fix, a_mov = ref.PointCloud(P, columns=["x", "y", "z"]), ref.PointCloud(M.copy(), columns=["x", "y", "z"])
-    a = ref.SimpleICP(verbose=False)
-    a.add_point_clouds(a_fix, a_mov)
-    with _Capture("simpleicp") as log_a:
-        H0, X0, rbp0, res0 = a.run(**kwargs)
+    g = np.load(GOLDEN / "live" / "runs.npz", allow_pickle=False)
+    H0, X0 = g[f"s{seed}_H"], g[f"s{seed}_X"].astype(np.float64)   # (X stored in float32: 1e-6 here, compared to 1e-4)
+    n_res0, std_res0 = g[f"s{seed}_res"]
+    rows_a, stopped_a = (int(v) for v in g[f"s{seed}_rows_stopped"])
 
     oracle_backend.install(monkeypatch)
     b_fix, b_mov = PointCloud(P, columns=["x", "y", "z"]), PointCloud(M.copy(), columns=["x", "y", "z"])
-    sel = a_fix.idx_selected                                   # the rows the reference estimated normals for
-    for c in ("nx", "ny", "nz", "planarity"):
+    sel = g[f"s{seed}_sel"]                                    # the rows the reference estimated normals for
+    for c, col in zip(("nx", "ny", "nz", "planarity"), g[f"s{seed}_normals"]):
         v = np.full(len(P), np.nan, np.float32)
-        v[sel] = a_fix[c].to_numpy()[sel]
+        v[sel] = col
         b_fix[c] = pd.arrays.SparseArray(v)
     b = SimpleICP(verbose=False)
     b.add_point_clouds(b_fix, b_mov)
@@ -56,20 +44,20 @@ def test_reference_and_mirror_agree_on_fresh_data(seed, kwargs, monkeypatch):
 
     assert np.array_equal(b_fix.idx_selected, sel)             # overlap pre-pass + sub-sampling: the same rows
     assert np.abs(H1 - H0).max() < 2e-6, np.abs(H1 - H0).max()
-    assert abs(len(res1) - len(res0)) <= 2 and abs(res1.std() - res0.std()) < 1e-5
+    assert abs(len(res1) - n_res0) <= 2 and abs(res1.std() - std_res0) < 1e-5
     assert np.abs(X1 - X0).max() < 1e-4 and np.array_equal(X1, b_mov.X)
-    x0 = np.array(rbp0.get_parameter_attributes_as_list("estimated_value"))
+    x0 = g[f"s{seed}_x"]
     x1 = np.array(rbp1.get_parameter_attributes_as_list("estimated_value"))
     ow = np.array(kwargs.get("rbp_observation_weights", (0.,) * 6), float)
     assert np.abs(x1 - x0).max() < 2e-6 and np.array_equal(x1[~np.isfinite(ow)], x0[~np.isfinite(ow)])
-    s0 = np.array(rbp0.get_parameter_attributes_as_list("estimated_uncertainty"))
+    s0 = g[f"s{seed}_s"]
     s1 = np.array(rbp1.get_parameter_attributes_as_list("estimated_uncertainty"))
     free = np.isfinite(ow)
     assert np.allclose(s1[free], s0[free], rtol=5e-3) and np.all(np.isnan(s1[~free])) and np.all(np.isnan(s0[~free]))
     # iteration count: one table row per iteration (simpleicp.py:275-280), except the converging one (it breaks before its row)
-    stopped = [any(m.startswith("Convergence criteria fulfilled") for m in log) for log in (log_a, log_b)]
-    assert _rows(log_a) == _rows(log_b) > 0 and stopped[0] == stopped[1]
-    assert b.last_run_info["iterations"] == _rows(log_b) + int(stopped[1])
+    stopped_b = any(m.startswith("Convergence criteria fulfilled") for m in log_b)
+    assert rows_a == _rows(log_b) > 0 and bool(stopped_a) == stopped_b
+    assert b.last_run_info["iterations"] == _rows(log_b) + int(stopped_b)
 
 
 def _rows(records):
