@@ -17,8 +17,9 @@ _logging.getLogger(__name__).addHandler(_logging.NullHandler())
 from .pointcloud import PointCloud, PointCloudException          # noqa: E402
 from .rbp import Parameter, RigidBodyParameters                  # noqa: E402
 from .icp import SimpleICP, SimpleICPException                   # noqa: E402
+from .batch import BatchResult, run_batch                        # noqa: E402
 
 from . import io                                                 # noqa: E402,F401
 
 __all__ = ["SimpleICP", "SimpleICPException", "PointCloud", "PointCloudException",
-           "RigidBodyParameters", "Parameter"]
+           "RigidBodyParameters", "Parameter", "run_batch", "BatchResult"]

@@ -35,6 +35,11 @@ EXPORTS = [
     "sicp_xyz_count", "sicp_xyz_read", "sicp_xyz_write",
 ]
 
+# include/simpleicp_hip_batch.h: a companion ABI with a version of its own (the list above and ABI_VERSION stay as they are)
+BATCH_EXPORTS = ["sicp_batch_version", "sicp_icp_run_batch", "sicp_ctx_lean"]
+BATCH_VERSION = 1
+BATCH_PATH_BATCHED, BATCH_PATH_FALLBACK = 1, 2
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -55,6 +60,12 @@ class IterResult(C.Structure):
                 ("dist_mean", C.c_double), ("dist_std", C.c_double), ("res_mean", C.c_double),
                 ("res_std", C.c_double), ("weight_used", C.c_double), ("cost", C.c_double),
                 ("lm_steps", C.c_int64), ("ne_evals", C.c_int64)]
+
+
+class BatchMember(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("params", IterParams), ("max_iterations", C.c_int64), ("min_change", C.c_double),
+                ("results", C.POINTER(IterResult)), ("iterations", C.c_int64), ("status", C.c_int), ("path", C.c_int),
+                ("error", C.c_char * 256)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -139,6 +150,12 @@ def load():
     for name in EXPORTS:
         if name != "sicp_last_error":
             getattr(L, name).restype = cint
+    if all(hasattr(L, name) for name in BATCH_EXPORTS):
+        L.sicp_batch_version.restype = cint
+        L.sicp_icp_run_batch.argtypes = [C.POINTER(BatchMember), i64, C.POINTER(i64)]
+        L.sicp_icp_run_batch.restype = cint
+        L.sicp_ctx_lean.argtypes = [vp]
+        L.sicp_ctx_lean.restype = cint
     _lib = L
     return L
 
@@ -168,6 +185,60 @@ def params_to_H(x):
     H = np.empty(16)
     load().sicp_params_to_H(_ptr(_f64(x)), _ptr(H))
     return H.reshape(4, 4)
+
+
+def batch_version():
+    """SICP_BATCH_VERSION of the loaded library; BackendError when it has no batch entry points."""
+    L = load()
+    missing = [name for name in BATCH_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise BackendError(f"{LIB_PATH} has no batch entry points ({', '.join(missing)}): it predates include/simpleicp_hip_batch.h; "
+                           "rebuild with `python -m simpleicp_amd.build`")
+    return L.sicp_batch_version()
+
+
+class BatchRun:
+    """One member's outcome of icp_run_batch: the per-iteration IterResults, the status, the message of a failure, the path."""
+
+    def __init__(self, results, status, error, path):
+        self.results, self.status, self.error, self.path = results, status, error, path
+
+    def raise_for_status(self):
+        """The BackendError (with `.results`) Context.icp_run would have raised, if any."""
+        if self.status != OK:
+            err = BackendError(self.error, self.status)
+            err.results = self.results
+            raise err
+
+
+def icp_run_batch(members):
+    """sicp_icp_run_batch over [(Context, icp_run keyword arguments), ...]: every member's loop behind one call.
+    Returns ([BatchRun per member, in order], fallback_count); raises BackendError on a batch-wide error (nothing ran then)."""
+    if batch_version() != BATCH_VERSION:
+        raise BackendError(f"{LIB_PATH} implements batch version {load().sicp_batch_version()}, this binding needs {BATCH_VERSION}")
+    arr = (BatchMember * max(len(members), 1))()
+    keep = []
+    for i, (ctx, kw) in enumerate(members):
+        m = arr[i]
+        m.ctx = ctx._h.value
+        m.params = ctx._params(kw.get("x"), kw.get("obs"), kw.get("obs_weight"), kw.get("min_planarity", 0.3),
+                               kw.get("distance_weight", 1.0), kw.get("max_lm_steps", 0))
+        n = int(kw.get("max_iterations", 100))
+        res = (IterResult * max(n, 1))()
+        keep.append(res)
+        m.results = C.cast(res, C.POINTER(IterResult))
+        m.max_iterations = n
+        m.min_change = float(kw.get("min_change", 1.0))
+    fb = C.c_int64()
+    L = load()
+    rc = L.sicp_icp_run_batch(arr, len(members), C.byref(fb))
+    if rc != OK:
+        raise BackendError(L.sicp_last_error().decode(), rc)
+    out = []
+    for i in range(len(members)):
+        m = arr[i]
+        out.append(BatchRun([keep[i][j] for j in range(m.iterations)], m.status, m.error.decode(), m.path))
+    return out, fb.value
 
 
 class Context:
@@ -212,6 +283,12 @@ class Context:
         self._chk(self._L.sicp_ctx_device_name(self._h, buf, 256))
         return buf.value.decode()
 
+    def make_lean(self):
+        """A lean batch member (sicp_ctx_lean): its staged uploads and download_both share ONE pinned ring with the process's other
+        lean contexts instead of a 48 MiB ring of its own."""
+        batch_version()
+        self._chk(self._L.sicp_ctx_lean(self._h))
+
     # -- clouds --
     def upload(self, slot, xyz, index_base=0):
         """xyz: (n,3) float64 numpy array or CUDA/host torch tensor."""
@@ -249,8 +326,13 @@ class Context:
             if len(src) != 3 or any(v.ndim != 1 or len(v) != n for v in src):
                 raise ValueError("x, y, z must be vectors of the same length")
             args = (None, _ptr(src[0]), _ptr(src[1]), _ptr(src[2]))
-        self._bg_src[slot] = src
-        self._chk(self._L.sicp_cloud_upload_start(self._h, slot, *args, n, int(index_base)))
+        # the slot's previous sources stay referenced until the C call has joined the helper that may still be reading them
+        prev = self._bg_src.get(slot)
+        try:
+            self._chk(self._L.sicp_cloud_upload_start(self._h, slot, *args, n, int(index_base)))
+        finally:
+            self._bg_src[slot] = src
+            del prev
 
     def upload_wait(self, slot):
         try:
@@ -354,6 +436,11 @@ class Context:
             raise err
         return R
 
+    @staticmethod
+    def _params(x, obs, obs_weight, min_planarity=0.3, distance_weight=1.0, max_lm_steps=0):
+        return IterParams((C.c_double * 6)(*x), (C.c_double * 6)(*obs), (C.c_double * 6)(*obs_weight),
+                          min_planarity, -1.0 if distance_weight is None else distance_weight, int(max_lm_steps))
+
     def icp_run(self, x, obs, obs_weight, min_planarity=0.3, distance_weight=1.0, max_iterations=100, min_change=1.0,
                 max_lm_steps=0):
         """The whole loop in one ABI call (sicp_icp_run).  Returns the list of per-iteration IterResult;
@@ -370,6 +457,12 @@ class Context:
             err.results = out
             raise err
         return out
+
+    def icp_run_batch(self, members):
+        """sicp_icp_run_batch with this context as the first member: see the module-level icp_run_batch."""
+        if not members or members[0][0] is not self:
+            raise ValueError("the batch's first member must be this context")
+        return icp_run_batch(members)
 
     def icp_state(self, pc2_idx=True, dist=True, keep=True, residual=True):
         Q = self._Q

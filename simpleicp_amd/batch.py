@@ -1,0 +1,182 @@
+"""run_batch -- many (fixed, movable) pairs registered in one call, their iterations batched on the GPU.
+
+Each pair gets exactly the preparation ``SimpleICP.run`` gives it (uploads, overlap pre-pass, ``select_n_points``, normals,
+selection masks, the movable cloud's planarity column), on a context of the pool in ``backend`` (one per pair, reused from call
+to call); then ONE ``sicp_icp_run_batch`` call runs every pair's loop (include/simpleicp_hip_batch.h): per iteration one match
+launch and one tail launch per k_icp_tail instantiation for all pairs.  Every pair's result is what ``run()`` returns for it, bit
+for bit; the batch never picks a "best" pair -- several initial guesses of one pair are several members, each reported.
+
+Unlike ``run()`` the inputs are not modified: the pairs' clouds are copied before their preparation.
+"""
+from __future__ import annotations
+
+import inspect
+import logging
+import time
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _lib, backend, dist
+from .icp import SimpleICP, SimpleICPException, _select_and_setup
+from .pointcloud import PointCloud, PointCloudException
+from .rbp import H_from_params, RigidBodyParameters
+
+_log = logging.getLogger(__name__)
+
+# where the last run_batch call spent its time (seconds): the pairs' preparation on the host, the batched loops, the results
+last_run_info: dict = {}
+
+# run()'s keyword arguments and their defaults, read off its signature (a default changed there is the batch's as well)
+_RUN_DEFAULTS = {name: prm.default for name, prm in inspect.signature(SimpleICP.run).parameters.items() if name != "self"}
+
+
+class BatchResult(tuple):
+    """One pair's outcome: unpacks like ``run()``'s ``(H, X_mov_transformed, rbp, residuals)``; besides ``iterations``,
+    ``n_kept`` / ``res_mean`` / ``res_std`` of the last iteration, and ``error`` (None, or the exception ``run()`` would
+    have raised for this pair -- then the four values are None)."""
+
+    def __new__(cls, H=None, X_mov_transformed=None, rbp=None, residuals=None, iterations=0, n_kept=0, res_mean=np.nan,
+                res_std=np.nan, error=None, path=None):
+        self = super().__new__(cls, (H, X_mov_transformed, rbp, residuals))
+        self.iterations, self.n_kept, self.res_mean, self.res_std = iterations, n_kept, res_mean, res_std
+        self.error = error
+        self.path = path          # "batched" / "fallback" (the pair ran through sicp_icp_run: Q > 2048 and the like)
+        return self
+
+    H = property(lambda self: self[0])
+    X_mov_transformed = property(lambda self: self[1])
+    rbp = property(lambda self: self[2])
+    residuals = property(lambda self: self[3])
+
+
+def _cloud(c) -> PointCloud:
+    """A copy of a PointCloud, or a new one from an (n, 3) array."""
+    if isinstance(c, PointCloud):
+        return PointCloud(c.copy(deep=True))
+    X = np.asarray(c, dtype=float)
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError("a cloud must be a PointCloud or an (n, 3) array")
+    return PointCloud(X, columns=["x", "y", "z"])
+
+
+def _quiet(*_args, **_kw):
+    pass
+
+
+def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] = None, return_transformed: bool = True,
+              **run_kwargs) -> list:
+    """Registers every ``(fixed, movable)`` pair of ``pairs`` (PointClouds or (n, 3) arrays) with ``run()``'s keyword arguments
+    ``run_kwargs``, overridden per pair by ``per_pair[i]`` (a dict or None).  Returns one BatchResult per pair, in order.
+    ``return_transformed=False``: no X_mov_transformed (None), no download of the movable clouds."""
+    t0 = time.time()
+    pairs = list(pairs)
+    if per_pair is not None and len(per_pair) != len(pairs):
+        raise ValueError(f"per_pair has {len(per_pair)} entries for {len(pairs)} pairs")
+    if dist.is_distributed():
+        raise SimpleICPException("run_batch does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
+    kws = []
+    for i in range(len(pairs)):
+        kw = dict(_RUN_DEFAULTS)
+        for src in (run_kwargs, (per_pair[i] or {}) if per_pair is not None else {}):
+            unknown = set(src) - set(_RUN_DEFAULTS)
+            if unknown:
+                raise TypeError(f"run_batch got unexpected keyword argument(s) {sorted(unknown)}")
+            kw.update(src)
+        if kw["debug_dirpath"]:
+            raise SimpleICPException("run_batch writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
+        kws.append(kw)
+    if not pairs:
+        return []
+
+    ctxs = backend.get_batch_contexts(len(pairs))
+    out = [None] * len(pairs)
+    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, kw)
+    members = []
+    for i, ((fix, mov), kw) in enumerate(zip(pairs, kws)):
+        ctx = ctxs[i]
+        ctx._corr_owner = None
+        try:
+            pc1, pc2 = _cloud(fix), _cloud(mov)
+            SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
+            obs = np.array(kw["rbp_observed_values"], dtype=float)
+            obs[:3] = obs[:3] * np.pi / 180
+            ow = np.array(kw["rbp_observation_weights"], dtype=float)
+            H = H_from_params(obs)
+            # SimpleICP.run's uploads on one GPU (the fixed cloud behind the caller, the movable one behind it)
+            pc1._upload(ctx, _lib.FIX, background=True)
+            partial = not bool(pc2["selected"].to_numpy().all())
+            msel = pc2.idx_selected if partial else None
+            if partial and not len(msel):
+                raise SimpleICPException("The movable point cloud has no selected points.")
+            n_search = len(msel) if partial else pc2.num_points
+
+            def upload_movable(rows=None, pc2=pc2, ctx=ctx):
+                n = pc2.num_points if rows is None else len(rows)
+                pc2._upload(ctx, _lib.MOV, 0, n, index_base=0, rows=rows)
+
+            sel0 = pc1._selection()
+            pc2._upload(ctx, _lib.MOV, background=True)
+            ctx.upload_wait(_lib.FIX)
+            _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel0, H, kw["correspondences"], kw["neighbors"],
+                              kw["max_overlap_distance"], info=_quiet)
+        except (SimpleICPException, PointCloudException, _lib.BackendError) as e:
+            # what run() would raise for this pair (no overlap, a non-finite coordinate, ...): the pair's error, the others go on
+            out[i] = BatchResult(error=e)
+            continue
+        members.append((ctx, dict(x=obs.copy(), obs=obs, obs_weight=ow, min_planarity=kw["min_planarity"],
+                                  distance_weight=kw["distance_weights"], max_iterations=kw["max_iterations"],
+                                  min_change=kw["min_change"])))
+        prepared.append((i, ctx, pc2, msel, obs, ow))
+
+    t1 = time.time()
+    runs, fallback = members[0][0].icp_run_batch(members) if members else ([], 0)
+    t2 = time.time()
+    for (i, ctx, pc2, msel, obs, ow), r in zip(prepared, runs):
+        out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed)
+    last_run_info.clear()
+    last_run_info.update(pairs=len(pairs), fallback=fallback, prepare_s=t1 - t0, batch_s=t2 - t1, results_s=time.time() - t2)
+    n_err = sum(1 for o in out if o.error is not None)
+    _log.info(f"run_batch: {len(pairs)} pairs ({len(members) - fallback} batched, {fallback} fallback, {n_err} failed) "
+              f"in {time.time() - t0:.3f} seconds")
+    return out
+
+
+def _result(ctx, pc2, msel, obs, ow, r, return_transformed) -> BatchResult:
+    """SimpleICP.run's epilogue for one member: what it returns, or the exception it raises."""
+    path = "fallback" if r.path == _lib.BATCH_PATH_FALLBACK else "batched"
+    whole = r.results
+    if r.status != _lib.OK:
+        if r.status == _lib.ERR_TOO_FEW:
+            err = SimpleICPException(str(_lib.BackendError(r.error, r.status)))
+        else:
+            err = _lib.BackendError(r.error, r.status)
+            err.results = whole
+        last = whole[-1] if whole else None
+        return BatchResult(iterations=len(whole), n_kept=int(last.n_kept) if last else 0, error=err, path=path)
+    rbp = RigidBodyParameters()
+    rbp.set_parameter_attributes_from_list("observed_value", list(obs))
+    rbp.set_parameter_attributes_from_list("observation_weight", list(ow))
+    H = H_from_params(obs)
+    residuals = np.empty(0)
+    R = whole[-1] if whole else None
+    if R is not None:
+        x_start = np.array(whole[-2].x[:]) if len(whole) > 1 else obs.copy()
+        x = np.array(R.x[:])
+        H = np.array(R.H[:]).reshape(4, 4)
+        rbp.set_parameter_attributes_from_list("initial_value", list(x_start))
+        rbp.set_parameter_attributes_from_list("estimated_value", list(x))
+        sigma = ctx.icp_uncertainties()
+        for name, s, free in zip(("alpha1", "alpha2", "alpha3", "tx", "ty", "tz"), sigma, np.isfinite(ow)):
+            if free:
+                getattr(rbp, name).estimated_uncertainty = float(s)
+        _, _, keep, res = ctx.icp_state(pc2_idx=False, dist=False)
+        residuals = res[keep]
+    X_new = None
+    if return_transformed:
+        if msel is not None:
+            pc2._upload(ctx, _lib.MOV)
+        ctx.transform(_lib.MOV, H)
+        X_new, _ = ctx.download_both(_lib.MOV)     # (through the lean contexts' shared pinned ring, like run()'s download)
+    return BatchResult(H, X_new, rbp, residuals, iterations=len(whole), n_kept=int(R.n_kept) if R else 0,
+                       res_mean=R.res_mean if R else np.nan, res_std=R.res_std if R else np.nan, path=path)

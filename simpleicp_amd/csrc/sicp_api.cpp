@@ -205,7 +205,8 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->stage_bg.release(); c->bg_small.release();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { (void)rccl()->CommDestroy(c->comm); c->comm = nullptr; }
-    if (c->h_dl) { (void)hipHostFree(c->h_dl); c->h_dl = nullptr; }
+    if (c->h_dl && !c->dl_shared) (void)hipHostFree(c->h_dl);
+    c->h_dl = nullptr;
     for (auto &e : c->dl_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto &p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto &p : c->pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -218,6 +219,9 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->resid.release(); c->flag.release(); c->keep.release(); c->small.release(); c->ne_partial.release();
     c->lm_bar_buf.release(); c->lm_gsum.release(); c->ticket.release(); c->icp_dev.release(); c->lm_dev.release(); c->resid2.release();
     c->corr_pl.release();
+    c->batch_tab.release(); c->batch_map.release();
+    if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
+    if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->h_rec) (void)hipHostFree(c->h_rec);

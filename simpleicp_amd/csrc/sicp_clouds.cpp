@@ -387,10 +387,34 @@ int upload_end(sicp_ctx *c, int slot) { return cloud_stats(c, slot); }
 constexpr int64_t UPLOAD_STAGED_MAX = 1 << 19;       // (one chunk: ~1.5 ms of host copy at most)
 constexpr long DL_CH = 1L << 19;          // the download's chunks: 512 Ki points = 12 MiB
 constexpr int DL_RING = 4;                // ... in flight: the pinned block is DL_RING x 3 x DL_CH doubles (48 MiB), on first use
+// The ring of the staged uploads and of sicp_cloud_download_both: the ctx's own, or -- a lean ctx (sicp_ctx_lean: the members of
+// run_batch's pool) -- ONE ring the process's lean contexts share, 48 MiB of pinned memory per process instead of per member.  Its
+// users hold shared_ring_lock() for the whole call, and leave no DMA on it behind them.
+namespace {
+std::mutex g_shared_ring_mu;
+double *g_shared_ring = nullptr;
+}
+std::unique_lock<std::mutex> shared_ring_lock(const sicp_ctx *c)
+{
+    return c->dl_shared ? std::unique_lock<std::mutex>(g_shared_ring_mu) : std::unique_lock<std::mutex>();
+}
+int dl_ring(sicp_ctx *c)
+{
+    if (c->h_dl) return SICP_OK;
+    if (c->dl_shared) {
+        if (!g_shared_ring) HIPCHK(hipHostMalloc((void **)&g_shared_ring, (size_t)DL_RING * 3 * DL_CH * sizeof(double), hipHostMallocPortable));
+        c->h_dl = g_shared_ring;
+        return SICP_OK;
+    }
+    HIPCHK(hipHostMalloc((void **)&c->h_dl, (size_t)DL_RING * 3 * DL_CH * sizeof(double), hipHostMallocDefault));
+    return SICP_OK;
+}
+
 int upload_staged(sicp_ctx *c, Cloud &cl, const double *xyz, const double *x, const double *y, const double *z, int64_t n)
 {
     const long CH = DL_CH;
-    if (!c->h_dl) HIPCHK(hipHostMalloc((void **)&c->h_dl, (size_t)DL_RING * 3 * DL_CH * sizeof(double), hipHostMallocDefault));      // (the download's ring; two of its buffers serve here)
+    const auto ring_lock = shared_ring_lock(c);
+    CHK(dl_ring(c));                                   // (the download's ring; two of its buffers serve here)
     for (auto &e : c->dl_ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const long nchunks = (n + CH - 1) / CH;
     for (long ch = 0; ch < nchunks; ++ch) {
@@ -412,6 +436,7 @@ int upload_staged(sicp_ctx *c, Cloud &cl, const double *xyz, const double *x, co
     }
     launch_pad_fill(c->stream, cl.x(), cl.y(), cl.z(), n, cl.npad);
     HIPCHK(hipGetLastError());
+    if (c->dl_shared) HIPCHK(hipStreamSynchronize(c->stream));       // (the next lean ctx may refill the shared ring at once)
     return SICP_OK;
 }
 
@@ -640,7 +665,8 @@ SICP_EXPORT int sicp_cloud_download_both(sicp_ctx *c, int slot, double *xyz_out,
     HIPCHK(hipSetDevice(c->device));
     Cloud &cl = c->cloud[slot];
     const long n = cl.n, CH = std::min<long>(DL_CH, round_up(n, 1024));      // (a small cloud is one chunk of its own size)
-    if (!c->h_dl) HIPCHK(hipHostMalloc((void **)&c->h_dl, (size_t)DL_RING * 3 * DL_CH * sizeof(double), hipHostMallocDefault));
+    const auto ring_lock = shared_ring_lock(c);
+    CHK(dl_ring(c));
     for (auto &e : c->dl_ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const long nchunks = (n + CH - 1) / CH;
     // host threads that fan the chunks out: as many as this process may actually run on (cgroup / affinity limits, not the machine's

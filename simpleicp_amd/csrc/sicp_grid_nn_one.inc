@@ -1,0 +1,239 @@
+// sicp_grid_nn_one.inc -- the search of ONE query by one wave: the body of k_grid_nn's per-query lambda, included textually by
+// k_grid_nn (sicp_grid.hip) and by the batched match k_grid_nn_batch, so that both compile the same tokens (a shared __device__
+// function changed k_grid_nn's register allocation).  Names it uses: the kernel's parameters (st, qx, qy, qz, prev_p2, cell_start,
+// rec, G, H, Hinv, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, post, G2, rec2), the locals lane, tight, approx,
+// cell_box, cell_start2, redo_list, and q, the query.  XFORM, CHAINED: the kernel's template parameters.
+    const double ax = qx[q], ay = qy[q], az = qz[q];      // (issued before the loop state is waited for)
+    double px0 = 0, py0 = 0, pz0 = 0;
+    if (prev_p2) { px0 = prev_p2[3 * q]; py0 = prev_p2[3 * q + 1]; pz0 = prev_p2[3 * q + 2]; }
+    float pnx = 0.f, pny = 0.f, pnz = 0.f, ppl = 0.f;     // the query's normal and planarity (wave-uniform; in flight during the search)
+    if (post.dist) { pnx = post.normals[3 * q]; pny = post.normals[3 * q + 1]; pnz = post.normals[3 * q + 2]; ppl = post.planarity[q]; }
+    if (CHAINED) {
+        H = st->H; Hinv = st->Hinv;
+        if (st->stop) return;
+    }
+    double cxq = ax, cyq = ay, czq = az;                  // query in the cloud's own frame
+    if (XFORM) xf(Hinv, ax, ay, az, cxq, cyq, czq);
+    // covers rounding of H^-1 q and |R^T R - I| ~ 1e-16: distances in the two frames agree to
+    // ~1e-15 * scale; 1e-12 * scale leaves three orders of magnitude
+    const double scale = rmax + (fabs(cxq) + fabs(cyq) + fabs(czq)) + 1.0;     // (1-norm: an upper bound of |q| is all the slack needs)
+    const double slack = 1e-12 * scale;
+    double r_lim = (max_d2 < __builtin_inf()) ? sqrt(max_d2) * (1.0 + 1e-12) + slack : __builtin_inf();
+    bool lim_is_bound = false;                            // r_lim is the distance to a cloud point: that ball is never empty
+    if (prev_p2) {
+        double X = px0, Y = py0, Z = pz0;
+        if (XFORM) { double u, v, w; xf(H, X, Y, Z, u, v, w); X = u; Y = v; Z = w; }
+        const double dx = X - ax, dy = Y - ay, dz = Z - az;
+        const double bnd = fma(dz, dz, fma(dy, dy, dx * dx));
+        if (bnd < __builtin_inf()) {
+            const double rb = sqrt(bnd) * (1.0 + 1e-12) + slack;
+            if (rb < r_lim) { r_lim = rb; lim_is_bound = true; }
+        }
+    }
+    // a bound that spans many cells (first iterations: the estimate still moves by metres) is not searched in one
+    // go: start small and let the first hit shrink the ball
+    double r = 0.75 * G.h;
+    if (r > r_lim || (tight && r_lim < __builtin_inf())) r = r_lim;
+
+    double best = __builtin_inf(), bx = 0, by = 0, bz = 0;
+    uint32_t bidx = 0xffffffffu;
+    unsigned long long n_cand = 0, n_rows = 0;
+    bool last = false;
+    for (int pass = 0; pass < 4096; ++pass) {                 // (ends by itself: the radius doubles until it hits, then one more pass)
+        // A cloud whose density varies by orders of magnitude is binned for its dense core (cells of centimetres) -- and a query whose
+        // answer lies metres away would walk ten thousand rows of that grid.  Such clouds carry a second, COARSE grid over the same
+        // points (cells 8 x as wide): a pass whose ball spans more than a few fine cells runs on it.  Both grids hold every point, so
+        // which one a pass reads changes what it costs, never what it finds.  (One query per wave: the choice is wave-uniform.)
+        const bool cp = cell_start2 != nullptr && r > 4.0 * G.h;
+        const GridGeom &Gp = cp ? G2 : G;
+        const uint32_t *__restrict__ csp = cp ? cell_start2 : cell_start;
+        const double4 *__restrict__ rcp = cp ? rec2 : rec;
+        int lo[3], hi[3];
+        const double c3[3] = {cxq, cyq, czq};
+        bool all = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double fl = floor((c3[a] - r - Gp.mn[a]) * Gp.inv_h - 1e-6);
+            const double fh = floor((c3[a] + r - Gp.mn[a]) * Gp.inv_h + 1e-6);
+            lo[a] = fl < 0.0 ? 0 : (fl > (double)(Gp.dim[a] - 1) ? Gp.dim[a] - 1 : (int)fl);
+            hi[a] = fh < 0.0 ? 0 : (fh > (double)(Gp.dim[a] - 1) ? Gp.dim[a] - 1 : (int)fh);
+            // whole axis covered <=> the ball reaches past both faces of the box
+            all = all && (fl <= 0.0) && (fh >= (double)(Gp.dim[a] - 1));
+        }
+        best = __builtin_inf(); bidx = 0xffffffffu;
+        const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+        const long nrows = (long)ny * nz;
+        // candidates of up to four rows: ranges are wave-uniform, lane l takes record l (+ 64, ...) of each row
+        auto scan_rows = [&](const uint32_t (&rbv)[4], const uint32_t (&rlv)[4]) {
+            uint32_t longest = rlv[0] > rlv[1] ? rlv[0] : rlv[1];
+            { const uint32_t t2 = rlv[2] > rlv[3] ? rlv[2] : rlv[3]; longest = longest > t2 ? longest : t2; }
+            for (uint32_t o = 0; o < longest; o += 64) {              // (rows longer than a wave: dense cells, duplicates)
+                double4 P[4];
+                bool ok[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    ok[u] = o + (uint32_t)lane < rlv[u];
+                    P[u] = rcp[ok[u] ? rbv[u] + o + (uint32_t)lane : 0u];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (!ok[u]) continue;
+                    double X = P[u].x, Y = P[u].y, Z = P[u].z;
+                    if (XFORM) { double a2, b2, c2; xf(H, X, Y, Z, a2, b2, c2); X = a2; Y = b2; Z = c2; }
+                    const double dx = X - ax, dy = Y - ay, dz = Z - az;
+                    const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
+                    const uint32_t oi = (uint32_t)__double_as_longlong(P[u].w);
+                    if (d2 < best || (d2 == best && oi < bidx)) { best = d2; bidx = oi; bx = P[u].x; by = P[u].y; bz = P[u].z; }
+                }
+                if (work) { for (int u = 0; u < 4; ++u) n_cand += ok[u] ? 1 : 0; }
+            }
+        };
+        // The ball, not its bounding cube: a row (cy, cz) is needed only if its (y, z) rectangle comes within r of the query,
+        // and then only the cells within sqrt(r^2 - lb^2) of it along x.  (`all`: the cube covers the whole grid and the pass
+        // ends the search whatever it finds -- then every row is taken in full.)
+        const double r2 = r * r, etol = 1e-6 * Gp.h;
+        double cull2 = __builtin_inf();                           // rows farther than this cannot hold the answer (set by hits)
+        const float inv_ny = 1.0f / (float)ny;
+        const bool few_rows = nrows < (1L << 22);
+        // row rr of the pass's block -> its cells [xl, xh] within the ball (the hit's, once there is one), its record range
+        auto row_range = [&](long rr, uint32_t &b, uint32_t &len, double &lb2, long &row, int &cy, int &cz, int &xl, int &xh) {
+            b = 0; len = 0;
+            int oy, oz;
+            row_split(rr, ny, inv_ny, few_rows, oy, oz);
+            cy = lo[1] + oy; cz = lo[2] + oz;
+            row = ((long)cz * Gp.dim[1] + cy) * Gp.dim[0];
+            xl = lo[0]; xh = hi[0];
+            lb2 = 0.0;
+            if (!all) {
+                const double yl = Gp.mn[1] + (double)cy * Gp.h, zl = Gp.mn[2] + (double)cz * Gp.h;
+                const double dy = fmax(fmax(yl - etol - cyq, cyq - (yl + Gp.h + etol)), 0.0);
+                const double dz = fmax(fmax(zl - etol - czq, czq - (zl + Gp.h + etol)), 0.0);
+                lb2 = fma(dy, dy, dz * dz);
+                const double rem = fmin(r2, cull2) - lb2;
+                if (rem >= 0.0) {
+                    // half-width along x, rounded up (float sqrt + margin; the cell tolerance covers the rest)
+                    const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
+                    const double fl = floor((cxq - hw - Gp.mn[0]) * Gp.inv_h - 1e-6);
+                    const double fh = floor((cxq + hw - Gp.mn[0]) * Gp.inv_h + 1e-6);
+                    const int tl = fl < 0.0 ? 0 : (fl > (double)(Gp.dim[0] - 1) ? Gp.dim[0] - 1 : (int)fl);
+                    const int th = fh < 0.0 ? 0 : (fh > (double)(Gp.dim[0] - 1) ? Gp.dim[0] - 1 : (int)fh);
+                    xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
+                } else {
+                    xh = xl - 1;                                  // outside the ball
+                }
+            }
+            if (xh >= xl && lb2 <= cull2) {
+                b = csp[row + xl];
+                len = csp[row + xh + 1] - b;
+            }
+        };
+        for (long rb = 0; rb < nrows; rb += 64) {
+            uint32_t b = 0, len = 0;
+            double lb2 = __builtin_inf();
+            long row = 0; int cy = 0, cz = 0, xl = 0, xh = -1;
+            if (rb + lane < nrows) {
+                row_range(rb + lane, b, len, lb2, row, cy, cz, xl, xh);
+                // (a later batch of a far search: an earlier batch's hit already bounds the answer)
+                if (cell_box && !cp && len > 0 && cull2 < __builtin_inf()) box_trim_row(cell_box, Gp, row, cy, cz, xl, xh, cxq, cyq, czq, cull2, etol, b, len);
+            }
+            unsigned long long todo = __ballot(len > 0);          // rows of this batch that hold points
+            if (work && len > 0) n_rows += 1;                     // (per-lane tallies, summed once at the end)
+            if (__popcll((long long)todo) > 4) {
+                // many rows (a wide ball: cold start, far query): nearest row first, then drop the rows its hit rules out
+                unsigned long long key = len > 0 ? (unsigned long long)__double_as_longlong(lb2) : ~0ull, mk = key;
+                { unsigned long long o;
+                  o = lane_xor64<32>(mk); mk = o < mk ? o : mk;  o = lane_xor64<16>(mk); mk = o < mk ? o : mk;
+                  o = lane_xor64<8>(mk);  mk = o < mk ? o : mk;  o = lane_xor64<4>(mk);  mk = o < mk ? o : mk;
+                  o = lane_xor64<2>(mk);  mk = o < mk ? o : mk;  o = lane_xor64<1>(mk);  mk = o < mk ? o : mk; }
+                const int j = __ffsll((long long)__ballot(len > 0 && key == mk)) - 1;
+                const uint32_t rbv[4] = {(uint32_t)__builtin_amdgcn_readlane((int)b, j), 0u, 0u, 0u};
+                const uint32_t rlv[4] = {(uint32_t)__builtin_amdgcn_readlane((int)len, j), 0u, 0u, 0u};
+                todo &= ~(1ull << j);
+                scan_rows(rbv, rlv);
+                double wb = best;
+                { double o;
+                  o = lane_xor_f64<32>(wb); wb = o < wb ? o : wb;  o = lane_xor_f64<16>(wb); wb = o < wb ? o : wb;
+                  o = lane_xor_f64<8>(wb);  wb = o < wb ? o : wb;  o = lane_xor_f64<4>(wb);  wb = o < wb ? o : wb;
+                  o = lane_xor_f64<2>(wb);  wb = o < wb ? o : wb;  o = lane_xor_f64<1>(wb);  wb = o < wb ? o : wb; }
+                if (wb < __builtin_inf()) {
+                    const double rbnd = sqrt(wb) * (1.0 + 1e-12) + slack;
+                    const double c2 = rbnd * rbnd;
+                    if (c2 < cull2) {
+                        cull2 = c2;
+                        // the rows still to do: their cells within the HIT's ball, trimmed by the cells' tight boxes
+                        if (cell_box && !cp && ((todo >> lane) & 1ull)) {
+                            row_range(rb + lane, b, len, lb2, row, cy, cz, xl, xh);
+                            if (len > 0) box_trim_row(cell_box, Gp, row, cy, cz, xl, xh, cxq, cyq, czq, cull2, etol, b, len);
+                        }
+                    }
+                    todo &= __ballot(len > 0 && lb2 <= cull2);
+                }
+            }
+            while (todo) {
+                // up to four rows per step: ranges by register broadcast, one record per lane and row
+                uint32_t rbv[4], rlv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    rbv[u] = 0; rlv[u] = 0;
+                    if (todo) {
+                        const int j = __ffsll((long long)todo) - 1;
+                        todo &= todo - 1ull;
+                        rbv[u] = (uint32_t)__builtin_amdgcn_readlane((int)b, j);
+                        rlv[u] = (uint32_t)__builtin_amdgcn_readlane((int)len, j);
+                    }
+                }
+                scan_rows(rbv, rlv);
+            }
+        }
+        // wave-wide lexicographic (d2, original index) minimum: DPP butterfly, every lane ends up with it;
+        // the lane that found it keeps the coordinates
+        const double lbest = best; const uint32_t lidx = bidx;
+#define SICP_LEXMIN_STEP(J)                                                                       \
+        {                                                                                         \
+            const double od = lane_xor_f64<J>(best);                                              \
+            const uint32_t oi = lane_xor32<J>(bidx);                                              \
+            if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; }                 \
+        }
+        SICP_LEXMIN_STEP(32) SICP_LEXMIN_STEP(16) SICP_LEXMIN_STEP(8) SICP_LEXMIN_STEP(4) SICP_LEXMIN_STEP(2) SICP_LEXMIN_STEP(1)
+#undef SICP_LEXMIN_STEP
+        const bool found = bidx != 0xffffffffu;
+        const bool winner = found && lbest == best && lidx == bidx;         // exactly one lane (indices are unique)
+        // sqrt(best) + margin <= r, tested on the squares (no sqrt, no division).  The relative margin is HALF the one a
+        // follow-up radius carries (r = sqrt(best) * (1 + 1e-12) + slack below), so the pass after a shrink terminates.
+        const double r_eff = (r - slack) * (1.0 - 5e-13);
+        const double r_eff2 = r_eff > 0.0 ? r_eff * r_eff * (1.0 - 1e-15) : -1.0;
+        const bool done = (found && best <= r_eff2)           // nothing outside the ball can beat or tie it
+                          || all || r >= r_lim                // searched everything that may qualify
+                          || last                             // this ball was sized to hold the previous pass's hit: it holds the answer
+                          || (approx && found);               // any cloud point will do
+        if (done) {
+            const bool ok = found && (best < max_d2);
+            if (winner || (!found && lane == 0)) {
+                d2_out[q] = ok ? best : __builtin_inf();
+                const int64_t m = ok ? idx_base + (int64_t)bidx : (int64_t)-1;
+                idx_out[q] = m;
+                if (p2_out) {
+                    p2_out[3 * q]     = ok ? bx : 0.0;
+                    p2_out[3 * q + 1] = ok ? by : 0.0;
+                    p2_out[3 * q + 2] = ok ? bz : 0.0;
+                }
+                if (post.dist) post_match(post, H, q, m, ok ? bx : 0.0, ok ? by : 0.0, ok ? bz : 0.0, ax, ay, az, pnx, pny, pnz, ppl);
+                if (post.pack) {
+                    double *r5 = post.pack + 5 * q;
+                    r5[0] = ok ? best : __builtin_inf(); r5[1] = __longlong_as_double((long long)m);
+                    r5[2] = ok ? bx : 0.0; r5[3] = ok ? by : 0.0; r5[4] = ok ? bz : 0.0;
+                }
+                if (post.pack_idx) post.pack_idx[q] = __longlong_as_double((long long)m);
+            }
+            break;
+        }
+        r = found ? sqrt(best) * (1.0 + 1e-12) + slack : 2.0 * r;
+        last = found;
+        if (r > r_lim) r = r_lim;
+    }
+    (void)lim_is_bound;
+    if (work) {
+        n_cand = wsum_u64(n_cand); n_rows = wsum_u64(n_rows);
+        if (lane == 0) { atomicAdd(work, n_cand); atomicAdd(work + 1, n_rows); }
+        if (q == 0 && lane == 0 && !redo_list) atomicAdd(work + 2, 1ull);
+    }

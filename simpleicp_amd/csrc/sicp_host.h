@@ -201,6 +201,7 @@ struct sicp_ctx {
     bool nn16f_min_q_forced = false;   // (the environment named it: no per-cloud adjustment)
                                    // (below: its two extra launches cost more than the filter saves on a machine that is not full)
     double far_move = 0.75;        // SICP_FAR_MOVE: the lean flavour goes first once the estimate moves by less than this many cells per iteration
+    bool dl_shared = false;        // sicp_ctx_lean: h_dl is the ring the process's lean contexts share (sicp_clouds.cpp: dl_ring), not this ctx's
     bool upload_staged = true;     // small uploads go through the pinned buffer (false: every upload a DMA straight out of the caller's arrays)
     bool use_boxes = false;        // SICP_BOXES=1: far searches trim their rows by the cells' tight boxes.  OFF by default: measured (profiles/r5), the
                                    // boxes cut 14-30 % of the candidates and never a microsecond -- DESIGN.md section 4
@@ -263,6 +264,13 @@ struct sicp_ctx {
     bool hsel_dirty = false;
     int nn_group = 0;              // SICP_NN_GROUP=8|16: lanes per query of the many-queries search (0: chosen per launch)
     int chain_depth = 4;           // iterations enqueued ahead of the last record read (two are not enough, four are: profiles/r2/ab_chain_depth.txt)
+    // sicp_icp_run_batch with this ctx as its FIRST member (sicp_batch.hip): the member table, the match's block -> member map followed
+    // by the tail buckets' member lists, and the pinned ring the members' records land in (B x REC_RING x REC_DOUBLES); grown, never shrunk
+    DevBuf<BatchMember> batch_tab;
+    DevBuf<uint32_t> batch_map;
+    double *h_batch_ring = nullptr;
+    long batch_ring_members = 0;
+    hipEvent_t batch_ev = nullptr;   // ... a member's preparation done on its own stream (the batch's stream waits for it)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;
@@ -364,6 +372,12 @@ int knnk_device(sicp_ctx *c, int slot, const double *qsoa, long Q, long qpad, in
                 float *normals_out = nullptr, float *planarity_out = nullptr, bool *fused = nullptr);
 int cloud_stats(sicp_ctx *c, int slot);
 int upload_join(sicp_ctx *c, int slot);
+int loop_state_init(sicp_ctx *c, const sicp_iter_params *P0);
+TailArgs tail_args(const sicp_ctx *c, const sicp_iter_params *P0, double min_change);
+int take_record(sicp_ctx *c, const sicp_iter_params *P0, const double *o, sicp_iter_result *results, int64_t *done_out,
+                double xcur[6], double *last_move, bool *over);
+bool device_tail(const sicp_ctx *c);
+int check_iter_args(sicp_ctx *c, const sicp_iter_params *P);
 
 }  // namespace sicph
 

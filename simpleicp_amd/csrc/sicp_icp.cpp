@@ -220,6 +220,98 @@ int check_iter_args(sicp_ctx *c, const sicp_iter_params *P)
 // (a sharded 6x6 reduction -- gn_shard -- runs there as well: one all-reduce of the 8x8 Gram block per evaluation)
 bool device_tail(const sicp_ctx *c) { return c->solve_mode != 2; }
 
+// ---- pieces of the device-chained loop that the batched loop (sicp_batch.hip) shares --------------------------------
+// the loop state a run starts from (estimate, sin / cos, H(x), its rigid inverse, the weight): staged in c->h_state, enqueued on c->stream
+int loop_state_init(sicp_ctx *c, const sicp_iter_params *P0)
+{
+    IcpDev &hs = *c->h_state;
+    std::memset(&hs, 0, sizeof hs);
+    double H12[12];
+    params_to_H12(P0->x, H12);
+    for (int j = 0; j < 6; ++j) hs.x[j] = P0->x[j];
+    for (int j = 0; j < 3; ++j) { hs.sc[2 * j] = std::sin(P0->x[j]); hs.sc[2 * j + 1] = std::cos(P0->x[j]); }
+    for (int i = 0; i < 12; ++i) hs.H.m[i] = H12[i];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) hs.Hinv.m[4 * i + j] = H12[4 * j + i];
+        hs.Hinv.m[4 * i + 3] = -(H12[i] * H12[3] + H12[4 + i] * H12[7] + H12[8 + i] * H12[11]);
+    }
+    hs.w = (P0->distance_weight > 0) ? P0->distance_weight : -1.0;
+    HIPCHK(hipMemcpyAsync(c->icp_dev.p, &hs, sizeof hs, hipMemcpyHostToDevice, c->stream));
+    return SICP_OK;
+}
+
+TailArgs tail_args(const sicp_ctx *c, const sicp_iter_params *P0, double min_change)
+{
+    const Cloud &cl = c->cloud[SICP_MOV];
+    TailArgs A;
+    for (int j = 0; j < 6; ++j) { A.obs[j] = P0->obs[j]; A.ow[j] = P0->obs_weight[j]; }
+    A.min_change = min_change;
+    A.seq = 0.0;
+    A.min_planarity = (float)P0->min_planarity;
+    A.max_steps = P0->max_lm_steps > 0 ? (int)P0->max_lm_steps : 100;
+    A.Q = (int)c->Q;
+    A.window = c->tail_window ? 1 : 0;
+    A.pl2 = cl.pl_n > 0 ? cl.pl.p : nullptr;
+    A.pl2_n = cl.pl_n;
+    return A;
+}
+
+// an iteration's record `o` (status 0 / 1 / 2) -> results[*done_out] and the ctx's last-iteration state; *over once the run ends
+// there (converged, too few correspondences, not finite).  xcur: the estimate the iteration started from (advanced here).
+int take_record(sicp_ctx *c, const sicp_iter_params *P0, const double *o, sicp_iter_result *results, int64_t *done_out,
+                double xcur[6], double *last_move, bool *over)
+{
+    const long Q = c->Q;
+    const Cloud &cl = c->cloud[SICP_MOV];
+    const bool small_q = Q <= SOLVE_MAX_Q;
+    const int status = (int)o[REC_STATUS];
+    int rc = SICP_OK;
+    sicp_iter_result &R = results[*done_out];
+    std::memset(&R, 0, sizeof R);
+    R.n_queries = Q; R.n_planar = (int64_t)o[0]; R.median = o[1]; R.mad = o[2]; R.n_kept = (int64_t)o[3];
+    R.dist_mean = o[4]; R.dist_std = o[5];
+    for (int j = 0; j < 6; ++j) R.x[j] = o[10 + j];
+    ++*done_out;
+    c->have_iter = true;
+    c->have_last_ne = false;
+    std::memcpy(c->last_x, R.x, sizeof c->last_x);
+    if (status == 1 || R.n_kept < 6) { rc = too_few((long long)R.n_kept); *over = true; return rc; }
+    if (status != 0) { rc = fail(SICP_ERR_NUMERIC, "objective is not finite"); *over = true; return rc; }
+    R.weight_used = o[6]; R.cost = o[7]; R.lm_steps = (int64_t)o[8]; R.ne_evals = (int64_t)o[9];
+    R.res_mean = o[16]; R.res_std = o[17];
+    params_to_H12(R.x, R.H);
+    R.H[12] = 0; R.H[13] = 0; R.H[14] = 0; R.H[15] = 1;
+    {
+        double dt = 0, da = 0;
+        for (int j = 0; j < 3; ++j) { da += (R.x[j] - xcur[j]) * (R.x[j] - xcur[j]); dt += (R.x[3 + j] - xcur[3 + j]) * (R.x[3 + j] - xcur[3 + j]); }
+        *last_move = std::sqrt(dt) + std::sqrt(da) * cl.rmax;
+        c->last_move = *last_move;                    // (a host-driven loop -- one iteration per call -- carries it from call to call)
+    }
+    std::memcpy(xcur, R.x, 6 * sizeof(double));
+    c->last_w = R.weight_used;
+    std::memcpy(c->last_obs, P0->obs, sizeof c->last_obs);
+    std::memcpy(c->last_ow, P0->obs_weight, sizeof c->last_ow);
+    std::memcpy(c->last_ne, o + 20, sizeof c->last_ne);
+    c->have_last_ne = true;
+    c->resid_slot = small_q ? 0 : (int)o[REC_RESID_SLOT];
+    if (small_q) {
+        std::memcpy(c->last_tail_cycles, o + 50, 5 * sizeof(double));
+        c->last_sel_rounds[0] = (long)o[56]; c->last_sel_rounds[1] = (long)o[58];
+        if (o[56] == 0.0 && o[58] == 0.0) ++c->sel_window_hits;
+    }
+    if (c->solve_trace && small_q)
+        std::fprintf(stderr, "[tail] cycles: load+dist %.0f select %.0f (median %.0f in %.0f rounds, MAD %.0f in %.0f) keep %.0f lm %.0f "
+                             "(%lld evals %.0f, %lld steps, solves %.0f, accept %.0f) final %.0f\n",
+                     o[50], o[51], o[55], o[56], o[57], o[58], o[52], o[53], (long long)R.ne_evals, o[59], (long long)R.lm_steps, o[60], o[62], o[54]);
+    if (c->solve_trace && small_q && c->trace_sel)      // (a -DSICP_SEL_FINE_TRACE build: build.build_variant)
+        std::fprintf(stderr, "[sel] median: atomics+barrier %.0f fold+barrier %.0f scan+pick %.0f (more rounds %.0f) gather+barrier %.0f rank %.0f | "
+                             "MAD: %.0f %.0f %.0f (%.0f) %.0f %.0f\n", o[38], o[39], o[40], o[41], o[42], o[43], o[44], o[45], o[46], o[47], o[48], o[49]);
+    if (c->solve_trace && small_q && c->trace_eval)     // (a -DSICP_EVAL_FINE_TRACE build)
+        std::fprintf(stderr, "[eval] rows + LDS writes %.0f barrier %.0f MFMA Gram %.0f block write + barrier %.0f fold %.0f\n", o[38], o[39], o[40], o[41], o[42]);
+    if (o[REC_CONVERGED] != 0.0) *over = true;
+    return rc;
+}
+
 // ---- iterations enqueued back to back, loop state on the device --------------------------------------------------
 // Q <= SOLVE_MAX_Q: match + ONE tail launch per iteration (sicp_tail.hip).  Larger Q: match, distances, rejection,
 // statistics, `lm_evals` multi-workgroup evaluations whose last block advances the solver, and a finishing launch
@@ -248,19 +340,9 @@ int run_device_tail(sicp_ctx *c, const sicp_iter_params *P0, int64_t max_it, dou
     const bool small_q = Q <= SOLVE_MAX_Q;
     const int depth = !grid ? 1 : small_q ? c->chain_depth : std::min(c->chain_depth, 2);
 
+    CHK(loop_state_init(c, P0));
     IcpDev &hs = *c->h_state;
-    std::memset(&hs, 0, sizeof hs);
     double H12[12];
-    params_to_H12(P0->x, H12);
-    for (int j = 0; j < 6; ++j) hs.x[j] = P0->x[j];
-    for (int j = 0; j < 3; ++j) { hs.sc[2 * j] = std::sin(P0->x[j]); hs.sc[2 * j + 1] = std::cos(P0->x[j]); }
-    for (int i = 0; i < 12; ++i) hs.H.m[i] = H12[i];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) hs.Hinv.m[4 * i + j] = H12[4 * j + i];
-        hs.Hinv.m[4 * i + 3] = -(H12[i] * H12[3] + H12[4 + i] * H12[7] + H12[8 + i] * H12[11]);
-    }
-    hs.w = (P0->distance_weight > 0) ? P0->distance_weight : -1.0;
-    HIPCHK(hipMemcpyAsync(c->icp_dev.p, &hs, sizeof hs, hipMemcpyHostToDevice, c->stream));
     if (!small_q) {
         LmDev &hl = *c->h_lm;
         std::memset(&hl, 0, sizeof hl);
@@ -269,15 +351,7 @@ int run_device_tail(sicp_ctx *c, const sicp_iter_params *P0, int64_t max_it, dou
         HIPCHK(hipMemcpyAsync(c->lm_dev.p, &hl, sizeof hl, hipMemcpyHostToDevice, c->stream));
     }
 
-    TailArgs A;
-    for (int j = 0; j < 6; ++j) { A.obs[j] = P0->obs[j]; A.ow[j] = P0->obs_weight[j]; }
-    A.min_change = min_change;
-    A.min_planarity = (float)P0->min_planarity;
-    A.max_steps = P0->max_lm_steps > 0 ? (int)P0->max_lm_steps : 100;
-    A.Q = (int)Q;
-    A.window = c->tail_window ? 1 : 0;
-    A.pl2 = cl.pl_n > 0 ? cl.pl.p : nullptr;
-    A.pl2_n = cl.pl_n;
+    TailArgs A = tail_args(c, P0, min_change);
 
     double seqs[REC_RING];
     double xcur[6]; std::memcpy(xcur, P0->x, sizeof xcur);
@@ -524,49 +598,9 @@ int run_device_tail(sicp_ctx *c, const sicp_iter_params *P0, int64_t max_it, dou
                                     "using the GPU?); the run was stopped and the barrier state reset", (long long)completed);
             continue;
         }
-        sicp_iter_result &R = results[*done_out];
-        std::memset(&R, 0, sizeof R);
-        R.n_queries = Q; R.n_planar = (int64_t)o[0]; R.median = o[1]; R.mad = o[2]; R.n_kept = (int64_t)o[3];
-        R.dist_mean = o[4]; R.dist_std = o[5];
-        for (int j = 0; j < 6; ++j) R.x[j] = o[10 + j];
-        ++completed; ++*done_out;
-        c->have_iter = true;
-        c->have_last_ne = false;
-        std::memcpy(c->last_x, R.x, sizeof c->last_x);
-        if (status == 1 || R.n_kept < 6) { rc = too_few((long long)R.n_kept); over = true; continue; }
-        if (status != 0) { rc = fail(SICP_ERR_NUMERIC, "objective is not finite"); over = true; continue; }
-        R.weight_used = o[6]; R.cost = o[7]; R.lm_steps = (int64_t)o[8]; R.ne_evals = (int64_t)o[9];
-        R.res_mean = o[16]; R.res_std = o[17];
-        params_to_H12(R.x, R.H);
-        R.H[12] = 0; R.H[13] = 0; R.H[14] = 0; R.H[15] = 1;
-        {
-            double dt = 0, da = 0;
-            for (int j = 0; j < 3; ++j) { da += (R.x[j] - xcur[j]) * (R.x[j] - xcur[j]); dt += (R.x[3 + j] - xcur[3 + j]) * (R.x[3 + j] - xcur[3 + j]); }
-            last_move = std::sqrt(dt) + std::sqrt(da) * cl.rmax;
-            c->last_move = last_move;                    // (a host-driven loop -- one iteration per call -- carries it from call to call)
-        }
-        std::memcpy(xcur, R.x, sizeof xcur);
-        c->last_w = R.weight_used;
-        std::memcpy(c->last_obs, P0->obs, sizeof c->last_obs);
-        std::memcpy(c->last_ow, P0->obs_weight, sizeof c->last_ow);
-        std::memcpy(c->last_ne, o + 20, sizeof c->last_ne);
-        c->have_last_ne = true;
-        c->resid_slot = small_q ? 0 : (int)o[REC_RESID_SLOT];
-        if (small_q) {
-            std::memcpy(c->last_tail_cycles, o + 50, 5 * sizeof(double));
-            c->last_sel_rounds[0] = (long)o[56]; c->last_sel_rounds[1] = (long)o[58];
-            if (o[56] == 0.0 && o[58] == 0.0) ++c->sel_window_hits;
-        }
-        if (c->solve_trace && small_q)
-            std::fprintf(stderr, "[tail] cycles: load+dist %.0f select %.0f (median %.0f in %.0f rounds, MAD %.0f in %.0f) keep %.0f lm %.0f "
-                                 "(%lld evals %.0f, %lld steps, solves %.0f, accept %.0f) final %.0f\n",
-                         o[50], o[51], o[55], o[56], o[57], o[58], o[52], o[53], (long long)R.ne_evals, o[59], (long long)R.lm_steps, o[60], o[62], o[54]);
-        if (c->solve_trace && small_q && c->trace_sel)      // (a -DSICP_SEL_FINE_TRACE build: build.build_variant)
-            std::fprintf(stderr, "[sel] median: atomics+barrier %.0f fold+barrier %.0f scan+pick %.0f (more rounds %.0f) gather+barrier %.0f rank %.0f | "
-                                 "MAD: %.0f %.0f %.0f (%.0f) %.0f %.0f\n", o[38], o[39], o[40], o[41], o[42], o[43], o[44], o[45], o[46], o[47], o[48], o[49]);
-        if (c->solve_trace && small_q && c->trace_eval)     // (a -DSICP_EVAL_FINE_TRACE build)
-            std::fprintf(stderr, "[eval] rows + LDS writes %.0f barrier %.0f MFMA Gram %.0f block write + barrier %.0f fold %.0f\n", o[38], o[39], o[40], o[41], o[42]);
-        if (o[REC_CONVERGED] != 0.0) over = true;
+        ++completed;
+        const int rr = take_record(c, P0, o, results, done_out, xcur, &last_move, &over);
+        if (rr != SICP_OK) rc = rr;
     }
     return rc;
 }

@@ -122,6 +122,29 @@ void launch_scatter(hipStream_t s, const double *x, const double *y, const doubl
 // cell_box (nullable): the cells' tight boxes (sicp_grid_dev.h): far searches trim their rows by them
 // a second, coarse grid over the SAME points (clouds whose density varies by orders of magnitude): wide passes of the exact search run on it
 struct GridLevel { GridGeom g; const uint32_t *cell_start; const void *rec; };
+// ---- many runs in one chain (sicp_batch.hip): the member table of a sicp_icp_run_batch call, one entry per member, in device memory.
+// Every launch of the batch reads it: the match finds its member through a per-block map, the tail through its bucket's member list.
+struct BatchMember {
+    IcpDev *st;                                   // the member context's loop state
+    const double *qx, *qy, *qz;                   // its query columns (qpad apart)
+    const float *normals, *planarity;
+    double *m_d2; int64_t *m_idx; double *m_p2;   // the match: d2, matched index, matched point
+    double *dist; uint8_t *flag, *keep; double *resid;
+    const uint32_t *cell_start; const void *rec;  // the movable cloud's grid (cell order records)
+    GridGeom G;                                   // ... its geometry
+    double rmax;
+    int64_t idx_base;
+    const double *prev0;                          // the first launch's bound source: m_p2 when it holds an earlier match, else null
+    double *ring;                                 // this member's REC_RING records in the batch's pinned ring
+    TailArgs A;                                   // (A.seq: the launch's)
+    int64_t max_it;                               // launches from this one on leave the member alone
+    uint32_t blk0, pad;                           // the member's first block of the match launch
+};
+void launch_grid_nn_batch(hipStream_t s, const BatchMember *tab, const uint32_t *blk_member, long blocks, long launch);
+void launch_icp_tail_batch(hipStream_t s, int ept, const BatchMember *tab, const uint32_t *members, long count, long launch, int slot,
+                           double seq);
+int  icp_tail_ept(long Q);                        // the k_icp_tail instantiation launch_icp_tail picks for Q correspondences
+
 constexpr int NN_TIGHT = 1;      // prev_p2 is a bound to search in one go (the nearest point of a subsample), not an old match
 constexpr int NN_APPROX = 2;     // the first hit is good enough: the caller wants a cloud point NEAR the query (a bound), not the nearest
 void launch_grid_nn(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,

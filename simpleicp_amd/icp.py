@@ -55,6 +55,45 @@ def _percent_change(new: float, old: float) -> float:
     return abs((new - old) / old * 100)
 
 
+def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors, max_overlap_distance,
+                      info=None):
+    """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass under
+    the initial H, select_n_points, normals (or pc1's nx, ny, nz, planarity columns), the movable cloud's selected subset and its
+    planarity column, sicp_icp_setup.  Returns the selected rows of pc1.  info: where the progress lines go (the log)."""
+    info = info or _log.info
+    if np.isfinite(max_overlap_distance):
+        info("Consider partial overlap of point clouds ...")
+        if sel is _ALL or len(sel):
+            # both clouds are resident already: only the verdicts cross the host link
+            near = ctx.select_in_range(_lib.FIX, _lib.MOV, None if sel is _ALL else sel, H, float(max_overlap_distance))
+            sel = pc1._keep_selected(sel, near)
+        if not len(sel) > 0:
+            raise SimpleICPException(
+                "Point clouds do not overlap within max_overlap_distance = "
+                f"{max_overlap_distance:.5f}! Consider increasing the value of "
+                "max_overlap_distance."
+            )
+
+    info("Select points for correspondences in fixed point cloud ...")
+    sel = pc1.select_n_points(correspondences, _cur=sel)
+    # (simpleicp.py:174,254 save and restore pc1's selection around every iteration because the
+    # reference's rejections edit it; here the masks live on the device and pc1 is never touched)
+
+    if not set(_ATTRS).issubset(pc1.columns):
+        info("Estimate normals of selected points ...")
+        pc1.estimate_normals(neighbors, _ctx=ctx, _uploaded=True, _sel=sel)
+    normals, planarity = pc1._attributes_of(sel)
+    ctx.upload_wait(_lib.MOV)                # (the movable cloud's verdict -- a non-finite coordinate -- is raised here)
+    if msel is not None:
+        upload_movable(msel)                 # from here on the searched cloud is pc2's selected subset
+    if "planarity" in pc2.columns:
+        # reject_wrt_planarity tests pc2's column as well when it exists (corrpts.py:158-163; NaN fails)
+        rows, vals = pc2._planarity_pairs(msel)
+        ctx.set_planarity(_lib.MOV, vals, rows=rows, n_global=n_search)
+    ctx.icp_setup(sel, normals, planarity)
+    return sel
+
+
 class SimpleICP:
     def __init__(self, verbose: bool = True) -> None:
         self.pc1: Optional[PointCloud] = None
@@ -164,36 +203,8 @@ class SimpleICP:
         if debug_dirpath:
             X_fix, X_mov = pc1.X, pc2.X
 
-        if np.isfinite(max_overlap_distance):
-            _log.info("Consider partial overlap of point clouds ...")
-            if sel is _ALL or len(sel):
-                # both clouds are resident already: only the verdicts cross the host link
-                near = ctx.select_in_range(_lib.FIX, _lib.MOV, None if sel is _ALL else sel, H, float(max_overlap_distance))
-                sel = pc1._keep_selected(sel, near)
-            if not len(sel) > 0:
-                raise SimpleICPException(
-                    "Point clouds do not overlap within max_overlap_distance = "
-                    f"{max_overlap_distance:.5f}! Consider increasing the value of "
-                    "max_overlap_distance."
-                )
-
-        _log.info("Select points for correspondences in fixed point cloud ...")
-        sel = pc1.select_n_points(correspondences, _cur=sel)
-        # (simpleicp.py:174,254 save and restore pc1's selection around every iteration because the
-        # reference's rejections edit it; here the masks live on the device and pc1 is never touched)
-
-        if not set(_ATTRS).issubset(pc1.columns):
-            _log.info("Estimate normals of selected points ...")
-            pc1.estimate_normals(neighbors, _ctx=ctx, _uploaded=True, _sel=sel)
-        normals, planarity = pc1._attributes_of(sel)
-        ctx.upload_wait(_lib.MOV)                # (the movable cloud's verdict -- a non-finite coordinate -- is raised here)
-        if msel is not None:
-            upload_movable(msel)                 # from here on the searched cloud is pc2's selected subset
-        if "planarity" in pc2.columns:
-            # reject_wrt_planarity tests pc2's column as well when it exists (corrpts.py:158-163; NaN fails)
-            rows, vals = pc2._planarity_pairs(msel)
-            ctx.set_planarity(_lib.MOV, vals, rows=rows, n_global=n_search)
-        ctx.icp_setup(sel, normals, planarity)
+        sel = _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors,
+                                max_overlap_distance)
 
         x = obs.copy()
         w = distance_weights
