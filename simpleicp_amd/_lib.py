@@ -40,6 +40,12 @@ BATCH_EXPORTS = ["sicp_batch_version", "sicp_icp_run_batch", "sicp_ctx_lean"]
 BATCH_VERSION = 1
 BATCH_PATH_BATCHED, BATCH_PATH_FALLBACK = 1, 2
 
+# include/simpleicp_hip_device.h: clouds in device memory, a companion ABI with a version of its own as well
+DEVICE_EXPORTS = ["sicp_device_version", "sicp_cloud_upload_strided", "sicp_select_n_device", "sicp_select_positions",
+                  "sicp_cloud_write_strided"]
+DEVICE_VERSION = 1
+DT_F32, DT_F64 = 1, 2
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -156,6 +162,13 @@ def load():
         L.sicp_icp_run_batch.restype = cint
         L.sicp_ctx_lean.argtypes = [vp]
         L.sicp_ctx_lean.restype = cint
+    if all(hasattr(L, name) for name in DEVICE_EXPORTS):
+        L.sicp_cloud_upload_strided.argtypes = [vp, cint, vp, cint, i64, i64, i64, i64]
+        L.sicp_select_n_device.argtypes = [vp, vp, i64, i64, vp, C.POINTER(i64)]
+        L.sicp_select_positions.argtypes = [i64, i64, vp, C.POINTER(i64)]
+        L.sicp_cloud_write_strided.argtypes = [vp, cint, vp, vp, cint, i64, i64]
+        for name in DEVICE_EXPORTS:
+            getattr(L, name).restype = cint
     _lib = L
     return L
 
@@ -195,6 +208,31 @@ def batch_version():
         raise BackendError(f"{LIB_PATH} has no batch entry points ({', '.join(missing)}): it predates include/simpleicp_hip_batch.h; "
                            "rebuild with `python -m simpleicp_amd.build`")
     return L.sicp_batch_version()
+
+
+def device_version():
+    """SICP_DEVICE_VERSION of the loaded library; BackendError when it has no device-cloud entry points."""
+    L = load()
+    missing = [name for name in DEVICE_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise BackendError(f"{LIB_PATH} has no device-cloud entry points ({', '.join(missing)}): it predates "
+                           "include/simpleicp_hip_device.h; rebuild with `python -m simpleicp_amd.build`")
+    v = L.sicp_device_version()
+    if v != DEVICE_VERSION:
+        raise BackendError(f"{LIB_PATH} implements device version {v}, this binding needs {DEVICE_VERSION}")
+    return v
+
+
+def select_positions(m, Q):
+    """The positions among m kept rows that select_n_points(Q) picks (sicp_select_positions; host only): int64 vector."""
+    device_version()
+    L = load()
+    out = np.empty(max(min(int(m), int(Q)), 1), np.int64)
+    cnt = C.c_int64()
+    rc = L.sicp_select_positions(int(m), int(Q), _ptr(out), C.byref(cnt))
+    if rc != OK:
+        raise BackendError(L.sicp_last_error().decode(), rc)
+    return out[:cnt.value]
 
 
 class BatchRun:
@@ -298,6 +336,45 @@ class Context:
         if tuple(xyz.shape) != (n, 3):
             raise ValueError("cloud must have shape (n, 3)")
         self._chk(self._L.sicp_cloud_upload(self._h, slot, _ptr(xyz), n, int(index_base)))
+
+    def upload_strided(self, slot, ptr, dtype, n, row_stride, col_stride, index_base=0):
+        """(n, 3) points of a strided view in device memory (sicp_cloud_upload_strided): ptr a device address, dtype DT_F32 /
+        DT_F64, strides in elements."""
+        device_version()
+        self._chk(self._L.sicp_cloud_upload_strided(self._h, slot, C.c_void_p(int(ptr)), int(dtype), int(n), int(row_stride),
+                                                     int(col_stride), int(index_base)))
+
+    def write_strided(self, slot, H, ptr, dtype, row_stride, col_stride):
+        """The slot's points under H into a strided (n, 3) view in device memory (sicp_cloud_write_strided); the slot is unchanged."""
+        device_version()
+        self._chk(self._L.sicp_cloud_write_strided(self._h, slot, _ptr(_f64(H).reshape(16)), C.c_void_p(int(ptr)), int(dtype),
+                                                   int(row_stride), int(col_stride)))
+
+    def select_n_device(self, mask_ptr, n, Q, sel_ptr):
+        """sicp_select_n_device: rows of a device mask (n bytes; None = all rows) picked as select_n_points(Q) picks them, into
+        device memory at sel_ptr (Q int64).  Returns how many were picked."""
+        device_version()
+        q = C.c_int64()
+        self._chk(self._L.sicp_select_n_device(self._h, None if mask_ptr is None else C.c_void_p(int(mask_ptr)), int(n), int(Q),
+                                               C.c_void_p(int(sel_ptr)), C.byref(q)))
+        return q.value
+
+    def select_in_range_into(self, query_slot, search_slot, H, max_range, out_ptr):
+        """select_in_range over ALL points of query_slot with the verdicts left in device memory (out_ptr: one byte per point)."""
+        Hp = None if H is None else _f64(H).reshape(16)
+        self._chk(self._L.sicp_select_in_range(self._h, query_slot, search_slot, None, self.size(query_slot), _ptr(Hp),
+                                               float(max_range), C.c_void_p(int(out_ptr))))
+
+    def estimate_normals_into(self, slot, sel_ptr, Q, k, normals_ptr, planarity_ptr):
+        """estimate_normals with the selection and both outputs in device memory ((Q, 3) / (Q) float32)."""
+        self._chk(self._L.sicp_estimate_normals(self._h, slot, C.c_void_p(int(sel_ptr)), int(Q), int(k),
+                                                C.c_void_p(int(normals_ptr)), C.c_void_p(int(planarity_ptr)), None))
+
+    def icp_setup_device(self, sel_ptr, Q, normals_ptr, planarity_ptr):
+        """icp_setup from device memory (selection (Q) int64, normals (Q, 3) and planarity (Q) float32)."""
+        self._chk(self._L.sicp_icp_setup(self._h, C.c_void_p(int(sel_ptr)), int(Q), C.c_void_p(int(normals_ptr)),
+                                         C.c_void_p(int(planarity_ptr))))
+        self._Q = int(Q)
 
     def upload_columns(self, slot, x, y, z, index_base=0):
         """x, y, z: contiguous float64 vectors of one length (no (n,3) gather on the host)."""

@@ -6,7 +6,9 @@ to call); then ONE ``sicp_icp_run_batch`` call runs every pair's loop (include/s
 launch and one tail launch per k_icp_tail instantiation for all pairs.  Every pair's result is what ``run()`` returns for it, bit
 for bit; the batch never picks a "best" pair -- several initial guesses of one pair are several members, each reported.
 
-Unlike ``run()`` the inputs are not modified: the pairs' clouds are copied before their preparation.
+Unlike ``run()`` the inputs are not modified: the pairs' clouds are copied before their preparation.  A pair of CUDA torch tensors
+takes the device road of ``run_tensors`` (simpleicp_amd/tensors.py) on its pool context: nothing coordinate-sized crosses the host
+link, its iterations go through the same batched call, and its X_mov_transformed is a device tensor.
 """
 from __future__ import annotations
 
@@ -18,9 +20,9 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib, backend, dist
-from .icp import SimpleICP, SimpleICPException, _select_and_setup
+from .icp import SimpleICP, SimpleICPException, _rbp_and_residuals, _select_and_setup
 from .pointcloud import PointCloud, PointCloudException
-from .rbp import H_from_params, RigidBodyParameters
+from .rbp import H_from_params
 
 _log = logging.getLogger(__name__)
 
@@ -41,7 +43,7 @@ class BatchResult(tuple):
         self = super().__new__(cls, (H, X_mov_transformed, rbp, residuals))
         self.iterations, self.n_kept, self.res_mean, self.res_std = iterations, n_kept, res_mean, res_std
         self.error = error
-        self.path = path          # "batched" / "fallback" (the pair ran through sicp_icp_run: Q > 2048 and the like)
+        self.path = path          # "batched" / "fallback" (the pair ran through sicp_icp_run: Q > 2048 and the like) / "device" (run_tensors)
         return self
 
     H = property(lambda self: self[0])
@@ -66,9 +68,10 @@ def _quiet(*_args, **_kw):
 
 def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] = None, return_transformed: bool = True,
               **run_kwargs) -> list:
-    """Registers every ``(fixed, movable)`` pair of ``pairs`` (PointClouds or (n, 3) arrays) with ``run()``'s keyword arguments
-    ``run_kwargs``, overridden per pair by ``per_pair[i]`` (a dict or None).  Returns one BatchResult per pair, in order.
-    ``return_transformed=False``: no X_mov_transformed (None), no download of the movable clouds."""
+    """Registers every ``(fixed, movable)`` pair of ``pairs`` (PointClouds or (n, 3) arrays, or two CUDA torch tensors as for
+    ``run_tensors``) with ``run()``'s keyword arguments ``run_kwargs``, overridden per pair by ``per_pair[i]`` (a dict or None).
+    Returns one BatchResult per pair, in order.  ``return_transformed=False``: no X_mov_transformed (None), no download of the
+    movable clouds (no egress of a device pair's)."""
     t0 = time.time()
     pairs = list(pairs)
     if per_pair is not None and len(per_pair) != len(pairs):
@@ -88,15 +91,28 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
         kws.append(kw)
     if not pairs:
         return []
+    on_device = [_device_pair(fix, mov) for fix, mov in pairs]
+    if any(on_device):
+        from . import tensors
+        for (fix, mov), d in zip(pairs, on_device):
+            if d:                          # (refused before any device work, like run_tensors' arguments)
+                tensors._check_cloud("a fixed cloud", fix, backend.default_device())
+                tensors._check_cloud("a movable cloud", mov, backend.default_device())
 
     ctxs = backend.get_batch_contexts(len(pairs))
     out = [None] * len(pairs)
-    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, kw)
+    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, device pair: (X_mov, its scratch) or None)
     members = []
     for i, ((fix, mov), kw) in enumerate(zip(pairs, kws)):
         ctx = ctxs[i]
         ctx._corr_owner = None
         try:
+            if on_device[i]:
+                SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
+                obs, ow, _, scratch = tensors.prepare(ctx, fix, mov, kw, _quiet)
+                members.append((ctx, _member_kwargs(obs, ow, kw)))
+                prepared.append((i, ctx, None, None, obs, ow, (mov, scratch)))
+                continue
             pc1, pc2 = _cloud(fix), _cloud(mov)
             SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
             obs = np.array(kw["rbp_observed_values"], dtype=float)
@@ -124,16 +140,14 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
             # what run() would raise for this pair (no overlap, a non-finite coordinate, ...): the pair's error, the others go on
             out[i] = BatchResult(error=e)
             continue
-        members.append((ctx, dict(x=obs.copy(), obs=obs, obs_weight=ow, min_planarity=kw["min_planarity"],
-                                  distance_weight=kw["distance_weights"], max_iterations=kw["max_iterations"],
-                                  min_change=kw["min_change"])))
-        prepared.append((i, ctx, pc2, msel, obs, ow))
+        members.append((ctx, _member_kwargs(obs, ow, kw)))
+        prepared.append((i, ctx, pc2, msel, obs, ow, None))
 
     t1 = time.time()
     runs, fallback = members[0][0].icp_run_batch(members) if members else ([], 0)
     t2 = time.time()
-    for (i, ctx, pc2, msel, obs, ow), r in zip(prepared, runs):
-        out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed)
+    for (i, ctx, pc2, msel, obs, ow, dev), r in zip(prepared, runs):
+        out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev)
     last_run_info.clear()
     last_run_info.update(pairs=len(pairs), fallback=fallback, prepare_s=t1 - t0, batch_s=t2 - t1, results_s=time.time() - t2)
     n_err = sum(1 for o in out if o.error is not None)
@@ -142,8 +156,22 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
     return out
 
 
-def _result(ctx, pc2, msel, obs, ow, r, return_transformed) -> BatchResult:
-    """SimpleICP.run's epilogue for one member: what it returns, or the exception it raises."""
+def _device_pair(fix, mov) -> bool:
+    from .tensors import _is_device_tensor
+    d = (_is_device_tensor(fix), _is_device_tensor(mov))
+    if d[0] != d[1]:
+        raise ValueError("a pair holds one CUDA tensor and one host cloud: both members go on the GPU (run_tensors) or both on the host")
+    return d[0]
+
+
+def _member_kwargs(obs, ow, kw) -> dict:
+    return dict(x=obs.copy(), obs=obs, obs_weight=ow, min_planarity=kw["min_planarity"], distance_weight=kw["distance_weights"],
+                max_iterations=kw["max_iterations"], min_change=kw["min_change"])
+
+
+def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None) -> BatchResult:
+    """SimpleICP.run's epilogue for one member: what it returns, or the exception it raises.  dev: (X_mov, scratch) of a device pair
+    (run_tensors' epilogue: the transformed cloud is a new device tensor)."""
     path = "fallback" if r.path == _lib.BATCH_PATH_FALLBACK else "batched"
     whole = r.results
     if r.status != _lib.OK:
@@ -154,26 +182,18 @@ def _result(ctx, pc2, msel, obs, ow, r, return_transformed) -> BatchResult:
             err.results = whole
         last = whole[-1] if whole else None
         return BatchResult(iterations=len(whole), n_kept=int(last.n_kept) if last else 0, error=err, path=path)
-    rbp = RigidBodyParameters()
-    rbp.set_parameter_attributes_from_list("observed_value", list(obs))
-    rbp.set_parameter_attributes_from_list("observation_weight", list(ow))
-    H = H_from_params(obs)
-    residuals = np.empty(0)
     R = whole[-1] if whole else None
+    H, x_start, x = H_from_params(obs), None, None
     if R is not None:
         x_start = np.array(whole[-2].x[:]) if len(whole) > 1 else obs.copy()
         x = np.array(R.x[:])
         H = np.array(R.H[:]).reshape(4, 4)
-        rbp.set_parameter_attributes_from_list("initial_value", list(x_start))
-        rbp.set_parameter_attributes_from_list("estimated_value", list(x))
-        sigma = ctx.icp_uncertainties()
-        for name, s, free in zip(("alpha1", "alpha2", "alpha3", "tx", "ty", "tz"), sigma, np.isfinite(ow)):
-            if free:
-                getattr(rbp, name).estimated_uncertainty = float(s)
-        _, _, keep, res = ctx.icp_state(pc2_idx=False, dist=False)
-        residuals = res[keep]
+    rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
     X_new = None
-    if return_transformed:
+    if return_transformed and dev is not None:
+        from . import tensors
+        X_new = tensors.transformed(ctx, dev[0], H)
+    elif return_transformed:
         if msel is not None:
             pc2._upload(ctx, _lib.MOV)
         ctx.transform(_lib.MOV, H)

@@ -220,6 +220,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->lm_bar_buf.release(); c->lm_gsum.release(); c->ticket.release(); c->icp_dev.release(); c->lm_dev.release(); c->resid2.release();
     c->corr_pl.release();
     c->batch_tab.release(); c->batch_map.release();
+    c->sel_blk.release(); c->sel_pos.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

@@ -363,6 +363,12 @@ int cloud_stats_on(sicp_ctx *c, int slot, hipStream_t s, unsigned long long *d_s
     HIPCHK(hipMemcpyAsync(h_st, d_st, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (s == c->stream) CHK(sync(c)); else HIPCHK(hipStreamSynchronize(s));
     unsigned long long hk[7]; std::memcpy(hk, h_st, sizeof hk);
+    return cloud_stats_take(c, slot, hk);
+}
+// the slot's statistics from the 7 words of a statistics pass (k_cloud_stats, or k_ingest's in the same pass as the upload)
+int cloud_stats_take(sicp_ctx *c, int slot, const unsigned long long hk[7])
+{
+    Cloud &cl = c->cloud[slot];
     double nn; std::memcpy(&nn, &hk[6], sizeof nn);
     if (!std::isfinite(nn)) {
         cl.n = 0;                                    // like cKDTree (pointcloud.py:161,185): no search structure over NaN / inf

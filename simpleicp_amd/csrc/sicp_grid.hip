@@ -34,19 +34,6 @@ namespace sicp {
 
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
-__device__ __forceinline__ unsigned long long okey(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double wmin_d(double v)
-{
-    v = fmin(v, lane_xor_f64<32>(v)); v = fmin(v, lane_xor_f64<16>(v)); v = fmin(v, lane_xor_f64<8>(v));
-    v = fmin(v, lane_xor_f64<4>(v));  v = fmin(v, lane_xor_f64<2>(v));  v = fmin(v, lane_xor_f64<1>(v));
-    return v;
-}
-
 // One pass over a cloud: out[0..2] = min keys, out[3..5] = max keys (ordered-uint64 image of the doubles),
 // out[6] = bits of the largest squared norm (a NaN sticks: the upload rejects non-finite clouds).
 // Wave reductions are register moves, the block folds in LDS: 7 atomics per BLOCK.

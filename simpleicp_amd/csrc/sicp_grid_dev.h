@@ -1,5 +1,5 @@
 // sicp_grid_dev.h -- device helpers shared by the grid kernels (sicp_grid.hip: the exact searches, the k-NN sweeps; sicp_gridf.hip: the
-// filtered many-queries search, the cells' tight boxes).  Device code only.
+// filtered many-queries search, the cells' tight boxes) and the device-cloud kernels (sicp_device.hip).  Device code only.
 #ifndef SICP_GRID_DEV_H
 #define SICP_GRID_DEV_H
 
@@ -22,6 +22,21 @@ __device__ __forceinline__ uint32_t cell_of(const GridGeom &G, double x, double 
     const int cy = cell_coord(y, G.mn[1], G.inv_h, G.dim[1]);
     const int cz = cell_coord(z, G.mn[2], G.inv_h, G.dim[2]);
     return ((uint32_t)cz * G.dim[1] + cy) * G.dim[0] + cx;
+}
+
+// ordered-uint64 image of a double (unsigned order = numeric order): the bounding-box keys of k_cloud_stats / k_ingest
+__device__ __forceinline__ unsigned long long okey(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// wave-wide minimum (every lane gets it)
+__device__ __forceinline__ double wmin_d(double v)
+{
+    v = fmin(v, lane_xor_f64<32>(v)); v = fmin(v, lane_xor_f64<16>(v)); v = fmin(v, lane_xor_f64<8>(v));
+    v = fmin(v, lane_xor_f64<4>(v));  v = fmin(v, lane_xor_f64<2>(v));  v = fmin(v, lane_xor_f64<1>(v));
+    return v;
 }
 
 // contract (T): rows 0..2 of H applied to a point, this operation order everywhere

@@ -271,6 +271,10 @@ struct sicp_ctx {
     double *h_batch_ring = nullptr;
     long batch_ring_members = 0;
     hipEvent_t batch_ev = nullptr;   // ... a member's preparation done on its own stream (the batch's stream waits for it)
+    // sicp_select_n_device (sicp_device.hip): per-block counts | their offsets | the total (4 bytes per 1 024 points), the Q picked
+    // positions (the kept rows themselves are stream-ordered memory of the call)
+    DevBuf<uint32_t> sel_blk;
+    DevBuf<int64_t> sel_pos;
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;
@@ -371,6 +375,8 @@ int grid_build(sicp_ctx *c, int slot, long icp_queries = -1);
 int knnk_device(sicp_ctx *c, int slot, const double *qsoa, long Q, long qpad, int k, double *d2_out, int64_t *idx_out,
                 float *normals_out = nullptr, float *planarity_out = nullptr, bool *fused = nullptr);
 int cloud_stats(sicp_ctx *c, int slot);
+int cloud_stats_take(sicp_ctx *c, int slot, const unsigned long long hk[7]);
+int upload_begin(sicp_ctx *c, int slot, int64_t n, int64_t index_base);
 int upload_join(sicp_ctx *c, int slot);
 int loop_state_init(sicp_ctx *c, const sicp_iter_params *P0);
 TailArgs tail_args(const sicp_ctx *c, const sicp_iter_params *P0, double min_change);

@@ -55,6 +55,14 @@ def _percent_change(new: float, old: float) -> float:
     return abs((new - old) / old * 100)
 
 
+def _no_overlap(max_overlap_distance) -> SimpleICPException:
+    return SimpleICPException(
+        "Point clouds do not overlap within max_overlap_distance = "
+        f"{max_overlap_distance:.5f}! Consider increasing the value of "
+        "max_overlap_distance."
+    )
+
+
 def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors, max_overlap_distance,
                       info=None):
     """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass under
@@ -68,11 +76,7 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
             near = ctx.select_in_range(_lib.FIX, _lib.MOV, None if sel is _ALL else sel, H, float(max_overlap_distance))
             sel = pc1._keep_selected(sel, near)
         if not len(sel) > 0:
-            raise SimpleICPException(
-                "Point clouds do not overlap within max_overlap_distance = "
-                f"{max_overlap_distance:.5f}! Consider increasing the value of "
-                "max_overlap_distance."
-            )
+            raise _no_overlap(max_overlap_distance)
 
     info("Select points for correspondences in fixed point cloud ...")
     sel = pc1.select_n_points(correspondences, _cur=sel)
@@ -92,6 +96,109 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
         ctx.set_planarity(_lib.MOV, vals, rows=rows, n_global=n_search)
     ctx.icp_setup(sel, normals, planarity)
     return sel
+
+
+def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None):
+    """_select_and_setup for clouds uploaded from device memory (run_tensors, run_batch's device pairs; every point selected, no
+    normals or planarity columns): the same steps with every array they hand on left in device memory -- the overlap verdicts, the
+    kept rows and the picks of select_n_points (sicp_select_n_device), the normals.  alloc(shape, kind) returns a device buffer
+    (kind "u8" / "i64" / "f32") and its address; the buffers are returned and must outlive the run's sicp_icp_setup."""
+    info = info or _log.info
+    mask = mask_p = None
+    if np.isfinite(max_overlap_distance):
+        info("Consider partial overlap of point clouds ...")
+        mask, mask_p = alloc((n_fix,), "u8")
+        ctx.select_in_range_into(_lib.FIX, _lib.MOV, H, float(max_overlap_distance), mask_p)
+    sel, sel_p = alloc((max(int(correspondences), 1),), "i64")
+    Q = ctx.select_n_device(mask_p, n_fix, int(correspondences), sel_p)
+    if mask is not None and Q == 0:
+        raise _no_overlap(max_overlap_distance)
+    info("Select points for correspondences in fixed point cloud ...")
+    info("Estimate normals of selected points ...")
+    nv, nv_p = alloc((Q, 3), "f32")
+    pl, pl_p = alloc((Q,), "f32")
+    ctx.estimate_normals_into(_lib.FIX, sel_p, Q, int(neighbors), nv_p, pl_p)
+    ctx.icp_setup_device(sel_p, Q, nv_p, pl_p)
+    return sel, nv, pl
+
+
+def _iterate(ctx, obs, ow, H, min_planarity, distance_weights, max_iterations, min_change, hooks=None):
+    """The iterations of a run after sicp_icp_setup, with run()'s log lines.  hooks None: ONE sicp_icp_run (same convergence test)
+    whose records are replayed; (before(it, H), after(it, H)): a debug run, one ABI call per iteration with the hooks around it.
+    Returns (R, x_start, x, H, stats, it) of the last iteration (R None when none ran)."""
+    x = obs.copy()
+    w = distance_weights
+    stats = []            # (n, mean, std) of the residuals per iteration
+    R = None
+    x_start = None
+    it = -1
+    _log.info("Start iterations ...")
+
+    def too_few(e):
+        if e.code == _lib.ERR_TOO_FEW:
+            raise SimpleICPException(str(e)) from None
+        raise e
+
+    # without debug dumps nothing on the host needs the intermediate states: the whole loop runs behind
+    # ONE ABI call (sicp_icp_run, same convergence test) and the per-iteration log is replayed below
+    whole, failed = None, None
+    if hooks is None:
+        try:
+            whole = ctx.icp_run(x, obs, ow, min_planarity, w, max_iterations, min_change)
+        except _lib.BackendError as e:
+            if e.code != _lib.ERR_TOO_FEW:
+                raise
+            whole, failed = e.results[:-1], e          # log the iterations before the failing one first
+    for it in range(0, max_iterations if whole is None else len(whole)):
+        if hooks is not None:
+            hooks[0](it, H)
+        x_start = x.copy()
+        if whole is not None:
+            R = whole[it]
+        else:
+            try:
+                R = ctx.icp_iterate(x, obs, ow, min_planarity, w)
+            except _lib.BackendError as e:
+                too_few(e)
+        if hooks is not None:
+            hooks[1](it, H)
+        if w is None:
+            w = R.weight_used                            # frozen after iteration 0 (simpleicp.py:229-234)
+        x = np.array(R.x[:])
+        H = np.array(R.H[:]).reshape(4, 4)
+        stats.append((int(R.n_kept), R.res_mean, R.res_std))
+
+        if it > 0 and SimpleICP._converged(stats[it], stats[it - 1], min_change):
+            _log.info("Convergence criteria fulfilled -> stop iteration!")
+            break
+
+        if it == 0:
+            _log.info(f"{'Iteration':>9s} | {'correspondences':>15s} | {'mean(residuals)':>15s} | "
+                      f"{'std(residuals)':>15s}")
+            _log.info(f"{'orig:0':>9s} | {int(R.n_kept):15d} | {R.dist_mean:15.4f} | {R.dist_std:15.4f}")
+        _log.info(f"{it + 1:9d} | {stats[it][0]:15d} | {stats[it][1]:15.4f} | {stats[it][2]:15.4f}")
+
+    if failed is not None:
+        too_few(failed)
+    return R, x_start, x, H, stats, it
+
+
+def _rbp_and_residuals(ctx, R, obs, ow, x_start, x):
+    """The RigidBodyParameters and the residuals run() returns after its last iteration R (None: no iteration ran)."""
+    rbp = RigidBodyParameters()
+    rbp.set_parameter_attributes_from_list("observed_value", list(obs))
+    rbp.set_parameter_attributes_from_list("observation_weight", list(ow))
+    residuals = np.empty(0)
+    if R is not None:
+        rbp.set_parameter_attributes_from_list("initial_value", list(x_start))
+        rbp.set_parameter_attributes_from_list("estimated_value", list(x))
+        sigma = ctx.icp_uncertainties()
+        for name, s, free in zip(("alpha1", "alpha2", "alpha3", "tx", "ty", "tz"), sigma, np.isfinite(ow)):
+            if free:
+                getattr(rbp, name).estimated_uncertainty = float(s)
+        _, _, keep, res = ctx.icp_state(pc2_idx=False, dist=False)
+        residuals = res[keep]
+    return rbp, residuals
 
 
 class SimpleICP:
@@ -206,75 +313,19 @@ class SimpleICP:
         sel = _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors,
                                 max_overlap_distance)
 
-        x = obs.copy()
-        w = distance_weights
-        stats = []            # (n, mean, std) of the residuals per iteration
-        R = None
-        it = -1
-        _log.info("Start iterations ...")
-        def too_few(e):
-            if e.code == _lib.ERR_TOO_FEW:
-                raise SimpleICPException(str(e)) from None
-            raise e
-
-        # without debug dumps nothing on the host needs the intermediate states: the whole loop runs behind
-        # ONE ABI call (sicp_icp_run, same convergence test) and the per-iteration log is replayed below
-        whole, failed = None, None
-        if not debug_dirpath:
-            try:
-                whole = ctx.icp_run(x, obs, ow, min_planarity, w, max_iterations, min_change)
-            except _lib.BackendError as e:
-                if e.code != _lib.ERR_TOO_FEW:
-                    raise
-                whole, failed = e.results[:-1], e          # log the iterations before the failing one first
-        for it in range(0, max_iterations if whole is None else len(whole)):
-            if debug_dirpath:
+        hooks = None
+        if debug_dirpath:
+            def before(it, H):
                 if it == 0:
                     pc1.write_xyz(Path(debug_dirpath).joinpath(f"iteration{it:03d}_preoptim_pcfix.xyz"))
                 self._write_cloud(Path(debug_dirpath).joinpath(f"iteration{it:03d}_preoptim_pcmov.xyz"), X_mov, H)
-            x_start = x.copy()
-            if whole is not None:
-                R = whole[it]
-            else:
-                try:
-                    R = ctx.icp_iterate(x, obs, ow, min_planarity, w)
-                except _lib.BackendError as e:
-                    too_few(e)
-            if debug_dirpath:
+
+            def after(it, H):
                 self._write_correspondences(ctx, Path(debug_dirpath).joinpath(
                     f"iteration{it:03d}_preoptim_correspondences.xyz"), X_fix, X_mov if msel is None else X_mov[msel], sel, H)
-            if w is None:
-                w = R.weight_used                            # frozen after iteration 0 (simpleicp.py:229-234)
-            x = np.array(R.x[:])
-            H = np.array(R.H[:]).reshape(4, 4)
-            stats.append((int(R.n_kept), R.res_mean, R.res_std))
-
-            if it > 0 and self._converged(stats[it], stats[it - 1], min_change):
-                _log.info("Convergence criteria fulfilled -> stop iteration!")
-                break
-
-            if it == 0:
-                _log.info(f"{'Iteration':>9s} | {'correspondences':>15s} | {'mean(residuals)':>15s} | "
-                          f"{'std(residuals)':>15s}")
-                _log.info(f"{'orig:0':>9s} | {int(R.n_kept):15d} | {R.dist_mean:15.4f} | {R.dist_std:15.4f}")
-            _log.info(f"{it + 1:9d} | {stats[it][0]:15d} | {stats[it][1]:15.4f} | {stats[it][2]:15.4f}")
-
-        if failed is not None:
-            too_few(failed)
-
-        rbp = RigidBodyParameters()
-        rbp.set_parameter_attributes_from_list("observed_value", list(obs))
-        rbp.set_parameter_attributes_from_list("observation_weight", list(ow))
-        residuals = np.empty(0)
-        if R is not None:
-            rbp.set_parameter_attributes_from_list("initial_value", list(x_start))
-            rbp.set_parameter_attributes_from_list("estimated_value", list(x))
-            sigma = ctx.icp_uncertainties()
-            for name, s, free in zip(("alpha1", "alpha2", "alpha3", "tx", "ty", "tz"), sigma, np.isfinite(ow)):
-                if free:
-                    getattr(rbp, name).estimated_uncertainty = float(s)
-            _, _, keep, res = ctx.icp_state(pc2_idx=False, dist=False)
-            residuals = res[keep]
+            hooks = (before, after)
+        R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, min_planarity, distance_weights, max_iterations, min_change, hooks)
+        rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
 
         self._log_result(H, rbp)
 

@@ -1,0 +1,131 @@
+"""run_tensors -- ICP on point clouds that are already torch tensors on the GPU: no coordinate-sized array crosses the host link.
+
+The road (include/simpleicp_hip_device.h): both clouds are read where they lie (k_ingest: any strides, float32 widened exactly to
+float64), the overlap pre-pass leaves its verdicts in device memory, the selection is compacted and picked on the device
+(sicp_select_n_device), the normals and sicp_icp_setup take device buffers, ONE sicp_icp_run runs the loop, and the transformed
+movable cloud is written into a new tensor (k_egress).  What comes back is what ``SimpleICP.run`` returns for the same clouds
+(widened to float64), bit for bit; ``X_mov_transformed`` is a new contiguous device tensor in ``X_mov``'s dtype (float32: the
+float64 result rounded to nearest).  The inputs are never modified.
+
+Stream rule: the library works on its context's own stream.  Before it reads the inputs, that stream waits for torch's CURRENT
+stream on the inputs' device, so whatever torch queued there that writes them comes first (no synchronise needed).  Every library
+call returns complete: when run_tensors returns, the output tensor is finished and any stream may read it.  Work on OTHER torch
+streams that writes an input must be ordered before the call by the caller, as for any torch op on the current stream.
+
+torch is imported here only, on the first call: ``import simpleicp_amd`` stays free of it (a plain run() must not pay for the import;
+dist.py says why).
+"""
+from __future__ import annotations
+
+import logging
+import time
+
+import numpy as np
+
+from . import _lib, backend, dist
+from .icp import SimpleICP, SimpleICPException, _iterate, _rbp_and_residuals, _select_and_setup_device
+from .rbp import H_from_params
+
+_log = logging.getLogger(__name__)
+
+_KINDS = {"u8": "uint8", "i64": "int64", "f32": "float32"}
+
+
+def _is_device_tensor(c) -> bool:
+    """A CUDA torch tensor (told without importing torch: a process that never imported it holds none)."""
+    return type(c).__module__.startswith("torch") and bool(getattr(c, "is_cuda", False))
+
+
+def _checked_kwargs(run_kwargs, who):
+    """run()'s keyword arguments with run()'s defaults, refused as run() / run_batch refuse them."""
+    from .batch import _RUN_DEFAULTS
+    unknown = set(run_kwargs) - set(_RUN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"{who} got unexpected keyword argument(s) {sorted(unknown)}")
+    kw = dict(_RUN_DEFAULTS)
+    kw.update(run_kwargs)
+    if kw["debug_dirpath"]:
+        raise SimpleICPException(f"{who} writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
+    SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
+    return kw
+
+
+def _check_cloud(name, t, device):
+    """An (n, 3) float32 / float64 torch tensor on cuda:<device>; anything else is refused before any device work."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__} (host arrays go through SimpleICP.run() or run_batch)")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name} must be float32 or float64, not {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must have shape (n, 3), not {tuple(t.shape)}")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} is on {t.device}: run_tensors takes clouds on the GPU; clouds in host memory go through "
+                         "SimpleICP.run() or run_batch")
+    if t.device.index != device:
+        raise ValueError(f"{name} is on {t.device}, the library's context on cuda:{device}")
+
+
+def _upload(ctx, slot, t):
+    dt = _lib.DT_F64 if t.element_size() == 8 else _lib.DT_F32
+    ctx.upload_strided(slot, t.data_ptr(), dt, t.shape[0], t.stride(0), t.stride(1))
+
+
+def prepare(ctx, X_fix, X_mov, kw, info):
+    """What a run does up to its first iteration, for a device pair on ctx: the stream wait, both uploads, the device road of
+    _select_and_setup.  Returns (obs, ow, H, scratch) -- scratch: device buffers that must live until the run is over."""
+    import torch
+    obs = np.array(kw["rbp_observed_values"], dtype=float)
+    obs[:3] = obs[:3] * np.pi / 180                       # degree -> rad (simpleicp.py:146-148)
+    ow = np.array(kw["rbp_observation_weights"], dtype=float)
+    H = H_from_params(obs)
+    dev = X_fix.device
+    # the stream rule: the library's stream waits for torch's current stream before it reads anything
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
+
+    def alloc(shape, kind):
+        b = torch.empty(shape, dtype=getattr(torch, _KINDS[kind]), device=dev)
+        return b, b.data_ptr()
+
+    _upload(ctx, _lib.FIX, X_fix)
+    _upload(ctx, _lib.MOV, X_mov)
+    scratch = _select_and_setup_device(ctx, X_fix.shape[0], H, kw["correspondences"], kw["neighbors"],
+                                       kw["max_overlap_distance"], alloc, info=info)
+    return obs, ow, H, scratch
+
+
+def transformed(ctx, X_mov, H):
+    """A new contiguous (n, 3) tensor in X_mov's dtype holding the movable cloud under H (k_egress; the slot stays as it is)."""
+    import torch
+    out = torch.empty((X_mov.shape[0], 3), dtype=X_mov.dtype, device=X_mov.device)
+    ctx.write_strided(_lib.MOV, H, out.data_ptr(), _lib.DT_F64 if out.element_size() == 8 else _lib.DT_F32, 3, 1)
+    return out
+
+
+def run_tensors(X_fix, X_mov, **run_kwargs):
+    """Registers X_mov to X_fix -- (n, 3) float32 / float64 torch tensors on the GPU of the library's context, any strides -- with
+    ``run()``'s keyword arguments.  Returns a BatchResult (path "device") that unpacks as ``(H, X_mov_transformed, rbp,
+    residuals)``: H, rbp and residuals are run()'s host values, X_mov_transformed a new device tensor; it also carries
+    ``iterations``, ``n_kept``, ``res_mean`` and ``res_std``.  Raises what run() raises, with the same messages."""
+    from .batch import BatchResult
+    t_start = time.time()
+    kw = _checked_kwargs(run_kwargs, "run_tensors")
+    if dist.is_distributed():
+        raise SimpleICPException("run_tensors does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
+    device = backend.default_device()
+    _check_cloud("X_fix", X_fix, device)
+    _check_cloud("X_mov", X_mov, device)
+    ctx = backend.get_context()
+    ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
+    dist.detach(ctx)
+    obs, ow, H, scratch = prepare(ctx, X_fix, X_mov, kw, _log.info)
+    R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, kw["min_planarity"], kw["distance_weights"], kw["max_iterations"],
+                                           kw["min_change"])
+    rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
+    SimpleICP._log_result(H, rbp)
+    X_new = transformed(ctx, X_mov, H)
+    del scratch
+    _log.info(f"Finished in {time.time() - t_start:.3f} seconds!")
+    return BatchResult(H, X_new, rbp, residuals, iterations=it + 1, n_kept=int(R.n_kept) if R is not None else 0,
+                       res_mean=R.res_mean if R is not None else np.nan, res_std=R.res_std if R is not None else np.nan,
+                       path="device")
