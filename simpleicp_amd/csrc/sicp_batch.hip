@@ -25,9 +25,7 @@ void set_status(sicp_batch_member &m, int rc)
 bool batchable(sicp_ctx *c, const sicp_batch_member &m)
 {
     if (check_iter_args(c, &m.params) != SICP_OK) return false;         // (joins the slots' background uploads: check_slot)
-    const Cloud &cl = c->cloud[SICP_MOV];
-    if (!device_tail(c) || c->Q > SOLVE_MAX_Q) return false;
-    if (!((c->knn1_mode == 0 || c->knn1_mode == 3) && cl.n < (1LL << 31))) return false;
+    if (!device_tail(c) || c->Q > SOLVE_MAX_Q || !takes_grid_search(c)) return false;
     return !(c->timing || c->count_work || c->host_trace || c->solve_trace);
 }
 
@@ -98,13 +96,10 @@ SICP_EXPORT int sicp_icp_run_batch(sicp_batch_member *mem, int64_t count, int64_
         if (m.max_iterations <= 0) continue;                             // (what sicp_icp_run does: nothing)
         sicp_ctx *c = m.ctx;
         if (!batchable(c, m)) { fallback.push_back(i); continue; }
-        // sicp_icp_run's preamble and run_device_tail's, for this member on its own stream
-        double min_change = std::isnan(m.min_change) ? 0.0 : m.min_change;
-        if (min_change < 0) min_change = 0.0;
-        c->have_corr = false;
-        c->resid_sharded = false;
-        int rc = grid_build(c, SICP_MOV, c->Q);
-        if (rc == SICP_OK) rc = loop_state_init(c, &m.params);
+        // a lone run's preparation, for this member on its own stream
+        MemberRun r;
+        bool grid;                                                       // (true: batchable)
+        int rc = chain_prepare(c, &m.params, &grid, &r.last_move);
         if (rc == SICP_OK && hipEventRecord(c->batch_ev, c->stream) != hipSuccess) rc = fail(SICP_ERR_HIP, "hipEventRecord failed");
         if (rc != SICP_OK) { set_status(m, rc); continue; }
         const Cloud &cl = c->cloud[SICP_MOV];
@@ -117,13 +112,11 @@ SICP_EXPORT int sicp_icp_run_batch(sicp_batch_member *mem, int64_t count, int64_
         e.cell_start = cl.grid.cell_start.p; e.rec = cl.grid.rec.p; e.G = cl.grid.g;
         e.rmax = cl.rmax; e.idx_base = cl.idx_base;
         e.prev0 = c->have_prev_match ? c->m_p2.p : nullptr;
-        e.A = tail_args(c, &m.params, min_change);
+        e.A = tail_args(c, &m.params, run_min_change(m.min_change));
         e.max_it = m.max_iterations;
         tab.push_back(e);
-        MemberRun r;
         r.idx = i;
         std::memcpy(r.xcur, m.params.x, sizeof r.xcur);
-        r.last_move = c->have_prev_match ? c->last_move : std::numeric_limits<double>::infinity();
         r.over = false;
         run.push_back(r);
     }

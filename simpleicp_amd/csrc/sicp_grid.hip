@@ -1993,73 +1993,42 @@ void launch_scatter(hipStream_t s, const double *x, const double *y, const doubl
     hipLaunchKernelGGL(k_scatter, dim3(cdiv(n, 256)), dim3(256), 0, s, x, y, z, ids, n, cursor, (double4 *)rec);
 }
 
-void launch_grid_nn(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,
-                    const GridGeom &G, const uint32_t *cell_start, const void *rec, const Xf *H, const Xf *Hinv, double rmax,
-                    double max_d2, int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out, unsigned long long *work,
-                    bool four_per_wave, const unsigned long long *cell_box, const GridLevel *coarse)
+// One launcher for k_grid_nn and k_grid_nn16 (sicp_internal.h: GridSearch, NnFlavour).  The transform picks XFORM / CHAINED: the
+// chain's loop state, else H by value, else none; EXT is on where an option of k_grid_nn's is live (boxes, coarse twin, redo list).
+void launch_grid_nn(hipStream_t s, const GridSearch &S, NnFlavour flavour)
 {
-    const dim3 grid(cdiv(Q, 4)), block(256);
-    Xf id = {};
-    const GridGeom G2 = coarse ? coarse->g : G;
-    const uint32_t *cs2 = coarse ? coarse->cell_start : nullptr;
-    const double4 *rec2 = coarse ? (const double4 *)coarse->rec : nullptr;
-    const bool ext = cell_box != nullptr || coarse != nullptr;
-    const uint32_t *no_list = nullptr;
-    unsigned *no_count = nullptr;
-    if (four_per_wave) {
-        const dim3 g16(cdiv(Q, 16));
-        if (H)
-            hipLaunchKernelGGL((k_grid_nn16<true, false, 16>), g16, block, 0, s, (const IcpDev *)nullptr, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, (const uint32_t *)nullptr, Q, G, *H, *Hinv, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, 0, PostMatch{});
-        else
-            hipLaunchKernelGGL((k_grid_nn16<false, false, 16>), g16, block, 0, s, (const IcpDev *)nullptr, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, (const uint32_t *)nullptr, Q, G, id, id, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, 0, PostMatch{});
+    const Xf id = {};
+    const Xf &H = S.H ? *S.H : id, &Hinv = S.H ? *S.Hinv : id;
+    const PostMatch pm = S.post ? *S.post : PostMatch{};
+    const double4 *rec = (const double4 *)S.rec;
+    const bool redo = flavour == NN_REDO;
+    const uint32_t *order = redo ? nullptr : S.order;       // (the list is the order)
+    unsigned g;
+    if (redo) {
+        const long want = S.Q / 256;                        // ~1.5 % of the queries at one per wave before the waves loop
+        g = (unsigned)(want < 8 ? 8 : (want > 1024 ? 1024 : want));
+    } else {
+        g = cdiv(S.Q, flavour == NN_LANES8 ? 32 : flavour == NN_LANES16 ? 16 : 4);
+        if (order) g = (g + 7u) & ~7u;
+    }
+    if (flavour == NN_LANES16 || flavour == NN_LANES8) {
+        // (eight lanes per query: chained searches only)
+        const auto kernel = flavour == NN_LANES8 ? k_grid_nn16<true, true, 8>
+                          : S.st ? k_grid_nn16<true, true, 16> : S.H ? k_grid_nn16<true, false, 16> : k_grid_nn16<false, false, 16>;
+        hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, S.st, S.qx, S.qy, S.qz, S.prev_p2, S.cell_start, rec, order, S.Q, S.G, H, Hinv,
+                           S.rmax, S.max_d2, S.idx_base, S.d2, S.idx, S.p2, S.work, S.flags & NN_TIGHT, pm);
         return;
     }
-    if (H)
-        if (ext) hipLaunchKernelGGL((k_grid_nn<true, false, true>), grid, block, 0, s, (const IcpDev *)nullptr, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, (const uint32_t *)nullptr, Q, G, *H,
-                           *Hinv, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, 0, PostMatch{}, cell_box, G2, cs2, rec2, no_list, no_count, no_count);
-        else hipLaunchKernelGGL((k_grid_nn<true, false, false>), grid, block, 0, s, (const IcpDev *)nullptr, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, (const uint32_t *)nullptr, Q, G, *H,
-                           *Hinv, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, 0, PostMatch{}, cell_box, G2, cs2, rec2, no_list, no_count, no_count);
-    else
-        if (ext) hipLaunchKernelGGL((k_grid_nn<false, false, true>), grid, block, 0, s, (const IcpDev *)nullptr, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, (const uint32_t *)nullptr, Q, G, id,
-                           id, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, 0, PostMatch{}, cell_box, G2, cs2, rec2, no_list, no_count, no_count);
-        else hipLaunchKernelGGL((k_grid_nn<false, false, false>), grid, block, 0, s, (const IcpDev *)nullptr, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, (const uint32_t *)nullptr, Q, G, id,
-                           id, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, 0, PostMatch{}, cell_box, G2, cs2, rec2, no_list, no_count, no_count);
-}
-
-// the match of a chained iteration: transform taken from the loop state on the device
-void launch_grid_nn_chained(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,
-                            const GridGeom &G, const uint32_t *cell_start, const void *rec, const IcpDev *st, double rmax,
-                            int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out, unsigned long long *work,
-                            const uint32_t *order, bool four_per_wave, int flags, const PostMatch *post, bool eight_per_wave,
-                            const unsigned long long *cell_box, const GridLevel *coarse)
-{
-    Xf id = {};
-    const GridGeom G2 = coarse ? coarse->g : G;
-    const uint32_t *cs2 = coarse ? coarse->cell_start : nullptr;
-    const double4 *rec2 = coarse ? (const double4 *)coarse->rec : nullptr;
-    PostMatch pm = {};
-    if (post) pm = *post;
-    if (four_per_wave) {
-        unsigned g16 = cdiv(Q, 16);
-        if (order) g16 = (g16 + 7u) & ~7u;
-        if (eight_per_wave) {
-            unsigned g8 = cdiv(Q, 32);
-            if (order) g8 = (g8 + 7u) & ~7u;
-            hipLaunchKernelGGL((k_grid_nn16<true, true, 8>), dim3(g8), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, order, Q, G, id, id, rmax, (double)__builtin_inf(), idx_base, d2_out, idx_out, p2_out, work, flags & NN_TIGHT, pm);
-            return;
-        }
-        hipLaunchKernelGGL((k_grid_nn16<true, true, 16>), dim3(g16), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, order, Q, G, id, id, rmax, (double)__builtin_inf(), idx_base, d2_out, idx_out, p2_out, work, flags & NN_TIGHT, pm);
-        return;
-    }
-    unsigned g = cdiv(Q, 4);
-    if (order) g = (g + 7u) & ~7u;
+    const GridLevel *c2 = S.coarse;
     // (the plain instantiation unless an option is live: see the kernel's EXT parameter)
-    if (cell_box != nullptr || coarse != nullptr)
-        hipLaunchKernelGGL((k_grid_nn<true, true, true>), dim3(g), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, order, Q, G, id, id, rmax, (double)__builtin_inf(), idx_base, d2_out, idx_out, p2_out, work, flags, pm,
-                           cell_box, G2, cs2, rec2, (const uint32_t *)nullptr, (const unsigned *)nullptr, (unsigned *)nullptr);
-    else
-        hipLaunchKernelGGL((k_grid_nn<true, true, false>), dim3(g), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, order, Q, G, id, id, rmax, (double)__builtin_inf(), idx_base, d2_out, idx_out, p2_out, work, flags, pm,
-                           cell_box, G2, cs2, rec2, (const uint32_t *)nullptr, (const unsigned *)nullptr, (unsigned *)nullptr);
+    const bool ext = redo || S.cell_box != nullptr || c2 != nullptr;
+    const auto kernel = S.st ? (ext ? k_grid_nn<true, true, true> : k_grid_nn<true, true, false>)
+                      : S.H  ? (ext ? k_grid_nn<true, false, true> : k_grid_nn<true, false, false>)
+                             : (ext ? k_grid_nn<false, false, true> : k_grid_nn<false, false, false>);
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, S.st, S.qx, S.qy, S.qz, S.prev_p2, S.cell_start, rec, order, S.Q, S.G, H, Hinv,
+                       S.rmax, S.max_d2, S.idx_base, S.d2, S.idx, S.p2, S.work, S.flags, pm, S.cell_box, c2 ? c2->g : S.G,
+                       c2 ? c2->cell_start : nullptr, c2 ? (const double4 *)c2->rec : nullptr, redo ? (const uint32_t *)S.redo_list : nullptr,
+                       redo ? (const unsigned *)S.redo_count : nullptr, redo ? S.redo_clear : nullptr);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2103,32 +2072,6 @@ __global__ __launch_bounds__(256) void k_grid_nn_batch(const BatchMember *__rest
 void launch_grid_nn_batch(hipStream_t s, const BatchMember *tab, const uint32_t *blk_member, long blocks, long launch)
 {
     hipLaunchKernelGGL(k_grid_nn_batch, dim3((unsigned)blocks), dim3(256), 0, s, tab, blk_member, launch);
-}
-
-// The exact one-wave-per-query search over a LIST of queries: what the filtered many-queries kernel (sicp_gridf.hip) would not
-// answer itself.  The launch cannot know how long the list is -- a few hundred waves share it; an empty list costs a launch that
-// exits at once.  st: the chain's loop state (then H, Hinv are ignored), else H (nullable: no transform).
-void launch_grid_nn_redo(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,
-                         const GridGeom &G, const uint32_t *cell_start, const void *rec, const IcpDev *st, const Xf *H, const Xf *Hinv,
-                         double rmax, double max_d2, int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out,
-                         unsigned long long *work, int flags, const PostMatch *post, const unsigned long long *cell_box,
-                         const uint32_t *redo_list, const unsigned *redo_count, unsigned *redo_clear, const GridLevel *coarse)
-{
-    Xf id = {};
-    const GridGeom G2 = coarse ? coarse->g : G;
-    const uint32_t *cs2 = coarse ? coarse->cell_start : nullptr;
-    const double4 *rec2 = coarse ? (const double4 *)coarse->rec : nullptr;
-    PostMatch pm = {};
-    if (post) pm = *post;
-    long want = Q / 256;                                   // ~1.5 % of the queries at one per wave before the waves loop
-    const unsigned g = (unsigned)(want < 8 ? 8 : (want > 1024 ? 1024 : want));
-    const uint32_t *no_order = nullptr;
-    if (st)
-        hipLaunchKernelGGL((k_grid_nn<true, true, true>), dim3(g), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, no_order, Q, G, id, id, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, flags, pm, cell_box, G2, cs2, rec2, redo_list, redo_count, redo_clear);
-    else if (H)
-        hipLaunchKernelGGL((k_grid_nn<true, false, true>), dim3(g), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, no_order, Q, G, *H, *Hinv, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, flags, pm, cell_box, G2, cs2, rec2, redo_list, redo_count, redo_clear);
-    else
-        hipLaunchKernelGGL((k_grid_nn<false, false, true>), dim3(g), dim3(256), 0, s, st, qx, qy, qz, prev_p2, cell_start, (const double4 *)rec, no_order, Q, G, id, id, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, flags, pm, cell_box, G2, cs2, rec2, redo_list, redo_count, redo_clear);
 }
 
 void launch_stride_sample(hipStream_t s, const double *x, const double *y, const double *z, long n, long stride, long m, long mpad,

@@ -510,26 +510,19 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
     }
 }
 
-void launch_grid_nn16f(hipStream_t s, int lanes_per_query, bool far, const IcpDev *st, const void *qrec, void *pslot, long Q,
-                       const GridGeom &G, const double c0[3], double eps_p, const uint32_t *cell_start,
-                       const void *recf, const void *rec, bool xcd_order, const Xf *H,
-                       const Xf *Hinv, double rmax, double max_d2, int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out,
-                       unsigned long long *work, int flags, uint8_t *state, uint32_t *redo_list, unsigned *redo_count)
+void launch_grid_nn16f(hipStream_t s, const GridSearch &S, int lanes_per_query, bool far)
 {
-    Xf id = {};
+    const Xf id = {};
     FilterGeom F;
-    for (int a = 0; a < 3; ++a) F.c0[a] = c0[a];
-    F.eps_p = eps_p;
-    const int has_H = H ? 1 : 0;
-    unsigned g = lanes_per_query == 8 ? cdivf(Q, 32) : cdivf(Q, 16);
+    for (int a = 0; a < 3; ++a) F.c0[a] = S.c0[a];
+    F.eps_p = S.eps_p;
+    const bool eight = lanes_per_query == 8, xcd_order = S.order != nullptr;
+    unsigned g = eight ? cdivf(S.Q, 32) : cdivf(S.Q, 16);
     if (xcd_order) g = (g + 7u) & ~7u;
-#define SICP_NN16F_LAUNCH(GS_, FAR_)                                                                                                       \
-    hipLaunchKernelGGL((k_grid_nn16f<GS_, FAR_>), dim3(g), dim3(256), 0, s, st, (const double4 *)qrec, (double4 *)pslot, cell_start,       \
-                       (const float4 *)recf, (const double4 *)rec, Q, G, F, H ? *H : id, Hinv ? *Hinv : id, has_H, rmax, max_d2, \
-                       idx_base, d2_out, idx_out, p2_out, work, flags, xcd_order ? 1 : 0, state, redo_list, redo_count)
-    if (lanes_per_query == 8) { if (far) SICP_NN16F_LAUNCH(8, true); else SICP_NN16F_LAUNCH(8, false); }
-    else { if (far) SICP_NN16F_LAUNCH(16, true); else SICP_NN16F_LAUNCH(16, false); }
-#undef SICP_NN16F_LAUNCH
+    const auto kernel = eight ? (far ? k_grid_nn16f<8, true> : k_grid_nn16f<8, false>) : (far ? k_grid_nn16f<16, true> : k_grid_nn16f<16, false>);
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, S.st, (const double4 *)S.qrec, (double4 *)S.pslot, S.cell_start,
+                       (const float4 *)S.recf, (const double4 *)S.rec, S.Q, S.G, F, S.H ? *S.H : id, S.Hinv ? *S.Hinv : id, S.H ? 1 : 0, S.rmax,
+                       S.max_d2, S.idx_base, S.d2, S.idx, S.p2, S.work, S.flags, xcd_order ? 1 : 0, S.state, S.redo_list, S.redo_count);
 }
 
 }  // namespace sicp

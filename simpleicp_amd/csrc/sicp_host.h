@@ -305,7 +305,44 @@ inline long filter_min_q(const sicp_ctx *c, bool nonuniform)
 {
     return (nonuniform && !c->nn16f_min_q_forced && c->nn16f_min_q > 65536) ? 65536 : c->nn16f_min_q;
 }
+// does a chained run match by the pruned exact search on the static grid?  (it serves every rigid H, i.e. every H(x) of the loop)
+inline bool takes_grid_search(const sicp_ctx *c) { return (c->knn1_mode == 0 || c->knn1_mode == 3) && c->cloud[SICP_MOV].n < (1LL << 31); }
+// sicp_icp_run's convergence threshold as the device tail takes it (negative there means "no test": the single-iteration API's)
+inline double run_min_change(double min_change) { return std::isnan(min_change) || min_change < 0 ? 0.0 : min_change; }
+// does a search of n queries on this grid ask for the float32 filter (sicp_gridf.hip)?  (whether float32 can hold the cloud is known
+// once its companions are built: Grid::filter_ok)
+inline bool wants_filter(const sicp_ctx *c, const Grid &gr, long n)
+{
+    return n > 0 && n >= c->nn16_min_q && n >= filter_min_q(c, gr.nonuniform) && c->nn16_filter != 0;
+}
+// a GridSearch's level: this grid, with its float32 companion
+inline void set_level(GridSearch &S, const Grid &gr)
+{
+    S.G = gr.g; S.cell_start = gr.cell_start.p; S.rec = gr.rec.p; S.recf = gr.recf.p; S.c0 = gr.c0; S.eps_p = gr.eps_p;
+}
+// the search S on the cloud's subsample instead, for any of its points near the query (NN_APPROX): a bound for the search proper
+inline GridSearch bound_search(GridSearch S, const Grid &sub, double *d2, int64_t *idx, double *p2)
+{
+    set_level(S, sub);
+    S.coarse = nullptr; S.cell_box = nullptr; S.idx_base = 0; S.d2 = d2; S.idx = idx; S.p2 = p2; S.work = nullptr; S.flags = NN_APPROX;
+    return S;
+}
 namespace sicph {
+
+// The filtered many-queries search (sicp_gridf.hip) of S.Q queries, ties and all: see filtered_search (sicp_search.cpp).  What its two
+// users -- a stand-alone search, a chained iteration's match -- do differently is named here and decided by them.
+struct FilteredSearch {
+    GridSearch S;                  // by-query columns, the level (set_level), coarse twin / boxes, transform, outputs, work;
+                                   // S.prev_p2 + redo_flags: what bounds the exact redo of the ties
+    DevBuf<double> *q_slot, *p_slot;   // the slot-ordered copies of the queries and their bounds: the run's own or a stand-alone search's
+    bool fill_slots;               // ... are (re)written first, in S.order, bounds from slot_prev (null: none)
+    const double *slot_prev;
+    const Grid *cold;              // nullable: the subsample's grid -- a cold pre-pass leaves its nearest point in the slots as the bound
+    int lanes;                     // lanes per query: 16 or 8
+    bool all_far;                  // no lean flavour first: the full one takes all slots
+    int redo_flags;
+};
+int filtered_search(sicp_ctx *c, const FilteredSearch &F);
 
 struct Timed {
     sicp_ctx *c; EventPair ev; bool on;
@@ -379,6 +416,7 @@ int cloud_stats_take(sicp_ctx *c, int slot, const unsigned long long hk[7]);
 int upload_begin(sicp_ctx *c, int slot, int64_t n, int64_t index_base);
 int upload_join(sicp_ctx *c, int slot);
 int loop_state_init(sicp_ctx *c, const sicp_iter_params *P0);
+int chain_prepare(sicp_ctx *c, const sicp_iter_params *P0, bool *grid, double *last_move);
 TailArgs tail_args(const sicp_ctx *c, const sicp_iter_params *P0, double min_change);
 int take_record(sicp_ctx *c, const sicp_iter_params *P0, const double *o, sicp_iter_result *results, int64_t *done_out,
                 double xcur[6], double *last_move, bool *over);

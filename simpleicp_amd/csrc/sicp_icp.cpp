@@ -72,10 +72,6 @@ bool spd_solve(int m, double *A, double *b)
 }
 
 
-}  // namespace sicph
-
-namespace sicph {
-
 // median / MAD rejection + keep mask + kept statistics for Q > REJECT_MAX_Q: ONE launch with grid barriers
 int reject_select(sicp_ctx *c, long Q, double *host_out, double seq, const IcpDev *st)
 {
@@ -114,10 +110,6 @@ int barrier_timed_out(sicp_ctx *c)
                               "GPU?); the barrier state was reset");
 }
 
-
-}  // namespace sicph
-
-namespace sicph {
 
 int normal_eq_host(sicp_ctx *c, const double x[6], bool write_resid, bool allow_shard, double out[30])
 {
@@ -320,289 +312,332 @@ int take_record(sicp_ctx *c, const sicp_iter_params *P0, const double *o, sicp_i
 // convergence verdict); with the grid search the match kernel takes its transform from that state too, so
 // `chain_depth` iterations are in flight ahead of the record the host is reading and nothing waits for a host
 // round trip.  Launches after the end of the run (converged / failed) see the stop flag and exit at once.
-// min_change < 0: no convergence test.
-int run_device_tail(sicp_ctx *c, const sicp_iter_params *P0, int64_t max_it, double min_change, sicp_iter_result *results,
-                    int64_t *done_out)
+// run_device_tail drives: per iteration plan_match decides, enqueue_match / _exchange / _tail launch, pump_record reads a record.
+
+// what a chained run does before its first launch; *last_move: how far the last completed iteration moved the estimate, as a
+// displacement at the cloud's edge (translation + rotation x radius) -- unknown (= far) until a cold run's first record is in,
+// the last run's for a run that continues from an earlier match
+int chain_prepare(sicp_ctx *c, const sicp_iter_params *P0, bool *grid, double *last_move)
 {
-    const long Q = c->Q;
-    Cloud &cl = c->cloud[SICP_MOV];
-    *done_out = 0;
-    if (max_it <= 0) return SICP_OK;
     c->have_corr = false;
     c->resid_sharded = false;
-    // the pruned exact search on the static grid serves every rigid H, i.e. every H(x) of the loop
-    const bool grid = (c->knn1_mode == 0 || c->knn1_mode == 3) && cl.n < (1LL << 31);
-    if (grid) {
-        long lo0 = 0, cnt0 = Q;
-        if (c->collective() && c->partition == SICP_PART_QUERIES) cnt0 = query_slice(c, Q, &lo0);      // (this rank's share selects the kernel)
+    *grid = takes_grid_search(c);
+    if (*grid) {
+        long lo0 = 0, cnt0 = c->Q;
+        if (c->collective() && c->partition == SICP_PART_QUERIES) cnt0 = query_slice(c, c->Q, &lo0);      // (this rank's share selects the kernel)
         CHK(grid_build(c, SICP_MOV, cnt0));
     }
-    const bool small_q = Q <= SOLVE_MAX_Q;
-    const int depth = !grid ? 1 : small_q ? c->chain_depth : std::min(c->chain_depth, 2);
-
     CHK(loop_state_init(c, P0));
-    IcpDev &hs = *c->h_state;
-    double H12[12];
-    if (!small_q) {
+    if (c->Q > SOLVE_MAX_Q) {             // the larger-Q solver chain's state (sicp_lm.hip), from the loop state just staged
+        const IcpDev &hs = *c->h_state;
         LmDev &hl = *c->h_lm;
         std::memset(&hl, 0, sizeof hl);
         for (int j = 0; j < 6; ++j) { hl.x[j] = hl.xt[j] = hs.x[j]; hl.sc[j] = hl.sct[j] = hs.sc[j]; }
         hl.w = hs.w; hl.first = 1;
         HIPCHK(hipMemcpyAsync(c->lm_dev.p, &hl, sizeof hl, hipMemcpyHostToDevice, c->stream));
     }
+    *last_move = c->have_prev_match ? c->last_move : std::numeric_limits<double>::infinity();
+    return SICP_OK;
+}
 
-    TailArgs A = tail_args(c, P0, min_change);
+namespace {
 
-    double seqs[REC_RING];
-    double xcur[6]; std::memcpy(xcur, P0->x, sizeof xcur);
-    // how far the last completed iteration moved the estimate, as a displacement at the cloud's edge (translation + rotation x radius);
-    // unknown (= far) until a cold run's first record is in, zero for a run that continues from an earlier match
-    double last_move = c->have_prev_match ? c->last_move : std::numeric_limits<double>::infinity();
+// what run_device_tail carries from iteration to iteration
+struct ChainRun {
+    TailArgs A;
+    double seqs[REC_RING];        // the tickets of the launches in flight
+    double xcur[6];               // the estimate the next record's iteration started from
+    double last_move;             // (chain_prepare; then take_record's)
     int64_t launched = 0, completed = 0;
-    const bool cold_start = !c->have_prev_match;      // no earlier match of these queries to bound the first searches
+    bool grid;                    // the match: grid search, else a brute-force flavour
+    bool cold_start;              // no earlier match of these queries to bound the first searches
     bool over = false;
-    int rc = SICP_OK;
-    const bool htrace = c->host_trace;
-    while (true) {
-        while (launched < max_it && launched - completed < depth && !over) {
-            const auto h0 = std::chrono::steady_clock::now();
-            const double *prev = c->have_prev_match ? c->m_p2.p : nullptr;
-            const bool qshard = c->collective() && c->partition == SICP_PART_QUERIES;
-            bool post_done = false;             // distances + planarity verdicts already written by the match kernel
-            bool packed = false;                // ... the exchange's packed records
-            if (grid) {
-                // (query shards: this rank searches its slice of the queries in the whole cloud, results land in
-                // their place in the full arrays)
-                long lo = 0, cnt = Q;
-                if (qshard) cnt = query_slice(c, Q, &lo);
-                c->last_match_kernel = (cnt >= c->nn16_min_q && (!cl.grid.nonuniform || cnt >= filter_min_q(c, true))) ? 5 : 2;
-                const bool ordered = c->order_min_q > 0 && cnt >= c->order_min_q;
-                if (ordered) CHK(query_order_build(c, lo, cnt, cl.grid.g.h));
-                // A search without a useful bound (the run's first iterations: no previous match, or one made under an estimate
-                // that was metres off) first asks the cloud's SUBSAMPLE for its nearest point: a cloud point, so a bound, and
-                // close enough to the answer that the real search goes straight to that radius instead of doubling its way out.
-                const bool coarse = cold_start && launched < c->coarse_iters && cl.n >= c->coarse_min_n && cnt > 0;
-                if (coarse) {
-                    CHK(subsample_build(c, SICP_MOV));
-                    CHK(c->bound_p2.reserve((size_t)3 * Q)); CHK(c->bound_d2.reserve(Q)); CHK(c->bound_idx.reserve(Q));
-                }
-                // EIGHT queries per wave (8 lanes each) once the query set is large and cells are small: twice the independent
-                // requests per wave in flight (0.69 -> 0.62 ms per 1 M queries on 10 M points); not with long rows (C5 sizes: the cell
-                // table's limit leaves 25 points per cell, 8 lanes need twice the steps: 2.07 -> 2.53 ms per step) nor below ~200 k
-                // queries (too few waves to fill the machine)
-                const bool eight = c->nn_group ? c->nn_group == 8 : (cnt >= 196608 && !cl.grid.cap_limited && cl.grid.avg_per_cell <= 20.0);
-                GridLevel coarse_lv; const GridLevel *coarse_grid = nullptr;
-                CHK(grid_coarse_level(c, SICP_MOV, &coarse_lv, &coarse_grid));
-                // (a nonuniform cloud: one wave per query -- 64 rows per batch, the coarse grid for wide passes -- until the filtered search takes over)
-                const bool many_q = cnt >= c->nn16_min_q && (!cl.grid.nonuniform || cnt >= filter_min_q(c, true));
-                // far searches (a run's first iterations) trim their rows by the tight boxes of the cells; large query sets are
-                // searched through the float32 filter (sicp_gridf.hip) when float32 can hold the cloud
-                const bool boxes = c->use_boxes && cnt > 0;
-                bool filt = many_q && c->nn16_filter != 0 && cnt > 0 && cnt >= filter_min_q(c, cl.grid.nonuniform);
-                if (filt || boxes) CHK(grid_companions(c, cl, cl.grid, cl.n, filt, boxes));
-                if (filt && coarse) CHK(grid_companions(c, cl, cl.sub_grid, cl.sub_n, true, false));
-                if (filt && (!cl.grid.filter_ok || (coarse && !cl.sub_grid.filter_ok))) filt = false;
-                const unsigned long long *cbox = boxes ? cl.grid.cell_box.p : nullptr;
-                if (filt) {
-                    // queries and their last matches in slot order (once per setup: a new setup, a new cloud or another slice start afresh)
-                    if (!c->have_prev_match || c->slot_lo != lo || c->slot_cnt != cnt || c->slot_ordered != ordered) {
-                        CHK(c->q_slot.reserve((size_t)4 * cnt)); CHK(c->p_slot.reserve((size_t)4 * cnt));
-                        CHK(c->nn_state.reserve((size_t)cnt));
-                        if (c->nn_redo.cap < (size_t)cnt + 2) {
-                            CHK(c->nn_redo.reserve((size_t)cnt + 2));
-                            HIPCHK(hipMemsetAsync(c->nn_redo.p, 0, 2 * sizeof(uint32_t), c->stream));
-                        }
-                        launch_slot_queries(c->stream, c->q.p + lo, c->q.p + c->qpad + lo, c->q.p + 2 * c->qpad + lo,
-                                            ordered ? c->q_order.p : nullptr, nullptr, cnt, c->q_slot.p, c->p_slot.p);
-                        HIPCHK(hipGetLastError());
-                        c->slot_lo = lo; c->slot_cnt = cnt; c->slot_ordered = ordered;
-                    }
-                    c->last_match_kernel = 6;
-                    const int lanes = eight ? 8 : 16;
-                    unsigned *tie_cnt = c->nn_redo.p + c->nn_parity, *tie_clear = c->nn_redo.p + (c->nn_parity ^ 1);
-                    uint32_t *tie_list = c->nn_redo.p + 2;
-                    unsigned long long *wk = c->count_work ? c->match_work.p : nullptr;
-                    const double inf = std::numeric_limits<double>::infinity();
-                    Timed t(c, SICP_K_KNN1);
-                    // cold: the subsample's nearest point (any point near the query: NN_APPROX) is left in the slot as the bound ...
-                    if (coarse)
-                        launch_grid_nn16f(c->stream, lanes, true, c->icp_dev.p, c->q_slot.p, c->p_slot.p, cnt, cl.sub_grid.g, cl.sub_grid.c0,
-                                          cl.sub_grid.eps_p, cl.sub_grid.cell_start.p, cl.sub_grid.recf.p, cl.sub_grid.rec.p, ordered,
-                                          nullptr, nullptr, cl.rmax, inf, 0, nullptr, nullptr, nullptr, nullptr, NN_APPROX, nullptr,
-                                          tie_list, tie_cnt);
-                    // ... and the search proper goes straight to that radius (NN_TIGHT).  A cold search is a far search for every
-                    // query: the full flavour takes all slots.  Later the lean flavour goes first and marks what it cannot do.
-                    // (the estimate still moves by a cell or so per iteration: most searches are wide -- the lean flavour would only find
-                    // that out and hand them on; judged from the last iterations the host has seen: the chain runs ahead of it)
-                    // (a nonuniform cloud -- cells of hundreds of points next to empty ones -- hands most of its queries on as well: measured on the
-                    // terrestrial stand-in at 1 M queries, 3.00 ms with the lean flavour first, 2.54 ms without)
-                    const bool all_far = coarse || c->nn16_filter == 1 || cl.grid.nonuniform || !(last_move <= c->far_move * cl.grid.g.h);
-                    if (!all_far)
-                        launch_grid_nn16f(c->stream, lanes, false, c->icp_dev.p, c->q_slot.p, c->p_slot.p, cnt, cl.grid.g, cl.grid.c0,
-                                          cl.grid.eps_p, cl.grid.cell_start.p, cl.grid.recf.p, cl.grid.rec.p, ordered, nullptr, nullptr,
-                                          cl.rmax, inf, cl.idx_base, c->m_d2.p + lo, c->m_idx.p + lo, c->m_p2.p + 3 * lo, wk, 0,
-                                          c->nn_state.p, tie_list, tie_cnt);
-                    launch_grid_nn16f(c->stream, lanes, true, c->icp_dev.p, c->q_slot.p, c->p_slot.p, cnt, cl.grid.g, cl.grid.c0,
-                                      cl.grid.eps_p, cl.grid.cell_start.p, cl.grid.recf.p, cl.grid.rec.p, ordered, nullptr, nullptr,
-                                      cl.rmax, inf, cl.idx_base, c->m_d2.p + lo, c->m_idx.p + lo, c->m_p2.p + 3 * lo, wk,
-                                      (coarse ? NN_TIGHT : 0), all_far ? nullptr : c->nn_state.p, tie_list, tie_cnt);
-                    // ties within the filter's margin (and queries float32 cannot place): the exact kernel, from the by-query
-                    // arrays (the previous match bounds them; in a cold iteration nothing does: they search outwards)
-                    // (the filtered kernels left every such query's approximate winner -- or "none" -- in the by-query match array)
-                    launch_grid_nn_redo(c->stream, c->q.p + lo, c->q.p + c->qpad + lo, c->q.p + 2 * c->qpad + lo, cnt,
-                                        c->m_p2.p + 3 * lo, cl.grid.g, cl.grid.cell_start.p, cl.grid.rec.p,
-                                        c->icp_dev.p, nullptr, nullptr, cl.rmax, inf, cl.idx_base, c->m_d2.p + lo, c->m_idx.p + lo,
-                                        c->m_p2.p + 3 * lo, wk, NN_TIGHT, nullptr, cbox, tie_list, tie_cnt, tie_clear, coarse_grid);
-                    c->nn_parity ^= 1;
-                } else {
-                Timed t(c, SICP_K_KNN1);
-                if (coarse)
-                    launch_grid_nn_chained(c->stream, c->q.p + lo, c->q.p + c->qpad + lo, c->q.p + 2 * c->qpad + lo, cnt, nullptr,
-                                           cl.sub_grid.g, cl.sub_grid.cell_start.p, cl.sub_grid.rec.p, c->icp_dev.p, cl.rmax, 0,
-                                           c->bound_d2.p + lo, c->bound_idx.p + lo, c->bound_p2.p + 3 * lo, nullptr,
-                                           ordered ? c->q_order.p : nullptr, many_q, NN_APPROX);
-                // without an exchange the match is final when its kernel ends: the winning lanes leave the point-to-plane
-                // distance and the planarity verdict too (what k_postmatch would re-read 72 bytes per correspondence for)
-                // (only in the one-wave-per-query flavour: with four queries per wave at the register limit the epilogue's late
-                // loads cost the search more than k_postmatch's launch -- match 693 -> 758 us at 1 M queries, measured)
-                // ... except below ~65 536 queries, where the machine is not full: there the epilogue costs the search ~0.07 us per
-                // 1 000 queries and k_postmatch's launch 5 us (profiles/r6: 10 000 correspondences, 63.6 -> 58.9 us per iteration)
-                post_done = !c->collective() && (!many_q || cnt < 65536);
-                // behind a cloud-shard exchange the winning lanes leave the exchange's packed record instead (no k_pack_best launch)
-                // (query shards: the slim record, the matched index alone -- no k_pack_idx launch)
-                const bool pack = c->collective() && !qshard && !exchange_by_keys(c, Q), pack_idx = c->collective() && qshard;
-                if (pack) CHK(c->x_send.reserve((size_t)5 * Q));
-                if (pack_idx) CHK(c->x_send.reserve((size_t)((Q + c->world - 1) / c->world)));
-                PostMatch pm = {c->normals.p, c->planarity.p, A.pl2, A.pl2_n, A.min_planarity, post_done ? c->dist.p : nullptr,
-                                post_done ? c->flag.p : nullptr, pack ? c->x_send.p : nullptr, pack_idx ? c->x_send.p : nullptr};
-                packed = (pack || pack_idx) && cnt > 0;
-                if (cnt > 0)
-                    launch_grid_nn_chained(c->stream, c->q.p + lo, c->q.p + c->qpad + lo, c->q.p + 2 * c->qpad + lo, cnt,
-                                           coarse ? c->bound_p2.p + 3 * lo : (prev ? prev + 3 * lo : nullptr), cl.grid.g,
-                                           cl.grid.cell_start.p, cl.grid.rec.p, c->icp_dev.p, cl.rmax, cl.idx_base, c->m_d2.p + lo,
-                                           c->m_idx.p + lo, c->m_p2.p + 3 * lo, c->count_work ? c->match_work.p : nullptr,
-                                           ordered ? c->q_order.p : nullptr, many_q, (coarse ? NN_TIGHT : 0),
-                                           (post_done || pack || pack_idx) ? &pm : nullptr, eight, cbox, coarse_grid);
-                }
-            } else if (qshard) {
-                return fail(SICP_ERR_INVALID, "query shards need the grid search (SICP_KNN1 forces another kernel)");
-            } else {
-                // brute-force flavours take H by value: one iteration in flight, H from the last record
-                params_to_H12(xcur, H12);
-                Xf X; for (int i = 0; i < 12; ++i) X.m[i] = H12[i];
-                CHK(knn1_device(c, SICP_MOV, c->q.p, Q, c->qpad, &X, std::numeric_limits<double>::infinity(), prev, c->m_d2.p,
-                                c->m_idx.p, c->m_p2.p));
-            }
-            HIPCHK(hipGetLastError());
-            c->have_prev_match = true;          // (after an exchange: the job-wide winner's coordinates -- still a valid bound)
-            if (qshard) { CHK(exchange_query_slices_idx(c, A, Q, packed)); post_done = true; c->last_xchg_form = 3; ++c->xchg_count; }      // (distances + verdicts formed by the unpack)
-            else if (c->collective() && c->partition == SICP_PART_CLOUD) {
-                CHK(c->x_send.reserve((size_t)5 * Q));
-                const bool by_keys = exchange_by_keys(c, Q);
-                if (by_keys) CHK(exchange_best_keys_chained(c, A, Q));                          // (many queries: all-reduces on 8-byte keys)
-                else CHK(exchange_best_chained(c, A, Q, packed));                              // (... by the lexicographic minimum's kernel)
-                // the filtered search keeps its bounds by slot and wrote THIS rank's winner there: make it the job-wide one
-                if (c->last_match_kernel == 6 && c->slot_cnt == Q)
-                    launch_slot_bounds(c->stream, c->q_slot.p, c->m_idx.p, c->m_p2.p, Q, c->p_slot.p);
-                post_done = true;
-                c->last_xchg_form = by_keys ? 2 : 1; ++c->xchg_count;
-            }
-            A.seq = (double)(++c->solve_seq);
-            seqs[launched % REC_RING] = A.seq;
-            double *rec = c->h_rec + (launched % REC_RING) * REC_DOUBLES;
-            const double *qx = c->q.p, *qy = c->q.p + c->qpad, *qz = c->q.p + 2 * c->qpad;
-            Xf unused = {};
-            if (small_q) {
-                if (!post_done)
-                    launch_postmatch(c->stream, qx, qy, qz, c->normals.p, c->planarity.p, c->m_p2.p, c->m_idx.p, Q, unused,
-                                     A.min_planarity, A.pl2, A.pl2_n, c->dist.p, c->flag.p, c->icp_dev.p);
-                Timed t(c, SICP_K_NORMALEQ);
-                launch_icp_tail(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, A, c->icp_dev.p, c->dist.p, c->flag.p, c->keep.p,
-                                c->resid.p, rec);
-            } else {
-                // distances + rejections (corrpts.py:139-211), kept-distance statistics, then the solver chain
-                if (Q <= REJECT_MAX_Q) {
-                    Timed t(c, SICP_K_SELECT);
-                    // distances + flags by the whole machine (the match kernel's epilogue, or k_postmatch behind an exchange), then
-                    // selection + keep mask + statistics by one workgroup on the 9 bytes per correspondence it still has to read
-                    if (!post_done)
-                        launch_postmatch(c->stream, qx, qy, qz, c->normals.p, c->planarity.p, c->m_p2.p, c->m_idx.p, Q, unused,
-                                         A.min_planarity, A.pl2, A.pl2_n, c->dist.p, c->flag.p, c->icp_dev.p);
-                    launch_reject(c->stream, c->dist.p, c->flag.p, Q, c->keep.p, c->small.p, c->icp_dev.p, c->small.p + 4,
-                                  c->tail_window && c->reject_prior);
-                    c->reject_prior = true;               // (c->small[0..3] now holds this iteration's statistics: the next launch's window)
-                } else {
-                    if (!post_done)
-                        launch_postmatch(c->stream, qx, qy, qz, c->normals.p, c->planarity.p, c->m_p2.p, c->m_idx.p, Q, unused,
-                                         A.min_planarity, A.pl2, A.pl2_n, c->dist.p, c->flag.p, c->icp_dev.p);
-                    {
-                        // median / MAD by digit selection over many workgroups, keep mask + kept statistics in one more pass
-                        Timed t(c, SICP_K_SELECT);
-                        CHK(reject_select(c, Q, nullptr, 0.0, c->icp_dev.p));
-                    }
-                }
-                {
-                    // gn_shard: every rank evaluates its slice of the correspondences, ONE all-reduce adds the
-                    // 8x8 Gram blocks (J^T J, J^T r, sum r, sum r^2, n) up, a one-wave launch advances the replicated solver
-                    const bool shard = c->gn_shard && c->collective();
-                    if (shard) CHK(c->lm_gsum.reserve(64));
-                    c->resid_sharded = shard;
-                    Timed t(c, SICP_K_NORMALEQ);
-                    if (c->lm_one_launch && !shard) {
-                        const size_t words = (lm_bar_bytes() + 7) / 8;
-                        if (c->lm_bar_buf.cap < words) {
-                            CHK(c->lm_bar_buf.reserve(words));
-                            HIPCHK(hipMemsetAsync(c->lm_bar_buf.p, 0, words * 8, c->stream));
-                            c->lm_bar = 0;
-                        }
-                        launch_lm_all(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, c->keep.p, Q, A, c->icp_dev.p, c->lm_dev.p, c->small.p,
-                                      c->small.p + 4, c->ne_partial.p, c->lm_bar_buf.p, &c->lm_bar, c->resid.p, c->resid2.p, rec,
-                                      c->test_barrier_fault == 2 ? 1u : 0u);
-                    } else {
-                        for (int e = 0; e < c->lm_evals; ++e) {
-                            launch_lm_eval(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, c->keep.p, Q, A, c->icp_dev.p, c->lm_dev.p,
-                                           c->small.p + 4, c->ne_partial.p, c->ticket.p, c->resid.p, c->resid2.p,
-                                           shard ? c->rank : 0, shard ? c->world : 1, shard ? c->lm_gsum.p : nullptr);
-                            if (shard) {
-                                CHK(all_reduce_sum_f64(c, c->lm_gsum.p, 64));
-                                launch_lm_advance(c->stream, A, c->icp_dev.p, c->lm_dev.p, c->small.p + 4, c->lm_gsum.p);
-                            }
-                        }
-                        launch_lm_finish(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, c->keep.p, Q, A, c->icp_dev.p, c->lm_dev.p,
-                                         c->small.p, c->small.p + 4, c->resid.p, c->resid2.p, rec);
-                    }
-                }
-            }
-            HIPCHK(hipGetLastError());
-            ++launched;
-            if (htrace) {
-                const auto h1 = std::chrono::steady_clock::now();
-                std::fprintf(stderr, "[host] iteration %lld enqueued in %.1f us\n", (long long)launched,
-                             std::chrono::duration<double, std::micro>(h1 - h0).count());
-            }
-        }
-        if (completed == launched) break;
-        const double *o = c->h_rec + (completed % REC_RING) * REC_DOUBLES;
-        CHK(wait_ticket(c, o + REC_TICKET, seqs[completed % REC_RING]));
-        const int status = (int)o[REC_STATUS];
-        if (status == 3) { ++completed; over = true; continue; }        // launched after the end of the run: not an iteration
-        if (status == 4) {
-            // a one-launch kernel could not meet itself at its grid barrier (its blocks were not all resident: CUs held by another
-            // process, a paused queue).  The launches behind it see the stop flag; start the barrier state afresh so that the next
-            // run is not poisoned by this one (the error word is sticky on the device by design: every later phase must see it)
-            ++completed; over = true;
-            (void)hipStreamSynchronize(c->stream);
-            CHK(reset_barrier_state(c));
-            c->have_iter = false;
-            rc = fail(SICP_ERR_HIP, "a device-wide barrier of iteration %lld timed out (blocks not co-resident: is another process "
-                                    "using the GPU?); the run was stopped and the barrier state reset", (long long)completed);
-            continue;
-        }
-        ++completed;
-        const int rr = take_record(c, P0, o, results, done_out, xcur, &last_move, &over);
-        if (rr != SICP_OK) rc = rr;
+    int depth;                    // iterations enqueued ahead of the record being read
+    int rc = SICP_OK;             // the run's verdict: the last failing record's
+};
+
+// one iteration's match, decided (plan_match gives the reasons)
+struct MatchPlan {
+    bool grid = false, qshard = false;
+    long lo = 0, cnt = 0;         // query shards: this rank's slice of the queries
+    bool ordered = false, coarse = false, eight = false, many_q = false, boxes = false;
+    bool filt = false;            // through the float32 filter (enqueue_match withdraws it where float32 cannot hold the cloud)
+    bool all_far = false;         // ... its full flavour for every slot
+    // the exact kernels' epilogue (the filtered search has none): distances + planarity verdicts, the exchange's packed records
+    bool post_done = false, pack = false, pack_idx = false;
+    int kernel = 0;               // sicp_last_match_kernel, unless the filter takes the search (6)
+};
+
+MatchPlan plan_match(const sicp_ctx *c, bool grid, int64_t iteration, bool cold_start, double last_move)
+{
+    const Cloud &cl = c->cloud[SICP_MOV];
+    const long Q = c->Q;
+    MatchPlan p;
+    p.grid = grid;
+    p.qshard = c->collective() && c->partition == SICP_PART_QUERIES;
+    if (!grid) return p;
+    // (query shards: this rank searches its slice of the queries in the whole cloud, results land in their place in the full arrays)
+    p.cnt = p.qshard ? query_slice(c, Q, &p.lo) : Q;
+    const long cnt = p.cnt;
+    // (a nonuniform cloud: one wave per query -- 64 rows per batch, the coarse grid for wide passes -- until the filtered search takes over)
+    p.many_q = cnt >= c->nn16_min_q && (!cl.grid.nonuniform || cnt >= filter_min_q(c, true));
+    p.kernel = p.many_q ? 5 : 2;
+    p.ordered = c->order_min_q > 0 && cnt >= c->order_min_q;
+    // A search without a useful bound (the run's first iterations: no previous match, or one made under an estimate
+    // that was metres off) first asks the cloud's SUBSAMPLE for its nearest point: a cloud point, so a bound, and
+    // close enough to the answer that the real search goes straight to that radius instead of doubling its way out.
+    p.coarse = cold_start && iteration < c->coarse_iters && cl.n >= c->coarse_min_n && cnt > 0;
+    // EIGHT queries per wave (8 lanes each) once the query set is large and cells are small: twice the independent
+    // requests per wave in flight (0.69 -> 0.62 ms per 1 M queries on 10 M points); not with long rows (C5 sizes: the cell
+    // table's limit leaves 25 points per cell, 8 lanes need twice the steps: 2.07 -> 2.53 ms per step) nor below ~200 k
+    // queries (too few waves to fill the machine)
+    p.eight = c->nn_group ? c->nn_group == 8 : (cnt >= 196608 && !cl.grid.cap_limited && cl.grid.avg_per_cell <= 20.0);
+    // far searches (a run's first iterations) trim their rows by the tight boxes of the cells; large query sets are
+    // searched through the float32 filter (sicp_gridf.hip) when float32 can hold the cloud
+    p.boxes = c->use_boxes && cnt > 0;
+    p.filt = wants_filter(c, cl.grid, cnt);
+    // (the estimate still moves by a cell or so per iteration: most searches are wide -- the lean flavour would only find
+    // that out and hand them on; judged from the last iterations the host has seen: the chain runs ahead of it)
+    // (a nonuniform cloud -- cells of hundreds of points next to empty ones -- hands most of its queries on as well: measured on the
+    // terrestrial stand-in at 1 M queries, 3.00 ms with the lean flavour first, 2.54 ms without)
+    p.all_far = p.coarse || c->nn16_filter == 1 || cl.grid.nonuniform || !(last_move <= c->far_move * cl.grid.g.h);
+    // without an exchange the match is final when its kernel ends: the winning lanes leave the point-to-plane
+    // distance and the planarity verdict too (what k_postmatch would re-read 72 bytes per correspondence for)
+    // (only in the one-wave-per-query flavour: with four queries per wave at the register limit the epilogue's late
+    // loads cost the search more than k_postmatch's launch -- match 693 -> 758 us at 1 M queries, measured)
+    // ... except below ~65 536 queries, where the machine is not full: there the epilogue costs the search ~0.07 us per
+    // 1 000 queries and k_postmatch's launch 5 us (profiles/r6: 10 000 correspondences, 63.6 -> 58.9 us per iteration)
+    p.post_done = !c->collective() && (!p.many_q || cnt < 65536);
+    // behind a cloud-shard exchange the winning lanes leave the exchange's packed record instead (no k_pack_best launch)
+    // (query shards: the slim record, the matched index alone -- no k_pack_idx launch)
+    p.pack = c->collective() && !p.qshard && !exchange_by_keys(c, Q);
+    p.pack_idx = c->collective() && p.qshard;
+    return p;
+}
+
+// the match of one chained iteration as planned: companions of the grid, then the launches
+int enqueue_match(sicp_ctx *c, const TailArgs &A, const double xcur[6], MatchPlan &p)
+{
+    const long Q = c->Q, lo = p.lo, cnt = p.cnt;
+    Cloud &cl = c->cloud[SICP_MOV];
+    const double *prev = c->have_prev_match ? c->m_p2.p : nullptr;
+    if (!p.grid) {
+        if (p.qshard) return fail(SICP_ERR_INVALID, "query shards need the grid search (SICP_KNN1 forces another kernel)");
+        // brute-force flavours take H by value: one iteration in flight, H from the last record
+        double H12[12];
+        params_to_H12(xcur, H12);
+        Xf X; for (int i = 0; i < 12; ++i) X.m[i] = H12[i];
+        return knn1_device(c, SICP_MOV, c->q.p, Q, c->qpad, &X, std::numeric_limits<double>::infinity(), prev, c->m_d2.p, c->m_idx.p,
+                           c->m_p2.p);
     }
-    return rc;
+    if (p.ordered) CHK(query_order_build(c, lo, cnt, cl.grid.g.h));
+    if (p.coarse) {
+        CHK(subsample_build(c, SICP_MOV));
+        CHK(c->bound_p2.reserve((size_t)3 * Q)); CHK(c->bound_d2.reserve(Q)); CHK(c->bound_idx.reserve(Q));
+    }
+    GridLevel coarse_lv; const GridLevel *coarse_grid = nullptr;
+    CHK(grid_coarse_level(c, SICP_MOV, &coarse_lv, &coarse_grid));
+    if (p.filt || p.boxes) CHK(grid_companions(c, cl, cl.grid, cl.n, p.filt, p.boxes));
+    if (p.filt && p.coarse) CHK(grid_companions(c, cl, cl.sub_grid, cl.sub_n, true, false));
+    if (p.filt && (!cl.grid.filter_ok || (p.coarse && !cl.sub_grid.filter_ok))) p.filt = false;
+    GridSearch S;
+    S.qx = c->q.p + lo; S.qy = c->q.p + c->qpad + lo; S.qz = c->q.p + 2 * c->qpad + lo; S.Q = cnt;
+    S.order = p.ordered ? c->q_order.p : nullptr;
+    set_level(S, cl.grid);
+    S.coarse = coarse_grid;
+    S.cell_box = p.boxes ? cl.grid.cell_box.p : nullptr;
+    S.st = c->icp_dev.p;
+    S.rmax = cl.rmax; S.idx_base = cl.idx_base;
+    S.d2 = c->m_d2.p + lo; S.idx = c->m_idx.p + lo; S.p2 = c->m_p2.p + 3 * lo;
+    S.work = c->count_work ? c->match_work.p : nullptr;
+    if (p.filt) {
+        // queries and their last matches in slot order (once per setup: a new setup, a new cloud or another slice start afresh)
+        const bool fill = !c->have_prev_match || c->slot_lo != lo || c->slot_cnt != cnt || c->slot_ordered != p.ordered;
+        FilteredSearch F = {S, &c->q_slot, &c->p_slot, fill, nullptr, p.coarse ? &cl.sub_grid : nullptr, p.eight ? 8 : 16, p.all_far, NN_TIGHT};
+        F.S.prev_p2 = S.p2;
+        CHK(filtered_search(c, F));
+        if (fill) { c->slot_lo = lo; c->slot_cnt = cnt; c->slot_ordered = p.ordered; }
+        return SICP_OK;
+    }
+    Timed t(c, SICP_K_KNN1);
+    if (p.coarse)                           // the subsample's nearest point -> bound_p2
+        launch_grid_nn(c->stream, bound_search(S, cl.sub_grid, c->bound_d2.p + lo, c->bound_idx.p + lo, c->bound_p2.p + 3 * lo),
+                       p.many_q ? NN_LANES16 : NN_WAVE);
+    if (p.pack) CHK(c->x_send.reserve((size_t)5 * Q));
+    if (p.pack_idx) CHK(c->x_send.reserve((size_t)((Q + c->world - 1) / c->world)));
+    const PostMatch pm = {c->normals.p, c->planarity.p, A.pl2, A.pl2_n, A.min_planarity, p.post_done ? c->dist.p : nullptr,
+                          p.post_done ? c->flag.p : nullptr, p.pack ? c->x_send.p : nullptr, p.pack_idx ? c->x_send.p : nullptr};
+    S.prev_p2 = p.coarse ? c->bound_p2.p + 3 * lo : (prev ? prev + 3 * lo : nullptr);
+    S.flags = p.coarse ? NN_TIGHT : 0;
+    S.post = (p.post_done || p.pack || p.pack_idx) ? &pm : nullptr;
+    if (cnt > 0) launch_grid_nn(c->stream, S, !p.many_q ? NN_WAVE : p.eight ? NN_LANES8 : NN_LANES16);
+    return SICP_OK;
+}
+
+// after the match, multi-GPU runs: the job-wide winners.  *post_done: the unpack formed distances + verdicts as well
+int enqueue_exchange(sicp_ctx *c, const TailArgs &A, const MatchPlan &p, bool packed, bool *post_done)
+{
+    const long Q = c->Q;
+    if (p.qshard) {
+        CHK(exchange_query_slices_idx(c, A, Q, packed));
+        *post_done = true; c->last_xchg_form = 3; ++c->xchg_count;
+    } else if (c->collective() && c->partition == SICP_PART_CLOUD) {
+        CHK(c->x_send.reserve((size_t)5 * Q));
+        const bool by_keys = exchange_by_keys(c, Q);
+        if (by_keys) CHK(exchange_best_keys_chained(c, A, Q));                          // (many queries: all-reduces on 8-byte keys)
+        else CHK(exchange_best_chained(c, A, Q, packed));                              // (... by the lexicographic minimum's kernel)
+        // the filtered search keeps its bounds by slot and wrote THIS rank's winner there: make it the job-wide one
+        if (c->last_match_kernel == 6 && c->slot_cnt == Q)
+            launch_slot_bounds(c->stream, c->q_slot.p, c->m_idx.p, c->m_p2.p, Q, c->p_slot.p);
+        *post_done = true;
+        c->last_xchg_form = by_keys ? 2 : 1; ++c->xchg_count;
+    }
+    return SICP_OK;
+}
+
+// distances + planarity verdicts by the whole machine, where neither the match kernel's epilogue nor an exchange's unpack left them
+void enqueue_postmatch(sicp_ctx *c, const TailArgs &A, bool post_done)
+{
+    if (post_done) return;
+    const Xf unused = {};
+    launch_postmatch(c->stream, c->q.p, c->q.p + c->qpad, c->q.p + 2 * c->qpad, c->normals.p, c->planarity.p, c->m_p2.p, c->m_idx.p, c->Q,
+                     unused, A.min_planarity, A.pl2, A.pl2_n, c->dist.p, c->flag.p, c->icp_dev.p);
+}
+
+// larger Q: the solver chain (sicp_lm.hip), its last launch streaming the record
+int enqueue_minimisation(sicp_ctx *c, const TailArgs &A, double *rec)
+{
+    const long Q = c->Q;
+    const double *qx = c->q.p, *qy = c->q.p + c->qpad, *qz = c->q.p + 2 * c->qpad;
+    // gn_shard: every rank evaluates its slice of the correspondences, ONE all-reduce adds the
+    // 8x8 Gram blocks (J^T J, J^T r, sum r, sum r^2, n) up, a one-wave launch advances the replicated solver
+    const bool shard = c->gn_shard && c->collective();
+    if (shard) CHK(c->lm_gsum.reserve(64));
+    c->resid_sharded = shard;
+    Timed t(c, SICP_K_NORMALEQ);
+    if (c->lm_one_launch && !shard) {
+        const size_t words = (lm_bar_bytes() + 7) / 8;
+        if (c->lm_bar_buf.cap < words) {
+            CHK(c->lm_bar_buf.reserve(words));
+            HIPCHK(hipMemsetAsync(c->lm_bar_buf.p, 0, words * 8, c->stream));
+            c->lm_bar = 0;
+        }
+        launch_lm_all(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, c->keep.p, Q, A, c->icp_dev.p, c->lm_dev.p, c->small.p,
+                      c->small.p + 4, c->ne_partial.p, c->lm_bar_buf.p, &c->lm_bar, c->resid.p, c->resid2.p, rec,
+                      c->test_barrier_fault == 2 ? 1u : 0u);
+        return SICP_OK;
+    }
+    for (int e = 0; e < c->lm_evals; ++e) {
+        launch_lm_eval(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, c->keep.p, Q, A, c->icp_dev.p, c->lm_dev.p,
+                       c->small.p + 4, c->ne_partial.p, c->ticket.p, c->resid.p, c->resid2.p,
+                       shard ? c->rank : 0, shard ? c->world : 1, shard ? c->lm_gsum.p : nullptr);
+        if (shard) {
+            CHK(all_reduce_sum_f64(c, c->lm_gsum.p, 64));
+            launch_lm_advance(c->stream, A, c->icp_dev.p, c->lm_dev.p, c->small.p + 4, c->lm_gsum.p);
+        }
+    }
+    launch_lm_finish(c->stream, qx, qy, qz, c->normals.p, c->m_p2.p, c->keep.p, Q, A, c->icp_dev.p, c->lm_dev.p,
+                     c->small.p, c->small.p + 4, c->resid.p, c->resid2.p, rec);
+    return SICP_OK;
+}
+
+// everything behind the match (and its exchange): distances, rejection (corrpts.py:139-211) + kept-distance statistics,
+// minimisation, the record `rec`
+int enqueue_tail(sicp_ctx *c, const TailArgs &A, bool post_done, double *rec)
+{
+    const long Q = c->Q;
+    if (Q <= SOLVE_MAX_Q) {
+        enqueue_postmatch(c, A, post_done);
+        Timed t(c, SICP_K_NORMALEQ);
+        launch_icp_tail(c->stream, c->q.p, c->q.p + c->qpad, c->q.p + 2 * c->qpad, c->normals.p, c->m_p2.p, A, c->icp_dev.p, c->dist.p,
+                        c->flag.p, c->keep.p, c->resid.p, rec);
+        return SICP_OK;
+    }
+    // (the one-workgroup rejection's timing column takes k_postmatch in, the other's does not: as it has been)
+    if (Q <= REJECT_MAX_Q) {
+        Timed t(c, SICP_K_SELECT);
+        // distances + flags by the whole machine (the match kernel's epilogue, or k_postmatch behind an exchange), then
+        // selection + keep mask + statistics by one workgroup on the 9 bytes per correspondence it still has to read
+        enqueue_postmatch(c, A, post_done);
+        launch_reject(c->stream, c->dist.p, c->flag.p, Q, c->keep.p, c->small.p, c->icp_dev.p, c->small.p + 4, c->tail_window && c->reject_prior);
+        c->reject_prior = true;               // (c->small[0..3] now holds this iteration's statistics: the next launch's window)
+    } else {
+        enqueue_postmatch(c, A, post_done);
+        // median / MAD by digit selection over many workgroups, keep mask + kept statistics in one more pass
+        Timed t(c, SICP_K_SELECT);
+        CHK(reject_select(c, Q, nullptr, 0.0, c->icp_dev.p));
+    }
+    return enqueue_minimisation(c, A, rec);
+}
+
+int enqueue_iteration(sicp_ctx *c, ChainRun &L)
+{
+    const auto h0 = std::chrono::steady_clock::now();
+    MatchPlan p = plan_match(c, L.grid, L.launched, L.cold_start, L.last_move);
+    if (p.grid) c->last_match_kernel = p.kernel;
+    CHK(enqueue_match(c, L.A, L.xcur, p));
+    HIPCHK(hipGetLastError());
+    c->have_prev_match = true;          // (after an exchange: the job-wide winner's coordinates -- still a valid bound)
+    bool post_done = !p.filt && p.post_done;
+    const bool packed = !p.filt && (p.pack || p.pack_idx) && p.cnt > 0;
+    CHK(enqueue_exchange(c, L.A, p, packed, &post_done));
+    L.A.seq = (double)(++c->solve_seq);
+    L.seqs[L.launched % REC_RING] = L.A.seq;
+    CHK(enqueue_tail(c, L.A, post_done, c->h_rec + (L.launched % REC_RING) * REC_DOUBLES));
+    HIPCHK(hipGetLastError());
+    ++L.launched;
+    if (c->host_trace)
+        std::fprintf(stderr, "[host] iteration %lld enqueued in %.1f us\n", (long long)L.launched,
+                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count());
+    return SICP_OK;
+}
+
+// the oldest launch's record: waited for, then taken (results, ctx state, L.xcur / last_move / over)
+int pump_record(sicp_ctx *c, const sicp_iter_params *P0, ChainRun &L, sicp_iter_result *results, int64_t *done_out)
+{
+    const double *o = c->h_rec + (L.completed % REC_RING) * REC_DOUBLES;
+    CHK(wait_ticket(c, o + REC_TICKET, L.seqs[L.completed % REC_RING]));
+    const int status = (int)o[REC_STATUS];
+    ++L.completed;
+    if (status == 3) { L.over = true; return SICP_OK; }        // launched after the end of the run: not an iteration
+    if (status == 4) {
+        // a one-launch kernel could not meet itself at its grid barrier (its blocks were not all resident: CUs held by another
+        // process, a paused queue).  The launches behind it see the stop flag; start the barrier state afresh so that the next
+        // run is not poisoned by this one (the error word is sticky on the device by design: every later phase must see it)
+        L.over = true;
+        (void)hipStreamSynchronize(c->stream);
+        CHK(reset_barrier_state(c));
+        c->have_iter = false;
+        L.rc = fail(SICP_ERR_HIP, "a device-wide barrier of iteration %lld timed out (blocks not co-resident: is another process "
+                                  "using the GPU?); the run was stopped and the barrier state reset", (long long)L.completed);
+        return SICP_OK;
+    }
+    const int rr = take_record(c, P0, o, results, done_out, L.xcur, &L.last_move, &L.over);
+    if (rr != SICP_OK) L.rc = rr;
+    return SICP_OK;
+}
+
+}  // namespace
+
+// min_change < 0: no convergence test.
+int run_device_tail(sicp_ctx *c, const sicp_iter_params *P0, int64_t max_it, double min_change, sicp_iter_result *results,
+                    int64_t *done_out)
+{
+    *done_out = 0;
+    if (max_it <= 0) return SICP_OK;
+    ChainRun L;
+    CHK(chain_prepare(c, P0, &L.grid, &L.last_move));
+    const bool small_q = c->Q <= SOLVE_MAX_Q;
+    L.depth = !L.grid ? 1 : small_q ? c->chain_depth : std::min(c->chain_depth, 2);
+    L.A = tail_args(c, P0, min_change);
+    std::memcpy(L.xcur, P0->x, sizeof L.xcur);
+    L.cold_start = !c->have_prev_match;
+    while (true) {
+        while (L.launched < max_it && L.launched - L.completed < L.depth && !L.over) CHK(enqueue_iteration(c, L));
+        if (L.completed == L.launched) break;
+        CHK(pump_record(c, P0, L, results, done_out));
+    }
+    return L.rc;
 }
 
 // ---- optimisation: optimization.py:65-124 as LM on fused 6x6 reductions over the rows of `keep`, from P->x ----
@@ -757,9 +792,8 @@ SICP_EXPORT int sicp_icp_run(sicp_ctx *c, const sicp_iter_params *P0, int64_t ma
     CHK(check_iter_args(c, P0));
     HIPCHK(hipSetDevice(c->device));
     if (device_tail(c)) {
-        if (std::isnan(min_change)) min_change = 0.0;
         // (a failing iteration's entry carries the estimate it started from: the tail kernel records it)
-        return run_device_tail(c, P0, max_iterations, min_change < 0 ? 0.0 : min_change, results, iterations_out);
+        return run_device_tail(c, P0, max_iterations, run_min_change(min_change), results, iterations_out);
     }
     sicp_iter_params P = *P0;
     auto change = [](double now, double before) {          // simpleicp.py:361-365

@@ -147,20 +147,35 @@ int  icp_tail_ept(long Q);                        // the k_icp_tail instantiatio
 
 constexpr int NN_TIGHT = 1;      // prev_p2 is a bound to search in one go (the nearest point of a subsample), not an old match
 constexpr int NN_APPROX = 2;     // the first hit is good enough: the caller wants a cloud point NEAR the query (a bound), not the nearest
-void launch_grid_nn(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,
-                    const GridGeom &G, const uint32_t *cell_start, const void *rec, const Xf *H, const Xf *Hinv, double rmax,
-                    double max_d2, int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out, unsigned long long *work,
-                    bool four_per_wave, const unsigned long long *cell_box = nullptr, const GridLevel *coarse = nullptr);
-void launch_grid_nn_chained(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,
-                            const GridGeom &G, const uint32_t *cell_start, const void *rec, const IcpDev *st, double rmax,
-                            int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out, unsigned long long *work,
-                            const uint32_t *order, bool four_per_wave, int flags = 0, const PostMatch *post = nullptr,
-                            bool eight_per_wave = false, const unsigned long long *cell_box = nullptr, const GridLevel *coarse = nullptr);
-void launch_grid_nn_redo(hipStream_t s, const double *qx, const double *qy, const double *qz, long Q, const double *prev_p2,
-                         const GridGeom &G, const uint32_t *cell_start, const void *rec, const IcpDev *st, const Xf *H, const Xf *Hinv,
-                         double rmax, double max_d2, int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out,
-                         unsigned long long *work, int flags, const PostMatch *post, const unsigned long long *cell_box,
-                         const uint32_t *redo_list, const unsigned *redo_count, unsigned *redo_clear, const GridLevel *coarse = nullptr);
+// One 1-NN search on a cloud's grid, as its launch wrappers take it (host side only: the kernels still receive these values one by
+// one).  Every optional field starts out "absent": a call site names what it uses.
+struct GridSearch {
+    const double *qx = nullptr, *qy = nullptr, *qz = nullptr;   // the queries by columns (k_grid_nn, k_grid_nn16) ...
+    long Q = 0;
+    const uint32_t *order = nullptr;              // ... in cell order (blocks rounded up to a multiple of 8: one share per XCD)
+    const double *prev_p2 = nullptr;              // (Q,3) a cloud point per query: its distance bounds the search
+    const void *qrec = nullptr; void *pslot = nullptr;   // ... or by slot (k_grid_nn16f): launch_slot_queries' records, the bounds
+    uint8_t *state = nullptr;                     // by slot: what the lean flavour leaves to the full one
+    GridGeom G = {}; const uint32_t *cell_start = nullptr; const void *rec = nullptr;   // the grid level
+    const GridLevel *coarse = nullptr;            // its coarse twin
+    const unsigned long long *cell_box = nullptr; // the cells' tight boxes
+    const void *recf = nullptr; const double *c0 = nullptr; double eps_p = 0.0;         // its float32 companion and frame ([3])
+    const IcpDev *st = nullptr;                   // the transform: the chain's loop state, else H with its rigid inverse by value,
+    const Xf *H = nullptr, *Hinv = nullptr;       // else none
+    double rmax = 0.0, max_d2 = __builtin_inf();
+    int64_t idx_base = 0;
+    double *d2 = nullptr; int64_t *idx = nullptr; double *p2 = nullptr;   // outputs
+    unsigned long long *work = nullptr;           // instrumented runs: tallies
+    int flags = 0;                                // NN_TIGHT | NN_APPROX
+    const PostMatch *post = nullptr;              // the epilogue of a chained match
+    // the queries the filtered search leaves to the exact one: written by k_grid_nn16f, read (and the other counter cleared) by NN_REDO
+    uint32_t *redo_list = nullptr; unsigned *redo_count = nullptr, *redo_clear = nullptr;
+};
+// k_grid_nn: one wave per query; k_grid_nn16: 16 or (chained searches only) 8 lanes per query; NN_REDO: k_grid_nn over redo_list --
+// what the filtered kernel would not answer itself.  That launch cannot know how long the list is -- a few hundred waves share it;
+// an empty list costs a launch that exits at once
+enum NnFlavour { NN_WAVE, NN_LANES16, NN_LANES8, NN_REDO };
+void launch_grid_nn(hipStream_t s, const GridSearch &S, NnFlavour flavour);
 // sicp_gridf.hip: the grid's lazily built companions and the filtered many-queries search
 void launch_recf(hipStream_t s, const void *rec, long n, const double c0[3], void *recf);
 void launch_cell_boxes(hipStream_t s, const uint32_t *cell_start, const void *rec, long ncells, const GridGeom &G, unsigned long long *cell_box);
@@ -169,11 +184,8 @@ void launch_slot_queries(hipStream_t s, const double *qx, const double *qy, cons
 void launch_slot_bounds(hipStream_t s, const void *qrec, const int64_t *idx, const double *p2, long Q, void *pslot);
 // far: the flavour with row batches, hit-driven culling and box trimming (a run's first iterations); otherwise the lean flavour,
 // which marks the queries it cannot do in `state` (1) for a launch of the other flavour over the same slots
-void launch_grid_nn16f(hipStream_t s, int lanes_per_query, bool far, const IcpDev *st, const void *qrec, void *pslot, long Q,
-                       const GridGeom &G, const double c0[3], double eps_p, const uint32_t *cell_start,
-                       const void *recf, const void *rec, bool xcd_order, const Xf *H,
-                       const Xf *Hinv, double rmax, double max_d2, int64_t idx_base, double *d2_out, int64_t *idx_out, double *p2_out,
-                       unsigned long long *work, int flags, uint8_t *state, uint32_t *redo_list, unsigned *redo_count);
+// (S.order only says whether the slots are in cell order: the slot records carry the queries)
+void launch_grid_nn16f(hipStream_t s, const GridSearch &S, int lanes_per_query, bool far);
 void launch_stride_sample(hipStream_t s, const double *x, const double *y, const double *z, long n, long stride, long m, long mpad,
                           double *out);
 void launch_scatter_order(hipStream_t s, const uint32_t *ids, long n, uint32_t *cursor, uint32_t *order);

@@ -20,10 +20,6 @@ void plan_chunks(const sicp_ctx *c, long npad, long qblocks, size_t bytes_per_ch
 }
 
 
-}  // namespace sicph
-
-namespace sicph {
-
 // H (rows 0..2) rigid to working precision?  Then Hinv = [R^T | -R^T t].
 bool rigid_inverse(const Xf &H, Xf *inv)
 {
@@ -66,6 +62,46 @@ double smax3(const Xf &H)
     return std::sqrt(std::max(l, 0.0)) * (1.0 + 1e-9);
 }
 
+// The filtered many-queries search, start to end: the slot-ordered copies, the float32 flavours (sicp_gridf.hip) and the exact redo
+// of what they leave -- ties within the filter's margin, queries float32 cannot place.  The same answers as the exact kernels'.
+int filtered_search(sicp_ctx *c, const FilteredSearch &F)
+{
+    const long Q = F.S.Q;
+    // queries and their bounds in slot order
+    if (F.fill_slots) { CHK(F.q_slot->reserve((size_t)4 * Q)); CHK(F.p_slot->reserve((size_t)4 * Q)); }
+    CHK(c->nn_state.reserve((size_t)Q));
+    if (c->nn_redo.cap < (size_t)Q + 2) {
+        CHK(c->nn_redo.reserve((size_t)Q + 2));
+        HIPCHK(hipMemsetAsync(c->nn_redo.p, 0, 2 * sizeof(uint32_t), c->stream));
+    }
+    if (F.fill_slots) {
+        launch_slot_queries(c->stream, F.S.qx, F.S.qy, F.S.qz, F.S.order, F.slot_prev, Q, F.q_slot->p, F.p_slot->p);
+        HIPCHK(hipGetLastError());
+    }
+    GridSearch S = F.S;
+    S.qrec = F.q_slot->p; S.pslot = F.p_slot->p;
+    // the counter pair alternates by launch: this search counts in one, its redo clears the other for the next
+    S.redo_list = c->nn_redo.p + 2;
+    S.redo_count = c->nn_redo.p + c->nn_parity; S.redo_clear = c->nn_redo.p + (c->nn_parity ^ 1);
+    c->last_match_kernel = 6;
+    Timed t(c, SICP_K_KNN1);
+    // cold: the subsample's nearest point (any point near the query: NN_APPROX) is left in the slot as the bound ...
+    if (F.cold) launch_grid_nn16f(c->stream, bound_search(S, *F.cold, nullptr, nullptr, nullptr), F.lanes, true);
+    // ... and the search proper goes straight to that radius (NN_TIGHT).  A cold search is a far search for every
+    // query: the full flavour takes all slots.  Later the lean flavour goes first and marks what it cannot do.
+    S.flags = 0; S.state = c->nn_state.p;
+    if (!F.all_far) launch_grid_nn16f(c->stream, S, F.lanes, false);
+    S.flags = F.cold ? NN_TIGHT : 0; S.state = F.all_far ? nullptr : c->nn_state.p;
+    launch_grid_nn16f(c->stream, S, F.lanes, true);
+    // ties within the filter's margin (and queries float32 cannot place): the exact kernel, from the by-query
+    // arrays (the previous match bounds them; in a cold iteration nothing does: they search outwards)
+    // (the filtered kernels left every such query's approximate winner -- or "none" -- in the by-query match array)
+    S.flags = F.redo_flags;
+    launch_grid_nn(c->stream, S, NN_REDO);
+    c->nn_parity ^= 1;
+    return SICP_OK;
+}
+
 // 1-NN of SoA queries (qx|qy|qz with stride qpad) in a slot; results in device buffers.
 //   prev_p2 : optional (Q,3) coordinates of a cloud point per query (last iteration's match): its
 //             exact distance under H is the filter bound; otherwise a strided-subsample exact
@@ -93,36 +129,25 @@ int knn1_device(sicp_ctx *c, int slot, const double *qsoa, long Q, long qpad, co
         // (a nonuniform cloud: one wave per query -- 64 rows per batch and the coarse grid for wide passes -- until the filtered search takes over)
         const bool four = Q >= c->nn16_min_q && !gr.nonuniform;
         c->last_match_kernel = four ? 5 : 2;
+        GridSearch S;
+        S.qx = qsoa; S.qy = qsoa + qpad; S.qz = qsoa + 2 * qpad; S.Q = Q;
+        S.prev_p2 = prev_p2;
+        S.coarse = coarse;
+        S.H = H; S.Hinv = H ? &Hinv : nullptr;
+        S.rmax = cl.rmax; S.max_d2 = max_d2; S.idx_base = cl.idx_base;
+        S.d2 = d2_out; S.idx = idx_out; S.p2 = p2_out;
+        S.work = c->count_work ? c->match_work.p : nullptr;
         // large query sets: through the float32 filter (sicp_gridf.hip), what it leaves (ties within its margin) through the exact
         // kernel -- the same answers
-        if (Q >= c->nn16_min_q && Q >= filter_min_q(c, gr.nonuniform) && c->nn16_filter != 0 && Q < (1L << 31)) {
+        if (wants_filter(c, gr, Q) && Q < (1L << 31)) {
             CHK(grid_companions(c, cl, gr, cl.n, true, c->use_boxes));
             if (gr.filter_ok) {
-                CHK(c->kq_slot.reserve((size_t)4 * Q)); CHK(c->kp_slot.reserve((size_t)4 * Q));
-                CHK(c->nn_state.reserve((size_t)Q));
-                if (c->nn_redo.cap < (size_t)Q + 2) {
-                    CHK(c->nn_redo.reserve((size_t)Q + 2));
-                    HIPCHK(hipMemsetAsync(c->nn_redo.p, 0, 2 * sizeof(uint32_t), c->stream));
-                }
-                launch_slot_queries(c->stream, qsoa, qsoa + qpad, qsoa + 2 * qpad, nullptr, prev_p2, Q, c->kq_slot.p, c->kp_slot.p);
-                const unsigned long long *cbox = c->use_boxes ? gr.cell_box.p : nullptr;
-                unsigned *tie_cnt = c->nn_redo.p + c->nn_parity, *tie_clear = c->nn_redo.p + (c->nn_parity ^ 1);
-                uint32_t *tie_list = c->nn_redo.p + 2;
-                unsigned long long *wk = c->count_work ? c->match_work.p : nullptr;
-                c->last_match_kernel = 6;
-                Timed t(c, SICP_K_KNN1);
-                const bool all_far = c->nn16_filter == 1 || gr.nonuniform;
-                if (!all_far)
-                    launch_grid_nn16f(c->stream, 16, false, nullptr, c->kq_slot.p, c->kp_slot.p, Q, gr.g, gr.c0, gr.eps_p, gr.cell_start.p,
-                                      gr.recf.p, gr.rec.p, false, H, H ? &Hinv : nullptr, cl.rmax, max_d2, cl.idx_base, d2_out,
-                                      idx_out, p2_out, wk, 0, c->nn_state.p, tie_list, tie_cnt);
-                launch_grid_nn16f(c->stream, 16, true, nullptr, c->kq_slot.p, c->kp_slot.p, Q, gr.g, gr.c0, gr.eps_p, gr.cell_start.p,
-                                  gr.recf.p, gr.rec.p, false, H, H ? &Hinv : nullptr, cl.rmax, max_d2, cl.idx_base, d2_out, idx_out,
-                                  p2_out, wk, 0, all_far ? nullptr : c->nn_state.p, tie_list, tie_cnt);
-                launch_grid_nn_redo(c->stream, qsoa, qsoa + qpad, qsoa + 2 * qpad, Q, p2_out ? p2_out : prev_p2, gr.g, gr.cell_start.p, gr.rec.p,
-                                    nullptr, H, H ? &Hinv : nullptr, cl.rmax, max_d2, cl.idx_base, d2_out, idx_out, p2_out, wk,
-                                    p2_out ? NN_TIGHT : 0, nullptr, cbox, tie_list, tie_cnt, tie_clear, coarse);
-                c->nn_parity ^= 1;
+                FilteredSearch F = {S, &c->kq_slot, &c->kp_slot, true, prev_p2, nullptr, 16, c->nn16_filter == 1 || gr.nonuniform,
+                                    p2_out ? NN_TIGHT : 0};
+                set_level(F.S, gr);
+                F.S.cell_box = c->use_boxes ? gr.cell_box.p : nullptr;
+                F.S.prev_p2 = p2_out ? p2_out : prev_p2;
+                CHK(filtered_search(c, F));
                 HIPCHK(hipGetLastError());
                 return SICP_OK;
             }
@@ -130,11 +155,11 @@ int knn1_device(sicp_ctx *c, int slot, const double *qsoa, long Q, long qpad, co
         // (stand-alone searches of a few queries do not pay for the boxes of a cloud: SICP_BOXES=2 builds them anyway -- tests)
         const bool boxes = c->use_boxes && (c->boxes_always || Q >= 4096);
         if (boxes) CHK(grid_companions(c, cl, gr, cl.n, false, true));
+        set_level(S, gr);
+        S.cell_box = boxes ? gr.cell_box.p : nullptr;
         {
             Timed t(c, SICP_K_KNN1);
-            launch_grid_nn(c->stream, qsoa, qsoa + qpad, qsoa + 2 * qpad, Q, prev_p2, gr.g, gr.cell_start.p, gr.rec.p, H,
-                           H ? &Hinv : nullptr, cl.rmax, max_d2, cl.idx_base, d2_out, idx_out, p2_out,
-                           c->count_work ? c->match_work.p : nullptr, four, boxes ? gr.cell_box.p : nullptr, coarse);
+            launch_grid_nn(c->stream, S, four ? NN_LANES16 : NN_WAVE);
         }
         HIPCHK(hipGetLastError());
         return SICP_OK;
@@ -294,8 +319,6 @@ int knnk_device(sicp_ctx *c, int slot, const double *qsoa, long Q, long qpad, in
     }
     return SICP_OK;
 }
-
-// fused reduction at parameters x over [lo,hi) -> host out[30] (sums over ranks if sharded)
 
 }  // namespace sicph
 
