@@ -265,7 +265,10 @@ class SimpleICP:
         # ... and only when a whole copy of the cloud (+ its grid) fits comfortably in every rank's free memory; a cloud that
         # only fits in shards stays sharded whatever the correspondence count (the verdict is the same on every rank of a
         # homogeneous node; SICP_PARTITION pins it explicitly)
-        qshard = sharded and (os.environ.get("SICP_PARTITION", "") == "queries"
+        # ... and always when the searched cloud has fewer rows than there are ranks: some index shard would be empty, which an
+        # upload refuses -- on those ranks alone, while the others went on into the run's collectives.  Every rank knows both
+        # numbers, so all of them take the replicated cloud together (n_search <= pc2.num_points covers the first upload too)
+        qshard = sharded and (n_search < world or os.environ.get("SICP_PARTITION", "") == "queries"
                               or (os.environ.get("SICP_PARTITION", "") != "cloud" and correspondences >= 100_000
                                   and dist.agree(dist.queries_partition_fits(ctx, n_search))))
 

@@ -1,6 +1,7 @@
-"""N > 1 path on CPU: world_size-2 gloo run of the exchange step in simpleicp_amd/dist.py --
+"""N > 1 path on CPU: gloo runs (world 2, 3 and 8) of the exchange step in simpleicp_amd/dist.py --
 the same functions the RCCL path calls on device tensors.  Local shard results come from the
 CPU oracle (tests may use it); the assertion is that sharded == unsharded, bit-exact."""
+import datetime
 import os
 import socket
 import sys
@@ -25,7 +26,8 @@ def _worker(rank, world, port, tmp):
     os.environ["MASTER_PORT"] = str(port)
     import torch
     import torch.distributed as td
-    td.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(1)                                 # (eight ranks on a few CPUs)
+    td.init_process_group("gloo", rank=rank, world_size=world, timeout=_GLOO_TIMEOUT)
     try:
         from oracle import orc
         from simpleicp_amd import dist
@@ -35,10 +37,16 @@ def _worker(rank, world, port, tmp):
         n, q = 30_001, 700
         Xm = np.round(rng.uniform(-5, 5, (n, 3)), 1)         # quantised -> exact ties across shards
         Xm[n // 2:n // 2 + 200] = Xm[:200]                   # duplicates living in different shards
+        Xm[5 * n // 6:5 * n // 6 + 200] = Xm[:200]           # ... a third copy: from world 3 on, three ranks hold each of them
         Xm[Xm == 0.0] = -0.0                                 # coordinates whose bit pattern a SUM would not carry (the key exchange's max must)
         Qp = np.round(rng.uniform(-5, 5, (q, 3)), 1)
         H = orc.params_to_H(np.array([0.1, -0.2, 0.05, 0.3, 0.1, -0.2]))
+        # queries sitting on the triplicated points under H: their winner's distance is held, bit for bit, by every shard with a copy
+        Qp = np.vstack((Qp, Xm[:60] @ H[:3, :3].T + H[:3, 3]))
+        q = len(Qp)
         lo, hi = dist.shard_bounds(n, rank, world)
+        owner = lambda row: next(r for r in range(world) if dist.shard_bounds(n, r, world)[1] > row)
+        assert len({owner(row) for row in (0, n // 2, 5 * n // 6)}) == min(world, 3)
 
         for max_dist in (np.inf, 0.15):
             idx, d2 = orc.knn(Xm[lo:hi], Qp, k=1, H=H, max_dist=max_dist, idx_base=lo)
@@ -65,7 +73,30 @@ def _worker(rank, world, port, tmp):
             gd2 = [torch.empty_like(t_d2) for _ in range(world)]
             td.all_gather(gd2, torch.from_numpy(d2))
             holders = sum((g.numpy() == t_d2.numpy()) & np.isfinite(g.numpy()) for g in gd2)
-            assert (holders >= 2).any()
+            assert (holders >= min(world, 3)).any()          # (from world 3 on: a tie among at least three ranks)
+
+        # empty shards: a cloud of 5 rows over the ranks -- at world 8 ranks 5 to 7 hold [lo, lo) and offer "no candidate"
+        # (idx -1, d2 +inf, xyz 0) for every query; both exchanges must still give the brute force over the whole cloud
+        X5 = np.round(np.random.default_rng(11).uniform(-5, 5, (5, 3)), 1)
+        X5[1] = X5[3]                                        # an exact tie between two ranks' single rows
+        lo5, hi5 = dist.shard_bounds(len(X5), rank, world)
+        if world == 8:
+            assert (hi5 - lo5) == (1 if rank < 5 else 0)
+        for max_dist in (np.inf, 2.0):
+            if hi5 > lo5:
+                idx, d2 = orc.knn(X5[lo5:hi5], Qp, k=1, H=H, max_dist=max_dist, idx_base=lo5)
+                idx, d2 = idx[:, 0].copy(), d2[:, 0].copy()
+            else:
+                idx, d2 = np.full(q, -1, np.int64), np.full(q, np.inf)
+            xyz = np.where((idx >= 0)[:, None], X5[np.maximum(idx, 0)], 0.0)
+            fidx, fd2 = orc.knn(X5, Qp, k=1, H=H, max_dist=max_dist)
+            ok = fidx[:, 0] >= 0
+            assert ok.any() and (np.isinf(max_dist) or (~ok).any())
+            for exchange in (dist.exchange_best_match, dist.exchange_best_keys):
+                t_d2, t_idx, t_xyz = torch.from_numpy(d2.copy()), torch.from_numpy(idx.copy()), torch.from_numpy(xyz.copy())
+                exchange(t_d2, t_idx, t_xyz)
+                assert np.array_equal(t_idx.numpy(), fidx[:, 0]) and np.array_equal(t_d2.numpy(), fd2[:, 0]), exchange.__name__
+                assert np.array_equal(t_xyz.numpy()[ok], X5[fidx[ok, 0]]) and np.all(t_xyz.numpy()[~ok] == 0), exchange.__name__
 
         # query shards (SURVEY 8e "alternative"): every rank matches its slice of the queries in the WHOLE cloud;
         # gathering the slices in rank order restores the full result -- no reduction, bit-exact by construction
@@ -79,6 +110,21 @@ def _worker(rank, world, port, tmp):
         dist.exchange_query_slices(t_d2, t_idx, t_xyz)
         assert np.array_equal(t_idx.numpy(), fidx[:, 0]) and np.array_equal(t_d2.numpy(), fd2[:, 0])
         assert np.array_equal(t_xyz.numpy(), Xm[fidx[:, 0]])
+        # ... with trailing slices empty: at world 8, Q = 41 (per 6) leaves rank 7 nothing, Q = 9 (per 2) ranks 5 to 7
+        for qs in (41, 9):
+            per = (qs + world - 1) // world
+            a, b = min(qs, per * rank), min(qs, per * rank + per)
+            if world == 8:
+                assert (b - a == 0) == (rank >= {41: 7, 9: 5}[qs])
+            t_d2 = torch.full((qs,), float("nan"), dtype=torch.float64); t_idx = torch.full((qs,), -7, dtype=torch.int64)
+            t_xyz = torch.full((qs, 3), float("nan"), dtype=torch.float64)
+            if b > a:
+                sidx, sd2 = orc.knn(Xm, Qp[a:b], k=1, H=H)
+                t_d2[a:b] = torch.from_numpy(sd2[:, 0]); t_idx[a:b] = torch.from_numpy(sidx[:, 0])
+                t_xyz[a:b] = torch.from_numpy(Xm[sidx[:, 0]])
+            dist.exchange_query_slices(t_d2, t_idx, t_xyz)
+            assert np.array_equal(t_idx.numpy(), fidx[:qs, 0]) and np.array_equal(t_d2.numpy(), fd2[:qs, 0])
+            assert np.array_equal(t_xyz.numpy(), Xm[fidx[:qs, 0]])
 
         # sharded 6x6 normal-equation reduction + SUM exchange == unsharded (to rounding)
         p1 = rng.uniform(-5, 5, (q, 3))
@@ -99,7 +145,10 @@ def _worker(rank, world, port, tmp):
         td.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3])
+_GLOO_TIMEOUT = datetime.timedelta(seconds=180)          # a rank that stops makes the others fail instead of waiting
+
+
+@pytest.mark.parametrize("world", [2, 3, 8])
 def test_exchange_world(world, tmp_path):
     import torch.multiprocessing as mp
     mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
@@ -109,13 +158,16 @@ def test_exchange_world(world, tmp_path):
 def test_shard_bounds_partition():
     sys.path.insert(0, str(ROOT))
     from simpleicp_amd.dist import shard_bounds
-    for n in (0, 1, 7, 8, 10_000_001):
+    for n in (0, 1, 2, 5, 7, 8, 10_000_001):
         for world in (1, 2, 3, 8):
             b = [shard_bounds(n, r, world) for r in range(world)]
             assert b[0][0] == 0 and b[-1][1] == n
             assert all(b[i][1] == b[i + 1][0] for i in range(world - 1))
             sizes = [hi - lo for lo, hi in b]
             assert max(sizes) - min(sizes) <= 1
+            if n < world:                                    # fewer rows than ranks: one row each, the trailing ranks empty
+                assert sizes == [1] * n + [0] * (world - n)
+    assert [hi - lo for lo, hi in (shard_bounds(5, r, 8) for r in range(8))] == [1, 1, 1, 1, 1, 0, 0, 0]
 
 
 def _worker_allgather(rank, world, port, tmp):
@@ -127,7 +179,8 @@ def _worker_allgather(rank, world, port, tmp):
     os.environ["MASTER_PORT"] = str(port)
     import torch
     import torch.distributed as td
-    td.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(1)
+    td.init_process_group("gloo", rank=rank, world_size=world, timeout=_GLOO_TIMEOUT)
     try:
         from simpleicp_amd import dist
         rng = np.random.default_rng(100 + rank)
@@ -151,6 +204,8 @@ def _worker_allgather(rank, world, port, tmp):
         t_d2, t_idx, t_xyz = torch.from_numpy(d2.copy()), torch.from_numpy(idx.copy()), torch.from_numpy(xyz.copy())
         dist.exchange_best_match(t_d2, t_idx, t_xyz)
         assert np.array_equal(t_idx.numpy(), bi) and np.array_equal(t_d2.numpy(), bd) and np.array_equal(t_xyz.numpy(), bx)
+        if world >= 3:                                       # the data did hold ties among three or more ranks
+            assert ((G[:, :, 0] == bd) & (G[:, :, 1].copy().view(np.int64) >= 0)).sum(axis=0).max() >= 3
         Path(tmp, f"ag{rank}").write_text("ok")
     finally:
         td.destroy_process_group()
@@ -160,6 +215,15 @@ def test_allgather_exchange_world2(tmp_path):
     import torch.multiprocessing as mp
     mp.spawn(_worker_allgather, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
     assert all((tmp_path / f"ag{r}").exists() for r in range(2))
+
+
+@pytest.mark.parametrize("world", [3, 8])
+def test_allgather_exchange_many_ranks(world, tmp_path):
+    """The records' all-gather and lexicographic reduce of test_allgather_exchange_world2 over more ranks: 8 records per query,
+    exact d2 ties among three and more of them."""
+    import torch.multiprocessing as mp
+    mp.spawn(_worker_allgather, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    assert all((tmp_path / f"ag{r}").exists() for r in range(world))
 
 
 class _FakeCtx:
