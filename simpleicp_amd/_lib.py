@@ -46,6 +46,11 @@ DEVICE_EXPORTS = ["sicp_device_version", "sicp_cloud_upload_strided", "sicp_sele
 DEVICE_VERSION = 1
 DT_F32, DT_F64 = 1, 2
 
+# include/simpleicp_hip_normals.h: rejection by the angle between normals, a companion ABI with a version of its own too
+NORMALS_EXPORTS = ["sicp_normals_version", "sicp_cloud_set_normals", "sicp_normal_angle_set", "sicp_corr_reject_normal_angle",
+                   "sicp_normal_angle_info", "sicp_normal_cache_read"]
+NORMALS_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -169,6 +174,14 @@ def load():
         L.sicp_cloud_write_strided.argtypes = [vp, cint, vp, vp, cint, i64, i64]
         for name in DEVICE_EXPORTS:
             getattr(L, name).restype = cint
+    if all(hasattr(L, name) for name in NORMALS_EXPORTS):
+        L.sicp_cloud_set_normals.argtypes = [vp, cint, vp, vp, i64, i64]
+        L.sicp_normal_angle_set.argtypes = [vp, dbl, cint]
+        L.sicp_corr_reject_normal_angle.argtypes = [vp, dbl, cint, vp, vp, C.POINTER(i64)]
+        L.sicp_normal_angle_info.argtypes = [vp, vp]
+        L.sicp_normal_cache_read.argtypes = [vp, vp, vp]
+        for name in NORMALS_EXPORTS:
+            getattr(L, name).restype = cint
     _lib = L
     return L
 
@@ -220,6 +233,19 @@ def device_version():
     v = L.sicp_device_version()
     if v != DEVICE_VERSION:
         raise BackendError(f"{LIB_PATH} implements device version {v}, this binding needs {DEVICE_VERSION}")
+    return v
+
+
+def normals_version():
+    """SICP_NORMALS_VERSION of the loaded library; BackendError when it has no normal-angle entry points."""
+    L = load()
+    missing = [name for name in NORMALS_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise BackendError(f"{LIB_PATH} has no normal-angle entry points ({', '.join(missing)}): it predates "
+                           "include/simpleicp_hip_normals.h; rebuild with `python -m simpleicp_amd.build`")
+    v = L.sicp_normals_version()
+    if v != NORMALS_VERSION:
+        raise BackendError(f"{LIB_PATH} implements normals version {v}, this binding needs {NORMALS_VERSION}")
     return v
 
 
@@ -458,6 +484,58 @@ class Context:
         n = int(n_global if n_global is not None else (len(pl) if r is None else self.size(slot)))
         dummy = np.zeros(1, np.float32)
         self._chk(self._L.sicp_cloud_set_planarity(self._h, slot, _ptr(r), _ptr(pl if len(pl) else dummy), len(pl), n))
+
+    def set_normals(self, slot, normals=None, rows=None, n_global=None):
+        """The cloud's normal columns (sicp_cloud_set_normals), like set_planarity: a dense (n, 3) float32 block by global point
+        index, or (rows, normals) pairs with NaN elsewhere; None = no such columns."""
+        normals_version()
+        if normals is None:
+            self._chk(self._L.sicp_cloud_set_normals(self._h, slot, None, None, 0, 0))
+            return
+        nv = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        if r is not None and len(r) != len(nv):
+            raise ValueError("rows and normals must have the same length")
+        n = int(n_global if n_global is not None else (len(nv) if r is None else self.size(slot)))
+        dummy = np.zeros(3, np.float32)
+        self._chk(self._L.sicp_cloud_set_normals(self._h, slot, _ptr(r), _ptr(nv if len(nv) else dummy), len(nv), n))
+
+    def normal_angle_set(self, cos_max=None, k=10):
+        """The ctx setting sicp_icp_run / sicp_icp_iterate honour (sicp_normal_angle_set): reject correspondences whose normals
+        have |cos| < cos_max; None = off."""
+        normals_version()
+        self._chk(self._L.sicp_normal_angle_set(self._h, 0.0 if cos_max is None else float(cos_max), int(k)))
+
+    def corr_reject_normal_angle(self, cos_max, k=10, H=None, pc2_normals=None):
+        """The operator (sicp_corr_reject_normal_angle) over the alive correspondences; pc2_normals: (Q, 3) float32 per
+        correspondence, None = the movable slot's columns or normals estimated on the device.  Returns how many are still alive."""
+        normals_version()
+        Hc = None if H is None else _f64(H).reshape(16)
+        nv = None
+        if pc2_normals is not None:
+            nv = np.ascontiguousarray(pc2_normals, dtype=np.float32)
+            if nv.shape != (self._Q, 3):
+                raise ValueError("pc2_normals must have one row per correspondence")
+        n = C.c_int64()
+        self._chk(self._L.sicp_corr_reject_normal_angle(self._h, float(cos_max), int(k), _ptr(Hc), _ptr(nv), C.byref(n)))
+        return n.value
+
+    def normal_angle_info(self):
+        """Since icp_setup (sicp_normal_angle_info): normals estimated on demand, correspondences the verdict dropped in the last
+        iteration, bytes of the cache, iterations whose miss list was empty."""
+        normals_version()
+        out = np.zeros(4, np.int64)
+        self._chk(self._L.sicp_normal_angle_info(self._h, _ptr(out)))
+        return {"normals_estimated": int(out[0]), "normal_angle_dropped": int(out[1]), "normal_cache_bytes": int(out[2]),
+                "normal_miss_free_iterations": int(out[3])}
+
+    def normal_cache(self):
+        """The movable slot's cache of estimated normals (sicp_normal_cache_read): ((n, 3) float32, (n,) bool "is there")."""
+        normals_version()
+        n = self.size(MOV)
+        nv, have = np.empty((n, 3), np.float32), np.empty(n, np.uint8)
+        self._chk(self._L.sicp_normal_cache_read(self._h, _ptr(nv), _ptr(have)))
+        return nv, have.astype(bool)
 
     # -- nearest neighbours --
     def knn(self, slot, q_xyz, k=1, H=None, max_dist=np.inf):

@@ -157,7 +157,28 @@ class CorrPts:
         self._drop_dead_rows(ctx)
 
     def reject_wrt_to_angle_between_normals(self) -> None:
-        raise NotImplementedError                               # as in the reference (corrpts.py:190-193)
+        """The reference's stub (corrpts.py:190-193), kept as it is: it takes no threshold, so it cannot be given a meaning without
+        changing its signature.  The working operator is ``reject_wrt_normal_angle(max_angle)``."""
+        raise NotImplementedError
+
+    def reject_wrt_normal_angle(self, max_angle: float, neighbors: int = 10) -> None:
+        """Keeps the correspondences whose normals -- unoriented -- enclose at most ``max_angle`` degrees (0 < max_angle <= 90;
+        NaN normals fail), contract (N) of DESIGN.md.  pc2's normal is its nx / ny / nz of the matched point when pc2 carries those
+        columns; otherwise it is estimated on the device from the point's ``neighbors`` nearest neighbours among the points of
+        pc2 that were searched (its selected ones)."""
+        import math
+        if not len(self._df.columns):
+            raise KeyError("pc1_idx")
+        if not 0.0 < float(max_angle) <= 90.0:
+            raise ValueError("max_angle must be an angle in degrees, > 0 and <= 90")
+        if self._Q == 0:
+            return
+        ctx = self._device()
+        nv2 = None
+        if {"nx", "ny", "nz"}.issubset(self._pc2.columns):
+            nv2 = self._per_correspondence(np.column_stack([self._of(2, c) for c in ("nx", "ny", "nz")]).astype(np.float32), np.float32)
+        ctx.corr_reject_normal_angle(math.cos(math.radians(float(max_angle))), neighbors, None, nv2)
+        self._drop_dead_rows(ctx)
 
     # ---- I/O (corrpts.py:213-237) ---------------------------------------------------------------
     def write_xyz(self, file: Path):

@@ -219,6 +219,8 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->resid.release(); c->flag.release(); c->keep.release(); c->small.release(); c->ne_partial.release();
     c->lm_bar_buf.release(); c->lm_gsum.release(); c->ticket.release(); c->icp_dev.release(); c->lm_dev.release(); c->resid2.release();
     c->corr_pl.release();
+    for (auto &cl : c->cloud) { cl.nv.release(); cl.nrm2.release(); cl.nrm2_have.release(); }
+    c->na.cnt.release(); c->na.list_q.release(); c->na.list_m.release(); c->na.iota.release(); c->na.cov.release(); c->na.per_q.release();
     c->batch_tab.release(); c->batch_map.release();
     c->sel_blk.release(); c->sel_pos.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);

@@ -26,6 +26,7 @@ bool batchable(sicp_ctx *c, const sicp_batch_member &m)
 {
     if (check_iter_args(c, &m.params) != SICP_OK) return false;         // (joins the slots' background uploads: check_slot)
     if (!device_tail(c) || c->Q > SOLVE_MAX_Q || !takes_grid_search(c)) return false;
+    if (normal_angle_on(c)) return false;                               // (its launches are not part of the batched chain)
     return !(c->timing || c->count_work || c->host_trace || c->solve_trace);
 }
 

@@ -343,6 +343,7 @@ int upload_begin(sicp_ctx *c, int slot, int64_t n, int64_t index_base)
     cl.n = n; cl.npad = round_up(n, TILE_PTS); cl.idx_base = index_base;
     cl.grid.valid = false; cl.sub_grid.valid = false; cl.coarse_grid.valid = false;
     cl.pl_n = 0;                                       // a new cloud has no planarity column until one is set
+    cl.nv_n = 0; cl.nrm2_valid = false;                // ... nor normals: neither its own columns nor estimated ones
     // (a new movable cloud: earlier matches are not its points -- neither the by-query ones nor those the filtered search keeps by slot,
     // which an operator-route match in between would not rebuild)
     if (slot == SICP_MOV) { c->have_prev_match = false; c->slot_cnt = -1; }
@@ -561,6 +562,7 @@ SICP_EXPORT int sicp_cloud_transform(sicp_ctx *c, int slot, const double H[16])
     launch_transform(c->stream, cl.x(), cl.y(), cl.z(), cl.n, X);
     HIPCHK(hipGetLastError());
     cl.grid.valid = false; cl.sub_grid.valid = false; cl.coarse_grid.valid = false;
+    cl.nrm2_valid = false;                                // (normals estimated in the old frame)
     return cloud_stats(c, slot);                          // new bounding box / largest norm (also the synchronisation point)
 }
 

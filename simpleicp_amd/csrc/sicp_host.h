@@ -94,6 +94,11 @@ struct Cloud {
     DevBuf<float> pl;     // `planarity` column by GLOBAL index (pl_n entries; 0 = the cloud has no such column)
     int64_t pl_n = 0;
     DevBuf<double> xyz;   // x[npad] | y[npad] | z[npad]
+    // rejection by the angle between normals (sicp_nangle.hip): the cloud's own normal columns by GLOBAL index (nv_n points; 0 = none),
+    // else normals estimated on demand, kept by local index with one "is there" bit per point (a normal that is there may be NaN)
+    DevBuf<float> nv; int64_t nv_n = 0;
+    DevBuf<float> nrm2; DevBuf<uint32_t> nrm2_have;
+    bool nrm2_valid = false; int nrm2_k = 0;       // (emptied where the grid is invalidated: another cloud, a transform; or another k)
     // every 64th point with a grid of its own (built on demand for a cold chained search): the nearest SUBSAMPLE point is a cloud
     // point, so its distance bounds the answer -- one cheap search hands the real one a radius instead of a doubling ladder
     DevBuf<double> sub_xyz; int64_t sub_n = 0, sub_npad = 0;
@@ -120,6 +125,19 @@ struct Rccl {
     decltype(&ncclCommUserRank) CommUserRank = nullptr;
     decltype(&ncclCommAbort) CommAbort = nullptr;
     std::string why;               // why the library is unusable (dlerror is read ONCE, where it is fresh)
+};
+
+// rejection by the angle between normals: the ctx's setting and the buffers of an iteration's launches (sicp_nangle.hip)
+struct NormalAngle {
+    double cos_max = 0.0;          // > 0: sicp_icp_run / sicp_icp_iterate reject by contract (N)
+    int k = 0;                     // neighbours of the normals estimated on demand
+    int par = 0;                   // which counter pair the next iteration's launches use
+    long iota_n = 0;               // leading words of `iota` that hold 0, 1, 2, ... (0: the four-per-wave sweep's spill list was written there)
+    bool counters_stale = false;   // sicp_icp_setup since the counters were last cleared
+    DevBuf<unsigned> cnt;          // sicp_nangle.hip: NA_*
+    DevBuf<uint32_t> list_q, list_m, iota;   // the miss list (correspondence, local point); 0, 1, 2, ... or the sweep's spill list
+    DevBuf<double> cov;            // (list position, 6)
+    DevBuf<float> per_q;           // the operator's per-correspondence normals
 };
 
 struct EventPair { hipEvent_t a, b; int kernel; };
@@ -230,6 +248,7 @@ struct sicp_ctx {
     hipEvent_t dl_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool have_iter = false;
     bool have_corr = false;        // sicp_corr_match has run: m_idx / m_p2 / dist hold its correspondences, `keep` the alive mask
+    NormalAngle na;
     DevBuf<float> corr_pl;         // per-correspondence planarity columns handed to sicp_corr_reject_planarity: pc1 [Q] | pc2 [Q]
     double last_x[6] = {0}, last_w = 1.0, last_obs[6] = {0}, last_ow[6] = {0};
     double last_ne[30] = {0};      // normal equations at last_x (fused path caches them)
@@ -422,6 +441,13 @@ int take_record(sicp_ctx *c, const sicp_iter_params *P0, const double *o, sicp_i
                 double xcur[6], double *last_move, bool *over);
 bool device_tail(const sicp_ctx *c);
 int check_iter_args(sicp_ctx *c, const sicp_iter_params *P);
+int check_corr(sicp_ctx *c);
+int corr_alive_stats(sicp_ctx *c, const double *also4, double **h_st_out);
+// rejection by the angle between normals (sicp_nangle.hip): is the ctx's setting on; a run's / an iteration's preparation (buffers,
+// cache, counters); one iteration's launches on c->flag -- H from the chained run's loop state `st`, or by value
+bool normal_angle_on(const sicp_ctx *c);
+int normal_angle_prepare(sicp_ctx *c);
+int normal_angle_enqueue(sicp_ctx *c, const IcpDev *st, const Xf *H);
 
 }  // namespace sicph
 

@@ -188,6 +188,7 @@ SICP_EXPORT int sicp_icp_setup(sicp_ctx *c, const int64_t *sel_idx, int64_t Q, c
     c->sel_window_hits = 0; c->last_sel_rounds[0] = c->last_sel_rounds[1] = 0;
     c->last_xchg_form = 0; c->xchg_count = 0;
     c->reject_prior = false;
+    c->na.counters_stale = true;
     return sync(c);
 }
 
@@ -336,6 +337,7 @@ int chain_prepare(sicp_ctx *c, const sicp_iter_params *P0, bool *grid, double *l
         hl.w = hs.w; hl.first = 1;
         HIPCHK(hipMemcpyAsync(c->lm_dev.p, &hl, sizeof hl, hipMemcpyHostToDevice, c->stream));
     }
+    if (normal_angle_on(c)) CHK(normal_angle_prepare(c));
     *last_move = c->have_prev_match ? c->last_move : std::numeric_limits<double>::infinity();
     return SICP_OK;
 }
@@ -581,6 +583,14 @@ int enqueue_iteration(sicp_ctx *c, ChainRun &L)
     bool post_done = !p.filt && p.post_done;
     const bool packed = !p.filt && (p.pack || p.pack_idx) && p.cnt > 0;
     CHK(enqueue_exchange(c, L.A, p, packed, &post_done));
+    if (normal_angle_on(c)) {
+        // behind the last launch that writes the flags (here k_postmatch, where the match left them to it) and before the tail reads them
+        // (k_postmatch is thereby enqueued outside enqueue_tail's SICP_K_SELECT timing scope: with the rejection on, sicp_timing_get's
+        // reject_select column for Q <= 16 384 no longer takes it in, and the new launches are in no column)
+        enqueue_postmatch(c, L.A, post_done);
+        post_done = true;
+        CHK(normal_angle_enqueue(c, c->icp_dev.p, nullptr));      // (H: the loop state's, as k_postmatch reads it)
+    }
     L.A.seq = (double)(++c->solve_seq);
     L.seqs[L.launched % REC_RING] = L.A.seq;
     CHK(enqueue_tail(c, L.A, post_done, c->h_rec + (L.launched % REC_RING) * REC_DOUBLES));
@@ -739,6 +749,7 @@ int iterate_host_lm(sicp_ctx *c, const sicp_iter_params *P, sicp_iter_result *R)
     launch_postmatch(c->stream, c->q.p, c->q.p + c->qpad, c->q.p + 2 * c->qpad, c->normals.p, c->planarity.p, c->m_p2.p,
                      c->m_idx.p, Q, X, (float)P->min_planarity, c->cloud[SICP_MOV].pl_n > 0 ? c->cloud[SICP_MOV].pl.p : nullptr,
                      c->cloud[SICP_MOV].pl_n, c->dist.p, c->flag.p);
+    if (normal_angle_on(c)) { CHK(normal_angle_prepare(c)); CHK(normal_angle_enqueue(c, nullptr, &X)); }
     double *h_st = c->h_small + 160;                      // pinned: [0..3] rejection, [4..6] n / mean / std, [15] ticket
     double seq = (double)(++c->solve_seq);
     {

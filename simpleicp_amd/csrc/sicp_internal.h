@@ -199,6 +199,11 @@ void launch_grid_knn_sweep(hipStream_t s, const double *qx, const double *qy, co
                            float *normals, float *planarity, unsigned long long *work, long batch_override = 0,
                            uint32_t *redo = nullptr /* Q + 1 words: enables the four-queries-per-wave kernel */, int group = 0 /* 0 auto, 1, 4 */);
 
+void launch_grid_knn_sweep_list(hipStream_t s, const double *cx, const double *cy, const double *cz, const uint32_t *points,
+                                const uint32_t *iota, const unsigned *count, long max_count, int k, const GridGeom &G,
+                                double avg_per_cell, const uint32_t *cell_start, const void *rec, double rmax, double *cov,
+                                uint32_t *spill = nullptr, unsigned *spill_count = nullptr);
+
 void launch_pack_best(hipStream_t s, const double *d2, const int64_t *idx, const double *p2, long Q, double *rec);
 // the job-wide winner by all-reduces on 8-byte keys (sicp_kernels.hip, "the same winner by three all-reduces")
 void launch_xkey_d2(hipStream_t s, const double *d2, const int64_t *idx, long Q, unsigned long long *key);

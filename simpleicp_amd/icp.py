@@ -17,6 +17,7 @@ Differences by design (documented in DESIGN.md):
 from __future__ import annotations
 
 import logging
+import math
 import time
 from dataclasses import fields
 from pathlib import Path
@@ -63,8 +64,37 @@ def _no_overlap(max_overlap_distance) -> SimpleICPException:
     )
 
 
+def _cos_of_max_angle(max_normal_angle):
+    """max_normal_angle (degrees, None = no such rejection) -> the cos_max of contract (N), computed once; 0 < angle <= 90."""
+    if max_normal_angle is None:
+        return None
+    try:
+        ok = 0.0 < float(max_normal_angle) <= 90.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise SimpleICPException("max_normal_angle must be an angle in degrees, > 0 and <= 90.")
+    return math.cos(math.radians(float(max_normal_angle)))
+
+
+def _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle):
+    """The context's normal-angle setting for the run about to start -- set on every run, off included, so that a pooled context
+    never inherits it --, with pc2's own nx, ny, nz columns when it has them (of the selected subset when pc2 is partially selected;
+    without them the normals are estimated on the device among the points of the movable slot, i.e. of that subset)."""
+    cos_max = _cos_of_max_angle(max_normal_angle)
+    if not hasattr(ctx, "normal_angle_set"):
+        # (a stand-in backend that predates the setting has nothing to switch off; asked to switch it on, it cannot)
+        if cos_max is not None:
+            raise _lib.BackendError("this backend has no rejection by the angle between normals")
+        return
+    if cos_max is not None and pc2 is not None and {"nx", "ny", "nz"}.issubset(pc2.columns):
+        nv = np.column_stack([np.asarray(pc2[c].to_numpy(), dtype=np.float32) for c in ("nx", "ny", "nz")])
+        ctx.set_normals(_lib.MOV, nv if msel is None else nv[msel], n_global=n_search)
+    ctx.normal_angle_set(cos_max, neighbors)
+
+
 def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors, max_overlap_distance,
-                      info=None):
+                      info=None, max_normal_angle=None):
     """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass under
     the initial H, select_n_points, normals (or pc1's nx, ny, nz, planarity columns), the movable cloud's selected subset and its
     planarity column, sicp_icp_setup.  Returns the selected rows of pc1.  info: where the progress lines go (the log)."""
@@ -94,11 +124,12 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
         # reject_wrt_planarity tests pc2's column as well when it exists (corrpts.py:158-163; NaN fails)
         rows, vals = pc2._planarity_pairs(msel)
         ctx.set_planarity(_lib.MOV, vals, rows=rows, n_global=n_search)
+    _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle)
     ctx.icp_setup(sel, normals, planarity)
     return sel
 
 
-def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None):
+def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None, max_normal_angle=None):
     """_select_and_setup for clouds uploaded from device memory (run_tensors, run_batch's device pairs; every point selected, no
     normals or planarity columns): the same steps with every array they hand on left in device memory -- the overlap verdicts, the
     kept rows and the picks of select_n_points (sicp_select_n_device), the normals.  alloc(shape, kind) returns a device buffer
@@ -118,6 +149,7 @@ def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_over
     nv, nv_p = alloc((Q, 3), "f32")
     pl, pl_p = alloc((Q,), "f32")
     ctx.estimate_normals_into(_lib.FIX, sel_p, Q, int(neighbors), nv_p, pl_p)
+    _set_normal_angle(ctx, None, None, 0, neighbors, max_normal_angle)
     ctx.icp_setup_device(sel_p, Q, nv_p, pl_p)
     return sel, nv, pl
 
@@ -202,6 +234,13 @@ def _rbp_and_residuals(ctx, R, obs, ow, x_start, x):
 
 
 class SimpleICP:
+    # Rejection by the angle between normals: degrees, 0 < angle <= 90; None = off.  An attribute, set after
+    # construction (``icp.max_normal_angle = 30.0``), because run()'s signature is the reference's.  A correspondence whose fixed and
+    # matched movable normals (unoriented) enclose a larger angle is dropped together with the planarity test.  The movable normals
+    # are pc2's nx / ny / nz columns when it has them, else they are estimated on the device with run()'s ``neighbors`` among the
+    # points of the movable cloud that take part in the search (its selected subset when it is partially selected).
+    max_normal_angle: Optional[float] = None
+
     def __init__(self, verbose: bool = True) -> None:
         self.pc1: Optional[PointCloud] = None
         self.pc2: Optional[PointCloud] = None
@@ -230,6 +269,7 @@ class SimpleICP:
         """See the reference docstring (simpleicp.py:88-133): identical arguments/returns.
         Returns (H, X_mov_transformed, rbp, distance_residuals)."""
         self._check_arguments(distance_weights, rbp_observed_values, rbp_observation_weights)
+        _cos_of_max_angle(self.max_normal_angle)
         t_start = time.time()
         pc1, pc2 = self.pc1, self.pc2
         ctx = backend.get_context()
@@ -314,7 +354,7 @@ class SimpleICP:
             X_fix, X_mov = pc1.X, pc2.X
 
         sel = _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors,
-                                max_overlap_distance)
+                                max_overlap_distance, max_normal_angle=self.max_normal_angle)
 
         hooks = None
         if debug_dirpath:
@@ -329,6 +369,8 @@ class SimpleICP:
             hooks = (before, after)
         R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, min_planarity, distance_weights, max_iterations, min_change, hooks)
         rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
+        # (read before the final transform of the movable slot, which empties the cache of estimated normals)
+        angle_info = ctx.normal_angle_info() if hasattr(ctx, "normal_angle_info") else {}
 
         self._log_result(H, rbp)
 
@@ -340,6 +382,7 @@ class SimpleICP:
             pc2.write_xyz(Path(debug_dirpath).joinpath(f"iteration{it:03d}_postoptim_pcmov.xyz"))
 
         self.last_run_info = {"iterations": it + 1, "stats": stats, "seconds": time.time() - t_start, **getattr(self, "_job", {})}
+        self.last_run_info.update(angle_info)
         if sharded:
             # how the shards' winners met: "records_allgather" / "key_allreduces" (cloud shards) / "query_slices", and how often
             xi = ctx.exchange_info()

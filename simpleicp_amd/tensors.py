@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from . import _lib, backend, dist
-from .icp import SimpleICP, SimpleICPException, _iterate, _rbp_and_residuals, _select_and_setup_device
+from .icp import SimpleICP, SimpleICPException, _cos_of_max_angle, _iterate, _rbp_and_residuals, _select_and_setup_device
 from .rbp import H_from_params
 
 _log = logging.getLogger(__name__)
@@ -36,7 +36,7 @@ def _is_device_tensor(c) -> bool:
     return type(c).__module__.startswith("torch") and bool(getattr(c, "is_cuda", False))
 
 
-def _checked_kwargs(run_kwargs, who):
+def _checked_kwargs(run_kwargs, who, max_normal_angle=None):
     """run()'s keyword arguments with run()'s defaults, refused as run() / run_batch refuse them."""
     from .batch import _RUN_DEFAULTS
     unknown = set(run_kwargs) - set(_RUN_DEFAULTS)
@@ -47,6 +47,8 @@ def _checked_kwargs(run_kwargs, who):
     if kw["debug_dirpath"]:
         raise SimpleICPException(f"{who} writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
     SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
+    _cos_of_max_angle(max_normal_angle)
+    kw["max_normal_angle"] = max_normal_angle
     return kw
 
 
@@ -90,7 +92,7 @@ def prepare(ctx, X_fix, X_mov, kw, info):
     _upload(ctx, _lib.FIX, X_fix)
     _upload(ctx, _lib.MOV, X_mov)
     scratch = _select_and_setup_device(ctx, X_fix.shape[0], H, kw["correspondences"], kw["neighbors"],
-                                       kw["max_overlap_distance"], alloc, info=info)
+                                       kw["max_overlap_distance"], alloc, info=info, max_normal_angle=kw.get("max_normal_angle"))
     return obs, ow, H, scratch
 
 
@@ -102,14 +104,15 @@ def transformed(ctx, X_mov, H):
     return out
 
 
-def run_tensors(X_fix, X_mov, **run_kwargs):
+def run_tensors(X_fix, X_mov, max_normal_angle=None, **run_kwargs):
     """Registers X_mov to X_fix -- (n, 3) float32 / float64 torch tensors on the GPU of the library's context, any strides -- with
     ``run()``'s keyword arguments.  Returns a BatchResult (path "device") that unpacks as ``(H, X_mov_transformed, rbp,
     residuals)``: H, rbp and residuals are run()'s host values, X_mov_transformed a new device tensor; it also carries
-    ``iterations``, ``n_kept``, ``res_mean`` and ``res_std``.  Raises what run() raises, with the same messages."""
+    ``iterations``, ``n_kept``, ``res_mean`` and ``res_std``.  Raises what run() raises, with the same messages.
+    ``max_normal_angle`` (degrees, None = off): SimpleICP's attribute of that name; the movable normals are estimated on the device."""
     from .batch import BatchResult
     t_start = time.time()
-    kw = _checked_kwargs(run_kwargs, "run_tensors")
+    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle)
     if dist.is_distributed():
         raise SimpleICPException("run_tensors does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     device = backend.default_device()
