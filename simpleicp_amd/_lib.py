@@ -51,6 +51,10 @@ NORMALS_EXPORTS = ["sicp_normals_version", "sicp_cloud_set_normals", "sicp_norma
                    "sicp_normal_angle_info", "sicp_normal_cache_read"]
 NORMALS_VERSION = 1
 
+# include/simpleicp_hip_voxel.h: at most one point per voxel, a companion ABI with a version of its own as well
+VOXEL_EXPORTS = ["sicp_voxel_version", "sicp_voxel_select", "sicp_voxel_select_masked"]
+VOXEL_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -182,6 +186,11 @@ def load():
         L.sicp_normal_cache_read.argtypes = [vp, vp, vp]
         for name in NORMALS_EXPORTS:
             getattr(L, name).restype = cint
+    if all(hasattr(L, name) for name in VOXEL_EXPORTS):
+        L.sicp_voxel_select.argtypes = [vp, cint, vp, i64, dbl, vp, vp, C.POINTER(i64)]
+        L.sicp_voxel_select_masked.argtypes = [vp, cint, vp, i64, dbl, vp, vp, C.POINTER(i64)]
+        for name in VOXEL_EXPORTS:
+            getattr(L, name).restype = cint
     _lib = L
     return L
 
@@ -246,6 +255,19 @@ def normals_version():
     v = L.sicp_normals_version()
     if v != NORMALS_VERSION:
         raise BackendError(f"{LIB_PATH} implements normals version {v}, this binding needs {NORMALS_VERSION}")
+    return v
+
+
+def voxel_version():
+    """SICP_VOXEL_VERSION of the loaded library; BackendError when it has no voxel entry points."""
+    L = load()
+    missing = [name for name in VOXEL_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise BackendError(f"{LIB_PATH} has no voxel entry points ({', '.join(missing)}): it predates "
+                           "include/simpleicp_hip_voxel.h; rebuild with `python -m simpleicp_amd.build`")
+    v = L.sicp_voxel_version()
+    if v != VOXEL_VERSION:
+        raise BackendError(f"{LIB_PATH} implements voxel version {v}, this binding needs {VOXEL_VERSION}")
     return v
 
 
@@ -536,6 +558,34 @@ class Context:
         nv, have = np.empty((n, 3), np.float32), np.empty(n, np.uint8)
         self._chk(self._L.sicp_normal_cache_read(self._h, _ptr(nv), _ptr(have)))
         return nv, have.astype(bool)
+
+    # -- at most one point per voxel (contract (V)) --
+    def voxel_select(self, slot, voxel_size, origin=None, rows=None, keep_ptr=None):
+        """sicp_voxel_select: among the rows `rows` of the slot (None = all its points) the lowest-index point of every voxel of
+        the lattice (cell voxel_size, origin None = zeros) is kept.  Returns the bool verdicts, one per candidate; with keep_ptr (a
+        device address of that many bytes) they are left there and the number kept is returned instead."""
+        voxel_version()
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        m = self.size(slot) if r is None else len(r)
+        o = None if origin is None else _f64(origin).reshape(3)
+        kept = C.c_int64()
+        if keep_ptr is not None:
+            self._chk(self._L.sicp_voxel_select(self._h, slot, _ptr(r), m, float(voxel_size), _ptr(o), C.c_void_p(int(keep_ptr)),
+                                                C.byref(kept)))
+            return kept.value
+        out = np.empty(max(m, 1), dtype=np.uint8)
+        self._chk(self._L.sicp_voxel_select(self._h, slot, _ptr(r), m, float(voxel_size), _ptr(o), _ptr(out), C.byref(kept)))
+        return out[:m].view(np.bool_)
+
+    def voxel_select_masked(self, slot, mask_ptr, n, voxel_size, origin=None, keep_ptr=None):
+        """sicp_voxel_select_masked: the candidates are the points whose byte of the device mask (n bytes at mask_ptr) is non-zero;
+        the verdicts go to keep_ptr (device memory, n bytes; None = over the mask).  Returns how many were kept."""
+        voxel_version()
+        o = None if origin is None else _f64(origin).reshape(3)
+        kept = C.c_int64()
+        self._chk(self._L.sicp_voxel_select_masked(self._h, slot, C.c_void_p(int(mask_ptr)), int(n), float(voxel_size), _ptr(o),
+                                                   C.c_void_p(int(mask_ptr if keep_ptr is None else keep_ptr)), C.byref(kept)))
+        return kept.value
 
     # -- nearest neighbours --
     def knn(self, slot, q_xyz, k=1, H=None, max_dist=np.inf):

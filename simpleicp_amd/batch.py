@@ -20,7 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib, backend, dist
-from .icp import SimpleICP, SimpleICPException, _cos_of_max_angle, _rbp_and_residuals, _select_and_setup
+from .icp import SimpleICP, SimpleICPException, _cos_of_max_angle, _rbp_and_residuals, _select_and_setup, _voxel_of
 from .pointcloud import PointCloud, PointCloudException
 from .rbp import H_from_params
 
@@ -32,7 +32,7 @@ last_run_info: dict = {}
 # run()'s keyword arguments and their defaults, read off its signature (a default changed there is the batch's as well)
 _RUN_DEFAULTS = {name: prm.default for name, prm in inspect.signature(SimpleICP.run).parameters.items() if name != "self"}
 # keywords of run_batch / run_tensors / the per_pair dicts that are not run()'s (SimpleICP carries them as attributes)
-_EXTRA_DEFAULTS = {"max_normal_angle": None}
+_EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None}
 
 
 class BatchResult(tuple):
@@ -69,12 +69,14 @@ def _quiet(*_args, **_kw):
 
 
 def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] = None, return_transformed: bool = True,
-              max_normal_angle: Optional[float] = None, **run_kwargs) -> list:
+              max_normal_angle: Optional[float] = None, voxel_size: Optional[float] = None, voxel_origin=None, **run_kwargs) -> list:
     """Registers every ``(fixed, movable)`` pair of ``pairs`` (PointClouds or (n, 3) arrays, or two CUDA torch tensors as for
     ``run_tensors``) with ``run()``'s keyword arguments ``run_kwargs``, overridden per pair by ``per_pair[i]`` (a dict or None).
     Returns one BatchResult per pair, in order.  ``return_transformed=False``: no X_mov_transformed (None), no download of the
     movable clouds (no egress of a device pair's).  ``max_normal_angle`` (degrees; also a key of the per_pair dicts): SimpleICP's
-    attribute of that name -- a pair that has it runs its loop on its own (``path`` "fallback"), the others stay batched."""
+    attribute of that name -- a pair that has it runs its loop on its own (``path`` "fallback"), the others stay batched.
+    ``voxel_size`` / ``voxel_origin`` (keys of the per_pair dicts too): SimpleICP's attributes of those names; only the pair's
+    preparation changes, its loop stays batched."""
     t0 = time.time()
     pairs = list(pairs)
     if per_pair is not None and len(per_pair) != len(pairs):
@@ -83,7 +85,7 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
         raise SimpleICPException("run_batch does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     kws = []
     for i in range(len(pairs)):
-        kw = dict(_RUN_DEFAULTS, max_normal_angle=max_normal_angle)
+        kw = dict(_RUN_DEFAULTS, max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin)
         for src in (run_kwargs, (per_pair[i] or {}) if per_pair is not None else {}):
             unknown = set(src) - set(_RUN_DEFAULTS) - set(_EXTRA_DEFAULTS)
             if unknown:
@@ -92,6 +94,7 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
         if kw["debug_dirpath"]:
             raise SimpleICPException("run_batch writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
         _cos_of_max_angle(kw["max_normal_angle"])
+        kw["voxel"] = _voxel_of(kw["voxel_size"], kw["voxel_origin"])
         kws.append(kw)
     if not pairs:
         return []
@@ -139,7 +142,7 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
             pc2._upload(ctx, _lib.MOV, background=True)
             ctx.upload_wait(_lib.FIX)
             _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel0, H, kw["correspondences"], kw["neighbors"],
-                              kw["max_overlap_distance"], info=_quiet, max_normal_angle=kw["max_normal_angle"])
+                              kw["max_overlap_distance"], info=_quiet, max_normal_angle=kw["max_normal_angle"], voxel=kw["voxel"])
         except (SimpleICPException, PointCloudException, _lib.BackendError) as e:
             # what run() would raise for this pair (no overlap, a non-finite coordinate, ...): the pair's error, the others go on
             out[i] = BatchResult(error=e)

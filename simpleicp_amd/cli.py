@@ -29,6 +29,9 @@ def build_parser():
                     help="Minimal change of mean and standard deviation of distances (in percent) needed to proceed "
                          "to next iteration")
     ap.add_argument("-x", "--max_iterations", type=int, default=100, help="Maximum number of iterations")
+    ap.add_argument("--voxel-size", type=float, default=None,
+                    help="keep at most one point of the fixed cloud per voxel of this size before the correspondences are selected "
+                         "(off by default)")
     ap.add_argument("--output", default="", help="write the transformed movable cloud to this .xyz file")
     ap.add_argument("--quiet", action="store_true", help="print only the 4x4 matrix")
     return ap
@@ -42,6 +45,7 @@ def main(argv=None) -> int:
         X_fix = io.read_xyz(args.fixed)
         X_mov = io.read_xyz(args.movable)
         icp = SimpleICP(verbose=not args.quiet)
+        icp.voxel_size = args.voxel_size
         icp.add_point_clouds(PointCloud(X_fix, columns=["x", "y", "z"]), PointCloud(X_mov, columns=["x", "y", "z"]))
         H, X_out, _, _ = icp.run(
             correspondences=args.correspondences, neighbors=args.neighbors, min_planarity=args.min_planarity,

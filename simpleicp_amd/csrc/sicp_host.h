@@ -294,6 +294,13 @@ struct sicp_ctx {
     // positions (the kept rows themselves are stream-ordered memory of the call)
     DevBuf<uint32_t> sel_blk;
     DevBuf<int64_t> sel_pos;
+    // voxel selection (sicp_voxel.hip): the hash table of {key, winner} word pairs, every candidate's slot in it, the rows and the
+    // verdicts of a call on their way in and out, [0] the kept count [1] the error bits; grown, never shrunk, gone with the ctx
+    DevBuf<unsigned long long> vx_tab;
+    DevBuf<uint32_t> vx_slot;
+    DevBuf<int64_t> vx_rows;
+    DevBuf<uint8_t> vx_keep;
+    DevBuf<unsigned> vx_cnt;
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

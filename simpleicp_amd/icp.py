@@ -26,7 +26,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib, backend, dist
-from .pointcloud import _ALL, PointCloud
+from .pointcloud import _ALL, PointCloud, voxel_arguments
 from .rbp import H_from_params, RigidBodyParameters
 
 _log = logging.getLogger(__name__)
@@ -77,6 +77,18 @@ def _cos_of_max_angle(max_normal_angle):
     return math.cos(math.radians(float(max_normal_angle)))
 
 
+def _voxel_of(voxel_size, voxel_origin=None):
+    """voxel_size (None = no voxel selection) and voxel_origin -> (cell, origin) of contract (V), checked once."""
+    if voxel_size is None:
+        return None
+    return voxel_arguments(voxel_size, voxel_origin, SimpleICPException)
+
+
+def _need_voxel_backend(ctx, voxel):
+    if voxel is not None and not hasattr(ctx, "voxel_select"):
+        raise _lib.BackendError("this backend has no voxel selection")
+
+
 def _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle):
     """The context's normal-angle setting for the run about to start -- set on every run, off included, so that a pooled context
     never inherits it --, with pc2's own nx, ny, nz columns when it has them (of the selected subset when pc2 is partially selected;
@@ -94,11 +106,12 @@ def _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle):
 
 
 def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors, max_overlap_distance,
-                      info=None, max_normal_angle=None):
-    """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass under
-    the initial H, select_n_points, normals (or pc1's nx, ny, nz, planarity columns), the movable cloud's selected subset and its
-    planarity column, sicp_icp_setup.  Returns the selected rows of pc1.  info: where the progress lines go (the log)."""
+                      info=None, max_normal_angle=None, voxel=None):
+    """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass
+    under the initial H, one point per voxel (voxel: (cell, origin) or None), select_n_points, normals (or pc1's nx, ny, nz,
+    planarity columns), the movable cloud's selected subset and its planarity column, sicp_icp_setup.  Returns the selected rows of pc1.  info: where the progress lines go (the log)."""
     info = info or _log.info
+    _need_voxel_backend(ctx, voxel)
     if np.isfinite(max_overlap_distance):
         info("Consider partial overlap of point clouds ...")
         if sel is _ALL or len(sel):
@@ -107,6 +120,18 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
             sel = pc1._keep_selected(sel, near)
         if not len(sel) > 0:
             raise _no_overlap(max_overlap_distance)
+
+    if voxel is not None:
+        # after the overlap pre-pass, so that a voxel's representative always lies inside the overlap
+        info("Keep one point per voxel ...")
+        if sel is _ALL or len(sel):
+            keep = ctx.voxel_select(_lib.FIX, voxel[0], voxel[1], None if sel is _ALL else sel)
+            sel = pc1._keep_selected(sel, keep)
+        if not len(sel) > 0:
+            # (reachable only with no selected point to start from; the exception an empty overlap raises, with words of its own)
+            if np.isfinite(max_overlap_distance):
+                raise _no_overlap(max_overlap_distance)
+            raise SimpleICPException("The fixed point cloud has no selected points left for the voxel selection.")
 
     info("Select points for correspondences in fixed point cloud ...")
     sel = pc1.select_n_points(correspondences, _cur=sel)
@@ -129,17 +154,26 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
     return sel
 
 
-def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None, max_normal_angle=None):
+def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None, max_normal_angle=None,
+                             voxel=None):
     """_select_and_setup for clouds uploaded from device memory (run_tensors, run_batch's device pairs; every point selected, no
     normals or planarity columns): the same steps with every array they hand on left in device memory -- the overlap verdicts, the
     kept rows and the picks of select_n_points (sicp_select_n_device), the normals.  alloc(shape, kind) returns a device buffer
     (kind "u8" / "i64" / "f32") and its address; the buffers are returned and must outlive the run's sicp_icp_setup."""
     info = info or _log.info
+    _need_voxel_backend(ctx, voxel)
     mask = mask_p = None
     if np.isfinite(max_overlap_distance):
         info("Consider partial overlap of point clouds ...")
         mask, mask_p = alloc((n_fix,), "u8")
         ctx.select_in_range_into(_lib.FIX, _lib.MOV, H, float(max_overlap_distance), mask_p)
+    if voxel is not None:
+        info("Keep one point per voxel ...")
+        if mask is None:
+            mask, mask_p = alloc((n_fix,), "u8")
+            ctx.voxel_select(_lib.FIX, voxel[0], voxel[1], keep_ptr=mask_p)
+        else:
+            ctx.voxel_select_masked(_lib.FIX, mask_p, n_fix, voxel[0], voxel[1])      # (the verdicts replace the mask)
     sel, sel_p = alloc((max(int(correspondences), 1),), "i64")
     Q = ctx.select_n_device(mask_p, n_fix, int(correspondences), sel_p)
     if mask is not None and Q == 0:
@@ -240,6 +274,11 @@ class SimpleICP:
     # are pc2's nx / ny / nz columns when it has them, else they are estimated on the device with run()'s ``neighbors`` among the
     # points of the movable cloud that take part in the search (its selected subset when it is partially selected).
     max_normal_angle: Optional[float] = None
+    # Voxel selection: a cell size, None = off.  After the overlap pre-pass and before select_n_points the
+    # fixed cloud's selection is thinned to the lowest-index point of every voxel of the lattice (cell voxel_size, origin
+    # voxel_origin), so the correspondences are even in space, not in index.  Attributes for the same reason as max_normal_angle.
+    voxel_size: Optional[float] = None
+    voxel_origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
 
     def __init__(self, verbose: bool = True) -> None:
         self.pc1: Optional[PointCloud] = None
@@ -270,12 +309,16 @@ class SimpleICP:
         Returns (H, X_mov_transformed, rbp, distance_residuals)."""
         self._check_arguments(distance_weights, rbp_observed_values, rbp_observation_weights)
         _cos_of_max_angle(self.max_normal_angle)
+        voxel = _voxel_of(self.voxel_size, self.voxel_origin)
         t_start = time.time()
         pc1, pc2 = self.pc1, self.pc2
         ctx = backend.get_context()
         ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
         import os
         sharded = dist.is_distributed() or (os.environ.get("SICP_FORCE_EXCHANGE") == "1" and dist.is_initialized())
+        if sharded and voxel is not None:
+            raise SimpleICPException("voxel_size does not run in a torch.distributed job: thin the clouds with one process first")
+        _need_voxel_backend(ctx, voxel)
 
         if debug_dirpath:
             _log.info(f'Write debug files to directory "{debug_dirpath}"')
@@ -334,7 +377,7 @@ class SimpleICP:
         try:
             return self._run_uploaded(ctx, sharded, msel, n_search, upload_movable, sel0, t_start, obs, ow, H,
                                       correspondences, neighbors, min_planarity, max_overlap_distance, min_change,
-                                      max_iterations, distance_weights, debug_dirpath)
+                                      max_iterations, distance_weights, debug_dirpath, voxel)
         except BaseException:
             # ANY way out of a sharded run that is not its normal end (a backend error, a host-side exception between two
             # collectives, KeyboardInterrupt, MemoryError) may leave this rank out of step with its peers: never revive the
@@ -348,13 +391,13 @@ class SimpleICP:
             dist.detach(ctx)
 
     def _run_uploaded(self, ctx, sharded, msel, n_search, upload_movable, sel, t_start, obs, ow, H, correspondences, neighbors,
-                      min_planarity, max_overlap_distance, min_change, max_iterations, distance_weights, debug_dirpath):
+                      min_planarity, max_overlap_distance, min_change, max_iterations, distance_weights, debug_dirpath, voxel=None):
         pc1, pc2 = self.pc1, self.pc2
         if debug_dirpath:
             X_fix, X_mov = pc1.X, pc2.X
 
         sel = _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors,
-                                max_overlap_distance, max_normal_angle=self.max_normal_angle)
+                                max_overlap_distance, max_normal_angle=self.max_normal_angle, voxel=voxel)
 
         hooks = None
         if debug_dirpath:

@@ -34,6 +34,26 @@ class PointCloudException(Exception):
     """Raised when the PointCloud class is misused (pointcloud.py:229)."""
 
 
+def voxel_arguments(voxel_size, origin=None, exc=ValueError):
+    """(cell size as a float, origin as three floats) of contract (V), DESIGN.md section 13: the cell finite and > 0, the origin
+    (None = zeros) three finite numbers; anything else raises ``exc`` before any device work."""
+    try:
+        c = float(voxel_size)
+        ok = not isinstance(voxel_size, (bool, str, bytes)) and np.isfinite(c) and c > 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise exc("voxel_size must be a finite number > 0.")
+    try:
+        o = tuple(float(v) for v in ((0.0, 0.0, 0.0) if origin is None else origin))
+        ok = len(o) == 3 and all(np.isfinite(v) for v in o)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise exc("voxel_origin must be three finite numbers.")
+    return c, o
+
+
 class PointCloud(pd.DataFrame):
     def __init__(self, *args, **kwargs) -> None:
         kwargs.pop("remapping", None)     # accepted and ignored, like the reference (pointcloud.py:25)
@@ -245,6 +265,19 @@ class PointCloud(pd.DataFrame):
         near = ctx.select_in_range(_lib.FIX, _lib.MOV, None if len(cur) == self._num_points else cur,
                                    max_range=float(max_range))
         self._set_idx_selected(cur[near])
+
+    def select_voxels(self, voxel_size: float, origin=(0.0, 0.0, 0.0), _ctx=None) -> None:
+        """Keeps, among the selected points, the lowest-index point of every voxel of the lattice with cell ``voxel_size`` and
+        ``origin`` (voxel of a point: ``np.floor((X - origin) / voxel_size)``; contract (V)) and deselects the
+        rest.  Not in the reference; composes with select_in_range and select_n_points the way those compose with each other."""
+        c, o = voxel_arguments(voxel_size, origin, PointCloudException)
+        ctx = _ctx or backend.get_context()
+        cur = self.idx_selected
+        if len(cur) == 0:
+            return
+        self._upload(ctx, _lib.FIX)
+        keep = ctx.voxel_select(_lib.FIX, c, o, None if len(cur) == self._num_points else cur)
+        self._set_idx_selected(cur[keep])
 
     # ---- attributes (pointcloud.py:173-203) ---------------------------------------------
     def estimate_normals(self, neighbors: int, _ctx=None, _uploaded=False, _sel=None) -> None:

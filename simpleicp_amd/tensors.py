@@ -23,7 +23,8 @@ import time
 import numpy as np
 
 from . import _lib, backend, dist
-from .icp import SimpleICP, SimpleICPException, _cos_of_max_angle, _iterate, _rbp_and_residuals, _select_and_setup_device
+from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _iterate, _rbp_and_residuals, _select_and_setup_device,
+                  _voxel_of)
 from .rbp import H_from_params
 
 _log = logging.getLogger(__name__)
@@ -36,7 +37,7 @@ def _is_device_tensor(c) -> bool:
     return type(c).__module__.startswith("torch") and bool(getattr(c, "is_cuda", False))
 
 
-def _checked_kwargs(run_kwargs, who, max_normal_angle=None):
+def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, voxel_origin=None):
     """run()'s keyword arguments with run()'s defaults, refused as run() / run_batch refuse them."""
     from .batch import _RUN_DEFAULTS
     unknown = set(run_kwargs) - set(_RUN_DEFAULTS)
@@ -49,6 +50,7 @@ def _checked_kwargs(run_kwargs, who, max_normal_angle=None):
     SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
     _cos_of_max_angle(max_normal_angle)
     kw["max_normal_angle"] = max_normal_angle
+    kw["voxel"] = _voxel_of(voxel_size, voxel_origin)
     return kw
 
 
@@ -92,7 +94,8 @@ def prepare(ctx, X_fix, X_mov, kw, info):
     _upload(ctx, _lib.FIX, X_fix)
     _upload(ctx, _lib.MOV, X_mov)
     scratch = _select_and_setup_device(ctx, X_fix.shape[0], H, kw["correspondences"], kw["neighbors"],
-                                       kw["max_overlap_distance"], alloc, info=info, max_normal_angle=kw.get("max_normal_angle"))
+                                       kw["max_overlap_distance"], alloc, info=info, max_normal_angle=kw.get("max_normal_angle"),
+                                       voxel=kw.get("voxel"))
     return obs, ow, H, scratch
 
 
@@ -104,15 +107,17 @@ def transformed(ctx, X_mov, H):
     return out
 
 
-def run_tensors(X_fix, X_mov, max_normal_angle=None, **run_kwargs):
+def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_origin=None, **run_kwargs):
     """Registers X_mov to X_fix -- (n, 3) float32 / float64 torch tensors on the GPU of the library's context, any strides -- with
     ``run()``'s keyword arguments.  Returns a BatchResult (path "device") that unpacks as ``(H, X_mov_transformed, rbp,
     residuals)``: H, rbp and residuals are run()'s host values, X_mov_transformed a new device tensor; it also carries
     ``iterations``, ``n_kept``, ``res_mean`` and ``res_std``.  Raises what run() raises, with the same messages.
-    ``max_normal_angle`` (degrees, None = off): SimpleICP's attribute of that name; the movable normals are estimated on the device."""
+    ``max_normal_angle`` (degrees, None = off): SimpleICP's attribute of that name; the movable normals are estimated on the device.
+    ``voxel_size`` / ``voxel_origin`` (None = off / zeros): SimpleICP's attributes of those names, applied to the fixed cloud on the
+    device; the movable cloud is thinned by the caller (``X_mov[voxel_keep(X_mov, c)]``)."""
     from .batch import BatchResult
     t_start = time.time()
-    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle)
+    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle, voxel_size, voxel_origin)
     if dist.is_distributed():
         raise SimpleICPException("run_tensors does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     device = backend.default_device()
@@ -132,3 +137,40 @@ def run_tensors(X_fix, X_mov, max_normal_angle=None, **run_kwargs):
     return BatchResult(H, X_new, rbp, residuals, iterations=it + 1, n_kept=int(R.n_kept) if R is not None else 0,
                        res_mean=R.res_mean if R is not None else np.nan, res_std=R.res_std if R is not None else np.nan,
                        path="device")
+
+
+def voxel_keep(X, voxel_size, origin=None, mask=None):
+    """The keep verdicts of contract (V) for X -- an (n, 3) float32 / float64 torch tensor on the GPU of the
+    library's context, any strides; float32 is widened exactly before the formula -- as a torch.bool tensor (n,): True for the
+    lowest-index point of every voxel of the lattice (cell ``voxel_size``, ``origin`` None = zeros).  ``mask`` (a bool / uint8 (n,)
+    tensor on the same device): only the points it marks are candidates, every other point is False.  Ingest and stream rule are
+    run_tensors'.  ``X[voxel_keep(X, c)]`` is the thinned cloud; the library's fixed slot holds X afterwards."""
+    import torch
+    voxel = _voxel_of(voxel_size, origin)
+    if dist.is_distributed():
+        raise SimpleICPException("voxel_keep does not run in a torch.distributed job: thin the clouds with one process first")
+    device = backend.default_device()
+    _check_cloud("X", X, device)
+    n = X.shape[0]
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
+            raise TypeError("mask must be a bool or uint8 torch.Tensor of shape (n,)")
+        if mask.device != X.device:
+            raise ValueError(f"mask is on {mask.device}, X on {X.device}")
+    if n == 0:
+        return torch.zeros(0, dtype=torch.bool, device=X.device)
+    ctx = backend.get_context()
+    ctx._corr_owner = None
+    dist.detach(ctx)
+    # everything torch has to do for this call -- the contiguous copy of a strided mask -- is queued on its current stream BEFORE
+    # the library's stream is made to wait for that stream: the library never reads a buffer torch is still writing
+    m8 = None if mask is None else mask.contiguous().view(torch.uint8)
+    keep = torch.empty(n, dtype=torch.uint8, device=X.device)
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=X.device).wait_stream(torch.cuda.current_stream(X.device))
+    _upload(ctx, _lib.FIX, X)
+    if m8 is None:
+        ctx.voxel_select(_lib.FIX, voxel[0], voxel[1], keep_ptr=keep.data_ptr())
+    else:
+        ctx.voxel_select_masked(_lib.FIX, m8.data_ptr(), n, voxel[0], voxel[1], keep_ptr=keep.data_ptr())
+    del m8                                               # (the call returned complete: nothing reads it any more)
+    return keep.view(torch.bool)
