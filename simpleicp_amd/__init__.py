@@ -20,7 +20,9 @@ from .icp import SimpleICP, SimpleICPException                   # noqa: E402
 from .batch import BatchResult, run_batch                        # noqa: E402
 from .tensors import run_tensors, voxel_keep                     # noqa: E402  (imports torch on its first call only)
 
+from .evaluation import Evaluation, evaluate_registration        # noqa: E402
 from . import io                                                 # noqa: E402,F401
 
 __all__ = ["SimpleICP", "SimpleICPException", "PointCloud", "PointCloudException",
-           "RigidBodyParameters", "Parameter", "run_batch", "BatchResult", "run_tensors", "voxel_keep"]
+           "RigidBodyParameters", "Parameter", "run_batch", "BatchResult", "run_tensors", "voxel_keep", "Evaluation",
+           "evaluate_registration"]

@@ -55,6 +55,10 @@ NORMALS_VERSION = 1
 VOXEL_EXPORTS = ["sicp_voxel_version", "sicp_voxel_select", "sicp_voxel_select_masked"]
 VOXEL_VERSION = 1
 
+# include/simpleicp_hip_eval.h: fitness, inlier RMSE and the information sums of a registration, the same kind of companion
+EVAL_EXPORTS = ["sicp_eval_version", "sicp_evaluate"]
+EVAL_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -62,6 +66,12 @@ class BackendError(RuntimeError):
     def __init__(self, message, code=None):
         super().__init__(message)
         self.code = code
+
+
+class EvalRecord(C.Structure):
+    """struct sicp_eval (contract (E)): 96 bytes."""
+    _fields_ = [("n_queries", C.c_int64), ("n_inliers", C.c_int64), ("sum_d2", C.c_double), ("sum_p", C.c_double * 3),
+                ("sum_pp", C.c_double * 6)]
 
 
 class IterParams(C.Structure):
@@ -191,6 +201,10 @@ def load():
         L.sicp_voxel_select_masked.argtypes = [vp, cint, vp, i64, dbl, vp, vp, C.POINTER(i64)]
         for name in VOXEL_EXPORTS:
             getattr(L, name).restype = cint
+    if all(hasattr(L, name) for name in EVAL_EXPORTS):
+        L.sicp_evaluate.argtypes = [vp, cint, cint, vp, i64, vp, dbl, C.POINTER(EvalRecord)]
+        for name in EVAL_EXPORTS:
+            getattr(L, name).restype = cint
     _lib = L
     return L
 
@@ -268,6 +282,19 @@ def voxel_version():
     v = L.sicp_voxel_version()
     if v != VOXEL_VERSION:
         raise BackendError(f"{LIB_PATH} implements voxel version {v}, this binding needs {VOXEL_VERSION}")
+    return v
+
+
+def eval_version():
+    """SICP_EVAL_VERSION of the loaded library; BackendError when it has no evaluation entry points."""
+    L = load()
+    missing = [name for name in EVAL_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise BackendError(f"{LIB_PATH} has no evaluation entry points ({', '.join(missing)}): it predates "
+                           "include/simpleicp_hip_eval.h; rebuild with `python -m simpleicp_amd.build`")
+    v = L.sicp_eval_version()
+    if v != EVAL_VERSION:
+        raise BackendError(f"{LIB_PATH} implements evaluation version {v}, this binding needs {EVAL_VERSION}")
     return v
 
 
@@ -586,6 +613,22 @@ class Context:
         self._chk(self._L.sicp_voxel_select_masked(self._h, slot, C.c_void_p(int(mask_ptr)), int(n), float(voxel_size), _ptr(o),
                                                    C.c_void_p(int(mask_ptr if keep_ptr is None else keep_ptr)), C.byref(kept)))
         return kept.value
+
+    # -- how good a registration is (contract (E)) --
+    def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):
+        """sicp_evaluate: every point of query_slot (rows: these rows of it, in this order -- an int64 array, or a device tensor)
+        searches its nearest point among H * search_slot (H None = identity) within max_distance (strict).  Returns the
+        EvalRecord: the number of queries and of inliers, and the ten tree sums of contract (E) over the inliers."""
+        eval_version()
+        if rows is not None and not hasattr(rows, "data_ptr"):
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+        Q = 0 if rows is None else int(rows.shape[0])
+        if rows is not None and Q == 0:
+            raise ValueError("rows must not be empty (None: every point of the slot)")
+        Hm = None if H is None else _f64(H).reshape(16)
+        rec = EvalRecord()
+        self._chk(self._L.sicp_evaluate(self._h, query_slot, search_slot, _ptr(rows), Q, _ptr(Hm), float(max_distance), C.byref(rec)))
+        return rec
 
     # -- nearest neighbours --
     def knn(self, slot, q_xyz, k=1, H=None, max_dist=np.inf):

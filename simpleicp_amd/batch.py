@@ -19,8 +19,9 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib, backend, dist
-from .icp import SimpleICP, SimpleICPException, _cos_of_max_angle, _rbp_and_residuals, _select_and_setup, _voxel_of
+from . import _lib, backend, dist, evaluation
+from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _evaluate_distance_of, _rbp_and_residuals, _select_and_setup,
+                  _voxel_of)
 from .pointcloud import PointCloud, PointCloudException
 from .rbp import H_from_params
 
@@ -32,19 +33,21 @@ last_run_info: dict = {}
 # run()'s keyword arguments and their defaults, read off its signature (a default changed there is the batch's as well)
 _RUN_DEFAULTS = {name: prm.default for name, prm in inspect.signature(SimpleICP.run).parameters.items() if name != "self"}
 # keywords of run_batch / run_tensors / the per_pair dicts that are not run()'s (SimpleICP carries them as attributes)
-_EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None}
+_EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None, "evaluate_distance": None}
 
 
 class BatchResult(tuple):
     """One pair's outcome: unpacks like ``run()``'s ``(H, X_mov_transformed, rbp, residuals)``; besides ``iterations``,
     ``n_kept`` / ``res_mean`` / ``res_std`` of the last iteration, and ``error`` (None, or the exception ``run()`` would
-    have raised for this pair -- then the four values are None)."""
+    have raised for this pair -- then the four values are None), and ``evaluation`` (the Evaluation of the pair under its final H
+    when evaluate_distance was set for it; None when it was not, and for a pair with ``error``)."""
 
     def __new__(cls, H=None, X_mov_transformed=None, rbp=None, residuals=None, iterations=0, n_kept=0, res_mean=np.nan,
-                res_std=np.nan, error=None, path=None):
+                res_std=np.nan, error=None, path=None, evaluation=None):
         self = super().__new__(cls, (H, X_mov_transformed, rbp, residuals))
         self.iterations, self.n_kept, self.res_mean, self.res_std = iterations, n_kept, res_mean, res_std
         self.error = error
+        self.evaluation = evaluation
         self.path = path          # "batched" / "fallback" (the pair ran through sicp_icp_run: Q > 2048 and the like) / "device" (run_tensors)
         return self
 
@@ -69,14 +72,17 @@ def _quiet(*_args, **_kw):
 
 
 def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] = None, return_transformed: bool = True,
-              max_normal_angle: Optional[float] = None, voxel_size: Optional[float] = None, voxel_origin=None, **run_kwargs) -> list:
+              max_normal_angle: Optional[float] = None, voxel_size: Optional[float] = None, voxel_origin=None,
+              evaluate_distance: Optional[float] = None, **run_kwargs) -> list:
     """Registers every ``(fixed, movable)`` pair of ``pairs`` (PointClouds or (n, 3) arrays, or two CUDA torch tensors as for
     ``run_tensors``) with ``run()``'s keyword arguments ``run_kwargs``, overridden per pair by ``per_pair[i]`` (a dict or None).
     Returns one BatchResult per pair, in order.  ``return_transformed=False``: no X_mov_transformed (None), no download of the
     movable clouds (no egress of a device pair's).  ``max_normal_angle`` (degrees; also a key of the per_pair dicts): SimpleICP's
     attribute of that name -- a pair that has it runs its loop on its own (``path`` "fallback"), the others stay batched.
     ``voxel_size`` / ``voxel_origin`` (keys of the per_pair dicts too): SimpleICP's attributes of those names; only the pair's
-    preparation changes, its loop stays batched."""
+    preparation changes, its loop stays batched.  ``evaluate_distance`` (a key of the per_pair dicts too; None = off): SimpleICP's
+    attribute of that name -- the pair stays batched, after the batched loop it is scored under its final H on its pool context
+    (``BatchResult.evaluation``)."""
     t0 = time.time()
     pairs = list(pairs)
     if per_pair is not None and len(per_pair) != len(pairs):
@@ -85,7 +91,8 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
         raise SimpleICPException("run_batch does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     kws = []
     for i in range(len(pairs)):
-        kw = dict(_RUN_DEFAULTS, max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin)
+        kw = dict(_RUN_DEFAULTS, max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin,
+                  evaluate_distance=evaluate_distance)
         for src in (run_kwargs, (per_pair[i] or {}) if per_pair is not None else {}):
             unknown = set(src) - set(_RUN_DEFAULTS) - set(_EXTRA_DEFAULTS)
             if unknown:
@@ -95,6 +102,7 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
             raise SimpleICPException("run_batch writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
         _cos_of_max_angle(kw["max_normal_angle"])
         kw["voxel"] = _voxel_of(kw["voxel_size"], kw["voxel_origin"])
+        kw["evaluate"] = _evaluate_distance_of(kw["evaluate_distance"])
         kws.append(kw)
     if not pairs:
         return []
@@ -108,17 +116,19 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
 
     ctxs = backend.get_batch_contexts(len(pairs))
     out = [None] * len(pairs)
-    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, device pair: (X_mov, its scratch) or None)
+    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, device pair: (X_mov, its scratch) or None, evaluate_distance or None)
     members = []
     for i, ((fix, mov), kw) in enumerate(zip(pairs, kws)):
         ctx = ctxs[i]
         ctx._corr_owner = None
         try:
+            if kw["evaluate"] is not None:
+                evaluation.need_backend(ctx)
             if on_device[i]:
                 SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
                 obs, ow, _, scratch = tensors.prepare(ctx, fix, mov, kw, _quiet)
                 members.append((ctx, _member_kwargs(obs, ow, kw)))
-                prepared.append((i, ctx, None, None, obs, ow, (mov, scratch)))
+                prepared.append((i, ctx, None, None, obs, ow, (mov, scratch), kw["evaluate"]))
                 continue
             pc1, pc2 = _cloud(fix), _cloud(mov)
             SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
@@ -148,13 +158,13 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
             out[i] = BatchResult(error=e)
             continue
         members.append((ctx, _member_kwargs(obs, ow, kw)))
-        prepared.append((i, ctx, pc2, msel, obs, ow, None))
+        prepared.append((i, ctx, pc2, msel, obs, ow, None, kw["evaluate"]))
 
     t1 = time.time()
     runs, fallback = members[0][0].icp_run_batch(members) if members else ([], 0)
     t2 = time.time()
-    for (i, ctx, pc2, msel, obs, ow, dev), r in zip(prepared, runs):
-        out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev)
+    for (i, ctx, pc2, msel, obs, ow, dev, eval_d), r in zip(prepared, runs):
+        out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev, eval_d)
     last_run_info.clear()
     last_run_info.update(pairs=len(pairs), fallback=fallback, prepare_s=t1 - t0, batch_s=t2 - t1, results_s=time.time() - t2)
     n_err = sum(1 for o in out if o.error is not None)
@@ -176,9 +186,9 @@ def _member_kwargs(obs, ow, kw) -> dict:
                 max_iterations=kw["max_iterations"], min_change=kw["min_change"])
 
 
-def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None) -> BatchResult:
+def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None, eval_d=None) -> BatchResult:
     """SimpleICP.run's epilogue for one member: what it returns, or the exception it raises.  dev: (X_mov, scratch) of a device pair
-    (run_tensors' epilogue: the transformed cloud is a new device tensor)."""
+    (run_tensors' epilogue: the transformed cloud is a new device tensor).  eval_d: the pair's evaluate_distance (None: off)."""
     path = "fallback" if r.path == _lib.BATCH_PATH_FALLBACK else "batched"
     whole = r.results
     if r.status != _lib.OK:
@@ -196,6 +206,8 @@ def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None) -> BatchRe
         x = np.array(R.x[:])
         H = np.array(R.H[:]).reshape(4, 4)
     rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
+    # (before the movable slot is uploaded again / transformed below: both clouds are as the loop left them)
+    ev = evaluation.after_run(ctx, H, eval_d) if eval_d is not None else None
     X_new = None
     if return_transformed and dev is not None:
         from . import tensors
@@ -206,4 +218,4 @@ def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None) -> BatchRe
         ctx.transform(_lib.MOV, H)
         X_new, _ = ctx.download_both(_lib.MOV)     # (through the lean contexts' shared pinned ring, like run()'s download)
     return BatchResult(H, X_new, rbp, residuals, iterations=len(whole), n_kept=int(R.n_kept) if R else 0,
-                       res_mean=R.res_mean if R else np.nan, res_std=R.res_std if R else np.nan, path=path)
+                       res_mean=R.res_mean if R else np.nan, res_std=R.res_std if R else np.nan, path=path, evaluation=ev)

@@ -32,6 +32,9 @@ def build_parser():
     ap.add_argument("--voxel-size", type=float, default=None,
                     help="keep at most one point of the fixed cloud per voxel of this size before the correspondences are selected "
                          "(off by default)")
+    ap.add_argument("--evaluate-distance", type=float, default=None,
+                    help="after the run, score every point of the fixed cloud under the result within this distance and print "
+                         "fitness and inlier RMSE (off by default)")
     ap.add_argument("--output", default="", help="write the transformed movable cloud to this .xyz file")
     ap.add_argument("--quiet", action="store_true", help="print only the 4x4 matrix")
     return ap
@@ -46,6 +49,7 @@ def main(argv=None) -> int:
         X_mov = io.read_xyz(args.movable)
         icp = SimpleICP(verbose=not args.quiet)
         icp.voxel_size = args.voxel_size
+        icp.evaluate_distance = args.evaluate_distance
         icp.add_point_clouds(PointCloud(X_fix, columns=["x", "y", "z"]), PointCloud(X_mov, columns=["x", "y", "z"]))
         H, X_out, _, _ = icp.run(
             correspondences=args.correspondences, neighbors=args.neighbors, min_planarity=args.min_planarity,
@@ -57,6 +61,9 @@ def main(argv=None) -> int:
     if args.quiet:
         for row in H:
             print(" ".join(f"{v:.9f}" for v in row))
+    if icp.evaluation is not None:
+        ev = icp.evaluation
+        print(f"fitness {ev.fitness:.9f} inlier_rmse {ev.inlier_rmse:.9f} inliers {ev.n_inliers} of {ev.n_queries}")
     if args.output:
         io.write_xyz(args.output, X_out)
     return 0

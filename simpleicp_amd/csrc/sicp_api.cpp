@@ -224,6 +224,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->batch_tab.release(); c->batch_map.release();
     c->sel_blk.release(); c->sel_pos.release();
     c->vx_tab.release(); c->vx_slot.release(); c->vx_rows.release(); c->vx_keep.release(); c->vx_cnt.release();
+    c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

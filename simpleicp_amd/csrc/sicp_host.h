@@ -301,6 +301,10 @@ struct sicp_ctx {
     DevBuf<int64_t> vx_rows;
     DevBuf<uint8_t> vx_keep;
     DevBuf<unsigned> vx_cnt;
+    // sicp_evaluate (sicp_eval.hip): the workgroups' partial sums and the levels above them, their inlier counts, the record on its
+    // way out; grown, never shrunk, gone with the ctx
+    DevBuf<double> ev_part, ev_out;
+    DevBuf<long long> ev_cnt;
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

@@ -229,6 +229,11 @@ hipError_t reject_by_select_one_launch(hipStream_t s, const double *dist, const 
 void launch_aos_to_soa(hipStream_t s, const double *aos, long n, long npad, double *x, double *y, double *z);
 void launch_found_mask(hipStream_t s, const int64_t *idx, long Q, uint8_t *out);
 void launch_pad_fill(hipStream_t s, double *x, double *y, double *z, long n, long npad);
+// sicp_eval.hip: the ten tree sums and the inlier count of contract (E) over 1-NN results; scratch holds 10 * (nb + ceil(nb / 256))
+// doubles (at least) and counts nb entries, nb = eval_partials_count(Q); out12 receives the 96 bytes of a sicp_eval record
+long eval_partials_count(long Q);
+void launch_eval(hipStream_t s, const int64_t *idx, const double *d2, const double *qx, const double *qy, const double *qz, long Q,
+                 double *scratch, long long *counts, double *out12);
 void launch_pack_chunks(hipStream_t s, const double *x, const double *y, const double *z, long n, long CH, double *out);
 void launch_soa_to_aos(hipStream_t s, const double *x, const double *y, const double *z, long n, double *aos);
 void launch_transform(hipStream_t s, double *x, double *y, double *z, long n, const Xf &H);

@@ -1,6 +1,7 @@
 // sicp_search.cpp -- the drivers of the 1-NN and k-NN searches (which kernel, on which structure, with which bound) and the exports that are
-// searches: sicp_knn, sicp_select_in_range, sicp_estimate_normals.  Split from sicp_api.cpp (round 5).
+// searches: sicp_knn, sicp_select_in_range, sicp_evaluate, sicp_estimate_normals.  Split from sicp_api.cpp (round 5).
 #include "sicp_host.h"
+#include "../../include/simpleicp_hip_eval.h"
 
 namespace sicph {
 
@@ -393,6 +394,58 @@ SICP_EXPORT int sicp_select_in_range(sicp_ctx *c, int query_slot, int search_slo
     if (rc == SICP_OK) rc = body();
     (void)hipStreamSynchronize(c->stream);
     sel.release(); mask.release();
+    return rc;
+}
+
+SICP_EXPORT int sicp_eval_version(void) { return SICP_EVAL_VERSION; }
+
+// sicp_select_in_range's search; instead of one byte per query the ten sums and the count of contract (E) leave the device
+SICP_EXPORT int sicp_evaluate(sicp_ctx *c, int query_slot, int search_slot, const int64_t *sel_idx, int64_t Q, const double *H,
+                              double max_distance, sicp_eval *out)
+{
+    if (!c) return fail(SICP_ERR_INVALID, "null ctx");
+    if (!out) return fail(SICP_ERR_INVALID, "out is null");
+    if (query_slot == search_slot) return fail(SICP_ERR_INVALID, "query_slot and search_slot must differ");
+    if (std::isnan(max_distance) || max_distance < 0) return fail(SICP_ERR_INVALID, "max_distance must be >= 0");
+    CHK(check_slot(c, query_slot, true));
+    CHK(check_slot(c, search_slot, true));
+    Cloud &qc = c->cloud[query_slot];
+    if (qc.idx_base != 0) return fail(SICP_ERR_INVALID, "the query cloud (query_slot) must not be a shard");
+    if (c->collective())
+        return fail(SICP_ERR_INVALID, "sicp_evaluate is not supported with an exchange (the sums of one rank's queries are not the job's)");
+    if (!sel_idx) Q = qc.n;
+    if (Q <= 0) return fail(SICP_ERR_INVALID, "Q must be > 0");
+    HIPCHK(hipSetDevice(c->device));
+    if (sel_idx) CHK(check_rows(sel_idx, Q, qc.n, "sel_idx"));
+    static_assert(sizeof(sicp_eval) == 12 * sizeof(double), "the record is twelve 8-byte words");
+    const long qpad = round_up(Q, QPAD);
+    const long nb = eval_partials_count(Q);
+    CHK(c->kq.reserve((size_t)3 * qpad));
+    CHK(c->k_d2.reserve((size_t)Q));
+    CHK(c->k_idx.reserve((size_t)Q));
+    // (scratch kept with the ctx, as sicp_estimate_normals keeps its own: at small Q a hipMalloc costs more than both kernels)
+    if (sel_idx) CHK(c->k_sel.reserve((size_t)Q));
+    CHK(c->ev_part.reserve((size_t)10 * (nb + (nb + 255) / 256)));
+    CHK(c->ev_cnt.reserve((size_t)nb));
+    CHK(c->ev_out.reserve(12));
+    auto body = [&]() -> int {
+        if (sel_idx) HIPCHK(hipMemcpyAsync(c->k_sel.p, sel_idx, (size_t)Q * sizeof(int64_t), hipMemcpyDefault, c->stream));
+        launch_gather_queries(c->stream, qc.x(), qc.y(), qc.z(), sel_idx ? c->k_sel.p : nullptr, Q, qpad, c->kq.p, c->kq.p + qpad,
+                              c->kq.p + 2 * qpad);
+        Xf X;
+        if (H) H16_to_Xf(H, &X);
+        CHK(knn1_device(c, search_slot, c->kq.p, Q, qpad, H ? &X : nullptr, max_distance, nullptr, c->k_d2.p, c->k_idx.p, nullptr));
+        launch_eval(c->stream, c->k_idx.p, c->k_d2.p, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, Q, c->ev_part.p, c->ev_cnt.p,
+                    c->ev_out.p);
+        HIPCHK(hipGetLastError());
+        double *h_rec = c->h_small + 192;                 // pinned: the record's twelve words
+        HIPCHK(hipMemcpyAsync(h_rec, c->ev_out.p, 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        CHK(sync(c));
+        std::memcpy(out, h_rec, sizeof *out);
+        return SICP_OK;
+    };
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
     return rc;
 }
 

@@ -25,7 +25,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _lib, backend, dist
+from . import _lib, backend, dist, evaluation
 from .pointcloud import _ALL, PointCloud, voxel_arguments
 from .rbp import H_from_params, RigidBodyParameters
 
@@ -82,6 +82,13 @@ def _voxel_of(voxel_size, voxel_origin=None):
     if voxel_size is None:
         return None
     return voxel_arguments(voxel_size, voxel_origin, SimpleICPException)
+
+
+def _evaluate_distance_of(evaluate_distance):
+    """evaluate_distance (None = no evaluation) -> the search bound of contract (E), checked once."""
+    if evaluate_distance is None:
+        return None
+    return evaluation._distance_of(evaluate_distance, SimpleICPException, "evaluate_distance")
 
 
 def _need_voxel_backend(ctx, voxel):
@@ -279,11 +286,19 @@ class SimpleICP:
     # voxel_origin), so the correspondences are even in space, not in index.  Attributes for the same reason as max_normal_angle.
     voxel_size: Optional[float] = None
     voxel_origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    # Evaluation: a distance, None = off.  After the last iteration, while both clouds are still resident,
+    # EVERY point of the fixed cloud (selected or not) searches its nearest neighbour among the movable cloud under the final H,
+    # strictly within this distance; the Evaluation (fitness, inlier RMSE, information matrix) goes to ``self.evaluation`` and
+    # ``last_run_info["evaluation"]``.  A movable cloud that was uploaded as its selected subset (a partial `selected` mask) is
+    # searched as that subset.  H, rbp, the residuals and the transformed cloud are the same bits either way.  An attribute for
+    # the same reason as max_normal_angle.
+    evaluate_distance: Optional[float] = None
 
     def __init__(self, verbose: bool = True) -> None:
         self.pc1: Optional[PointCloud] = None
         self.pc2: Optional[PointCloud] = None
         self.last_run_info: dict = {}
+        self.evaluation: Optional[evaluation.Evaluation] = None      # of the last run that had evaluate_distance set
         if verbose:
             _enable_verbose_logging()
 
@@ -310,6 +325,7 @@ class SimpleICP:
         self._check_arguments(distance_weights, rbp_observed_values, rbp_observation_weights)
         _cos_of_max_angle(self.max_normal_angle)
         voxel = _voxel_of(self.voxel_size, self.voxel_origin)
+        eval_d = _evaluate_distance_of(self.evaluate_distance)
         t_start = time.time()
         pc1, pc2 = self.pc1, self.pc2
         ctx = backend.get_context()
@@ -319,6 +335,11 @@ class SimpleICP:
         if sharded and voxel is not None:
             raise SimpleICPException("voxel_size does not run in a torch.distributed job: thin the clouds with one process first")
         _need_voxel_backend(ctx, voxel)
+        if eval_d is not None:
+            if sharded:
+                raise SimpleICPException("evaluate_distance does not run in a torch.distributed job: score the result with one process")
+            evaluation.need_backend(ctx)
+        self.evaluation = None
 
         if debug_dirpath:
             _log.info(f'Write debug files to directory "{debug_dirpath}"')
@@ -377,7 +398,7 @@ class SimpleICP:
         try:
             return self._run_uploaded(ctx, sharded, msel, n_search, upload_movable, sel0, t_start, obs, ow, H,
                                       correspondences, neighbors, min_planarity, max_overlap_distance, min_change,
-                                      max_iterations, distance_weights, debug_dirpath, voxel)
+                                      max_iterations, distance_weights, debug_dirpath, voxel, eval_d)
         except BaseException:
             # ANY way out of a sharded run that is not its normal end (a backend error, a host-side exception between two
             # collectives, KeyboardInterrupt, MemoryError) may leave this rank out of step with its peers: never revive the
@@ -391,7 +412,8 @@ class SimpleICP:
             dist.detach(ctx)
 
     def _run_uploaded(self, ctx, sharded, msel, n_search, upload_movable, sel, t_start, obs, ow, H, correspondences, neighbors,
-                      min_planarity, max_overlap_distance, min_change, max_iterations, distance_weights, debug_dirpath, voxel=None):
+                      min_planarity, max_overlap_distance, min_change, max_iterations, distance_weights, debug_dirpath, voxel=None,
+                      eval_d=None):
         pc1, pc2 = self.pc1, self.pc2
         if debug_dirpath:
             X_fix, X_mov = pc1.X, pc2.X
@@ -416,6 +438,9 @@ class SimpleICP:
         angle_info = ctx.normal_angle_info() if hasattr(ctx, "normal_angle_info") else {}
 
         self._log_result(H, rbp)
+        if eval_d is not None:
+            # (before the movable slot is uploaded again / transformed below: both clouds are as the loop left them)
+            self.evaluation = evaluation.after_run(ctx, H, eval_d, _log.info)
 
         # final transformation of the caller's movable cloud (simpleicp.py:316): all of its points
         if sharded or msel is not None:
@@ -426,6 +451,8 @@ class SimpleICP:
 
         self.last_run_info = {"iterations": it + 1, "stats": stats, "seconds": time.time() - t_start, **getattr(self, "_job", {})}
         self.last_run_info.update(angle_info)
+        if eval_d is not None:
+            self.last_run_info["evaluation"] = self.evaluation
         if sharded:
             # how the shards' winners met: "records_allgather" / "key_allreduces" (cloud shards) / "query_slices", and how often
             xi = ctx.exchange_info()

@@ -23,8 +23,9 @@ import time
 import numpy as np
 
 from . import _lib, backend, dist
-from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _iterate, _rbp_and_residuals, _select_and_setup_device,
-                  _voxel_of)
+from . import evaluation
+from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _evaluate_distance_of, _iterate, _rbp_and_residuals,
+                  _select_and_setup_device, _voxel_of)
 from .rbp import H_from_params
 
 _log = logging.getLogger(__name__)
@@ -37,7 +38,7 @@ def _is_device_tensor(c) -> bool:
     return type(c).__module__.startswith("torch") and bool(getattr(c, "is_cuda", False))
 
 
-def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, voxel_origin=None):
+def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None):
     """run()'s keyword arguments with run()'s defaults, refused as run() / run_batch refuse them."""
     from .batch import _RUN_DEFAULTS
     unknown = set(run_kwargs) - set(_RUN_DEFAULTS)
@@ -51,6 +52,7 @@ def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, vox
     _cos_of_max_angle(max_normal_angle)
     kw["max_normal_angle"] = max_normal_angle
     kw["voxel"] = _voxel_of(voxel_size, voxel_origin)
+    kw["evaluate"] = _evaluate_distance_of(evaluate_distance)
     return kw
 
 
@@ -107,17 +109,19 @@ def transformed(ctx, X_mov, H):
     return out
 
 
-def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_origin=None, **run_kwargs):
+def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None, **run_kwargs):
     """Registers X_mov to X_fix -- (n, 3) float32 / float64 torch tensors on the GPU of the library's context, any strides -- with
     ``run()``'s keyword arguments.  Returns a BatchResult (path "device") that unpacks as ``(H, X_mov_transformed, rbp,
     residuals)``: H, rbp and residuals are run()'s host values, X_mov_transformed a new device tensor; it also carries
     ``iterations``, ``n_kept``, ``res_mean`` and ``res_std``.  Raises what run() raises, with the same messages.
     ``max_normal_angle`` (degrees, None = off): SimpleICP's attribute of that name; the movable normals are estimated on the device.
     ``voxel_size`` / ``voxel_origin`` (None = off / zeros): SimpleICP's attributes of those names, applied to the fixed cloud on the
-    device; the movable cloud is thinned by the caller (``X_mov[voxel_keep(X_mov, c)]``)."""
+    device; the movable cloud is thinned by the caller (``X_mov[voxel_keep(X_mov, c)]``).
+    ``evaluate_distance`` (None = off): SimpleICP's attribute of that name -- every fixed point is scored under the final H on the
+    device, the Evaluation is the result's ``evaluation``."""
     from .batch import BatchResult
     t_start = time.time()
-    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle, voxel_size, voxel_origin)
+    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle, voxel_size, voxel_origin, evaluate_distance)
     if dist.is_distributed():
         raise SimpleICPException("run_tensors does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     device = backend.default_device()
@@ -126,17 +130,20 @@ def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_orig
     ctx = backend.get_context()
     ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
     dist.detach(ctx)
+    if kw["evaluate"] is not None:
+        evaluation.need_backend(ctx)
     obs, ow, H, scratch = prepare(ctx, X_fix, X_mov, kw, _log.info)
     R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, kw["min_planarity"], kw["distance_weights"], kw["max_iterations"],
                                            kw["min_change"])
     rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
     SimpleICP._log_result(H, rbp)
+    ev = evaluation.after_run(ctx, H, kw["evaluate"], _log.info) if kw["evaluate"] is not None else None
     X_new = transformed(ctx, X_mov, H)
     del scratch
     _log.info(f"Finished in {time.time() - t_start:.3f} seconds!")
     return BatchResult(H, X_new, rbp, residuals, iterations=it + 1, n_kept=int(R.n_kept) if R is not None else 0,
                        res_mean=R.res_mean if R is not None else np.nan, res_std=R.res_std if R is not None else np.nan,
-                       path="device")
+                       path="device", evaluation=ev)
 
 
 def voxel_keep(X, voxel_size, origin=None, mask=None):
