@@ -59,6 +59,12 @@ VOXEL_VERSION = 1
 EVAL_EXPORTS = ["sicp_eval_version", "sicp_evaluate"]
 EVAL_VERSION = 1
 
+# include/simpleicp_hip_outlier.h: the statistical and the radius outlier filter, the same kind of companion
+OUTLIER_EXPORTS = ["sicp_outlier_version", "sicp_outlier_statistical", "sicp_outlier_radius", "sicp_outlier_radius_cells"]
+OUTLIER_VERSION = 1
+OUTLIER_MAX_K = 128
+OUTLIER_MAX_BOX_CELLS = 4096
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -72,6 +78,16 @@ class EvalRecord(C.Structure):
     """struct sicp_eval (contract (E)): 96 bytes."""
     _fields_ = [("n_queries", C.c_int64), ("n_inliers", C.c_int64), ("sum_d2", C.c_double), ("sum_p", C.c_double * 3),
                 ("sum_pp", C.c_double * 6)]
+
+
+class OutlierStats(C.Structure):
+    """struct sicp_outlier_stats (contract (O)): 40 bytes."""
+    _fields_ = [("n_candidates", C.c_int64), ("n_kept", C.c_int64), ("mean", C.c_double), ("std", C.c_double),
+                ("threshold", C.c_double)]
+
+    def as_dict(self):
+        return dict(n_candidates=int(self.n_candidates), n_kept=int(self.n_kept), mean=float(self.mean), std=float(self.std),
+                    threshold=float(self.threshold))
 
 
 class IterParams(C.Structure):
@@ -205,6 +221,12 @@ def load():
         L.sicp_evaluate.argtypes = [vp, cint, cint, vp, i64, vp, dbl, C.POINTER(EvalRecord)]
         for name in EVAL_EXPORTS:
             getattr(L, name).restype = cint
+    if all(hasattr(L, name) for name in OUTLIER_EXPORTS):
+        L.sicp_outlier_statistical.argtypes = [vp, cint, vp, i64, vp, cint, dbl, vp, vp, C.POINTER(OutlierStats)]
+        L.sicp_outlier_radius.argtypes = [vp, cint, vp, i64, vp, dbl, i64, vp, vp, C.POINTER(i64)]
+        L.sicp_outlier_radius_cells.argtypes = [vp, cint, dbl, vp]
+        for name in OUTLIER_EXPORTS:
+            getattr(L, name).restype = cint
     _lib = L
     return L
 
@@ -295,6 +317,19 @@ def eval_version():
     v = L.sicp_eval_version()
     if v != EVAL_VERSION:
         raise BackendError(f"{LIB_PATH} implements evaluation version {v}, this binding needs {EVAL_VERSION}")
+    return v
+
+
+def outlier_version():
+    """SICP_OUTLIER_VERSION of the loaded library; BackendError when it has no outlier entry points."""
+    L = load()
+    missing = [name for name in OUTLIER_EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise BackendError(f"{LIB_PATH} has no outlier entry points ({', '.join(missing)}): it predates "
+                           "include/simpleicp_hip_outlier.h; rebuild with `python -m simpleicp_amd.build`")
+    v = L.sicp_outlier_version()
+    if v != OUTLIER_VERSION:
+        raise BackendError(f"{LIB_PATH} implements outlier version {v}, this binding needs {OUTLIER_VERSION}")
     return v
 
 
@@ -613,6 +648,61 @@ class Context:
         self._chk(self._L.sicp_voxel_select_masked(self._h, slot, C.c_void_p(int(mask_ptr)), int(n), float(voxel_size), _ptr(o),
                                                    C.c_void_p(int(mask_ptr if keep_ptr is None else keep_ptr)), C.byref(kept)))
         return kept.value
+
+    # -- outlier removal (contract (O)) --
+    def _outlier_shape(self, slot, rows, mask_ptr):
+        """(rows as int64 or None, entries of every output) of an outlier call."""
+        if rows is not None and mask_ptr is not None:
+            raise ValueError("rows and mask_ptr are mutually exclusive")
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        if r is not None and len(r) == 0:
+            raise ValueError("rows must not be empty (None: every point of the slot)")
+        return r, (self.size(slot) if r is None else len(r))
+
+    def outlier_statistical(self, slot, k, std_ratio, rows=None, mask_ptr=None, keep_ptr=None, mean_ptr=None):
+        """sicp_outlier_statistical: the candidates -- the rows `rows` of the slot, the points whose byte of the device mask at
+        mask_ptr is non-zero, or (both None) every point -- whose mean distance to their k nearest points of the slot is at most
+        mean + std_ratio * std over the candidates are kept.  Returns (bool verdicts, (N,) float64 mean distances, OutlierStats),
+        N = len(rows) or the slot's size; with keep_ptr (device memory, N bytes; may be mask_ptr) the verdicts are left there, the
+        distances at mean_ptr if given (N doubles), and the OutlierStats alone is returned."""
+        outlier_version()
+        r, N = self._outlier_shape(slot, rows, mask_ptr)
+        st = OutlierStats()
+        mp = None if mask_ptr is None else C.c_void_p(int(mask_ptr))
+        if keep_ptr is not None:
+            self._chk(self._L.sicp_outlier_statistical(self._h, slot, _ptr(r), N, mp, int(k), float(std_ratio), C.c_void_p(int(keep_ptr)),
+                                                       None if mean_ptr is None else C.c_void_p(int(mean_ptr)), C.byref(st)))
+            return st
+        keep, d = np.empty(max(N, 1), np.uint8), np.empty(max(N, 1), np.float64)
+        self._chk(self._L.sicp_outlier_statistical(self._h, slot, _ptr(r), N, mp, int(k), float(std_ratio), _ptr(keep), _ptr(d),
+                                                   C.byref(st)))
+        return keep[:N].view(np.bool_), d[:N], st
+
+    def outlier_radius(self, slot, radius, min_points, rows=None, mask_ptr=None, keep_ptr=None, count_ptr=None):
+        """sicp_outlier_radius: the candidates (as outlier_statistical takes them) with more than min_points points of the slot,
+        themselves included, closer than radius (strict) are kept.  Returns (bool verdicts, (N,) uint32 counts capped at
+        min_points + 1, number kept); with keep_ptr (device memory, N bytes) the verdicts are left there, the counts at count_ptr
+        if given, and the number kept alone is returned."""
+        outlier_version()
+        r, N = self._outlier_shape(slot, rows, mask_ptr)
+        kept = C.c_int64()
+        mp = None if mask_ptr is None else C.c_void_p(int(mask_ptr))
+        if keep_ptr is not None:
+            self._chk(self._L.sicp_outlier_radius(self._h, slot, _ptr(r), N, mp, float(radius), int(min_points), C.c_void_p(int(keep_ptr)),
+                                                  None if count_ptr is None else C.c_void_p(int(count_ptr)), C.byref(kept)))
+            return kept.value
+        keep, cnt = np.empty(max(N, 1), np.uint8), np.empty(max(N, 1), np.uint32)
+        self._chk(self._L.sicp_outlier_radius(self._h, slot, _ptr(r), N, mp, float(radius), int(min_points), _ptr(keep), _ptr(cnt),
+                                              C.byref(kept)))
+        return keep[:N].view(np.bool_), cnt[:N], kept.value
+
+    def outlier_radius_cells(self, slot, radius):
+        """sicp_outlier_radius_cells: (cells along x, y, z, their product) of the box a ball of this radius spans on the slot's
+        grid; outlier_radius is accepted iff the product is at most OUTLIER_MAX_BOX_CELLS."""
+        outlier_version()
+        out = np.zeros(4, np.int64)
+        self._chk(self._L.sicp_outlier_radius_cells(self._h, slot, float(radius), _ptr(out)))
+        return tuple(int(v) for v in out)
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):

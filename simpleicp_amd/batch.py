@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib, backend, dist, evaluation
 from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _evaluate_distance_of, _rbp_and_residuals, _select_and_setup,
-                  _voxel_of)
+                  _check_outlier_size, _outlier_of, _voxel_of)
 from .pointcloud import PointCloud, PointCloudException
 from .rbp import H_from_params
 
@@ -33,21 +33,24 @@ last_run_info: dict = {}
 # run()'s keyword arguments and their defaults, read off its signature (a default changed there is the batch's as well)
 _RUN_DEFAULTS = {name: prm.default for name, prm in inspect.signature(SimpleICP.run).parameters.items() if name != "self"}
 # keywords of run_batch / run_tensors / the per_pair dicts that are not run()'s (SimpleICP carries them as attributes)
-_EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None, "evaluate_distance": None}
+_EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None, "evaluate_distance": None,
+                   "outlier_neighbors": None, "outlier_std_ratio": 2.0}
 
 
 class BatchResult(tuple):
     """One pair's outcome: unpacks like ``run()``'s ``(H, X_mov_transformed, rbp, residuals)``; besides ``iterations``,
     ``n_kept`` / ``res_mean`` / ``res_std`` of the last iteration, and ``error`` (None, or the exception ``run()`` would
     have raised for this pair -- then the four values are None), and ``evaluation`` (the Evaluation of the pair under its final H
-    when evaluate_distance was set for it; None when it was not, and for a pair with ``error``)."""
+    when evaluate_distance was set for it; None when it was not, and for a pair with ``error``), and ``outlier`` (the statistics
+    of the pair's outlier removal -- n_candidates, n_kept, mean, std, threshold -- when outlier_neighbors was set for it, else None)."""
 
     def __new__(cls, H=None, X_mov_transformed=None, rbp=None, residuals=None, iterations=0, n_kept=0, res_mean=np.nan,
-                res_std=np.nan, error=None, path=None, evaluation=None):
+                res_std=np.nan, error=None, path=None, evaluation=None, outlier=None):
         self = super().__new__(cls, (H, X_mov_transformed, rbp, residuals))
         self.iterations, self.n_kept, self.res_mean, self.res_std = iterations, n_kept, res_mean, res_std
         self.error = error
         self.evaluation = evaluation
+        self.outlier = outlier
         self.path = path          # "batched" / "fallback" (the pair ran through sicp_icp_run: Q > 2048 and the like) / "device" (run_tensors)
         return self
 
@@ -73,7 +76,8 @@ def _quiet(*_args, **_kw):
 
 def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] = None, return_transformed: bool = True,
               max_normal_angle: Optional[float] = None, voxel_size: Optional[float] = None, voxel_origin=None,
-              evaluate_distance: Optional[float] = None, **run_kwargs) -> list:
+              evaluate_distance: Optional[float] = None, outlier_neighbors: Optional[int] = None, outlier_std_ratio: float = 2.0,
+              **run_kwargs) -> list:
     """Registers every ``(fixed, movable)`` pair of ``pairs`` (PointClouds or (n, 3) arrays, or two CUDA torch tensors as for
     ``run_tensors``) with ``run()``'s keyword arguments ``run_kwargs``, overridden per pair by ``per_pair[i]`` (a dict or None).
     Returns one BatchResult per pair, in order.  ``return_transformed=False``: no X_mov_transformed (None), no download of the
@@ -82,7 +86,9 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
     ``voxel_size`` / ``voxel_origin`` (keys of the per_pair dicts too): SimpleICP's attributes of those names; only the pair's
     preparation changes, its loop stays batched.  ``evaluate_distance`` (a key of the per_pair dicts too; None = off): SimpleICP's
     attribute of that name -- the pair stays batched, after the batched loop it is scored under its final H on its pool context
-    (``BatchResult.evaluation``)."""
+    (``BatchResult.evaluation``).  ``outlier_neighbors`` / ``outlier_std_ratio`` (keys of the per_pair dicts too; None = off):
+    SimpleICP's attributes of those names; only the pair's preparation changes, its loop stays batched
+    (``BatchResult.outlier``)."""
     t0 = time.time()
     pairs = list(pairs)
     if per_pair is not None and len(per_pair) != len(pairs):
@@ -92,7 +98,7 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
     kws = []
     for i in range(len(pairs)):
         kw = dict(_RUN_DEFAULTS, max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin,
-                  evaluate_distance=evaluate_distance)
+                  evaluate_distance=evaluate_distance, outlier_neighbors=outlier_neighbors, outlier_std_ratio=outlier_std_ratio)
         for src in (run_kwargs, (per_pair[i] or {}) if per_pair is not None else {}):
             unknown = set(src) - set(_RUN_DEFAULTS) - set(_EXTRA_DEFAULTS)
             if unknown:
@@ -103,6 +109,8 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
         _cos_of_max_angle(kw["max_normal_angle"])
         kw["voxel"] = _voxel_of(kw["voxel_size"], kw["voxel_origin"])
         kw["evaluate"] = _evaluate_distance_of(kw["evaluate_distance"])
+        kw["outlier"] = _outlier_of(kw["outlier_neighbors"], kw["outlier_std_ratio"])
+        kw["outlier_stats"] = {}
         kws.append(kw)
     if not pairs:
         return []
@@ -116,7 +124,7 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
 
     ctxs = backend.get_batch_contexts(len(pairs))
     out = [None] * len(pairs)
-    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, device pair: (X_mov, its scratch) or None, evaluate_distance or None)
+    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, device pair: (X_mov, its scratch) or None, evaluate_distance or None, outlier statistics or None)
     members = []
     for i, ((fix, mov), kw) in enumerate(zip(pairs, kws)):
         ctx = ctxs[i]
@@ -126,11 +134,14 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
                 evaluation.need_backend(ctx)
             if on_device[i]:
                 SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
+                _check_outlier_size(kw["outlier"], fix.shape[0])
                 obs, ow, _, scratch = tensors.prepare(ctx, fix, mov, kw, _quiet)
                 members.append((ctx, _member_kwargs(obs, ow, kw)))
-                prepared.append((i, ctx, None, None, obs, ow, (mov, scratch), kw["evaluate"]))
+                prepared.append((i, ctx, None, None, obs, ow, (mov, scratch), kw["evaluate"],
+                                 kw["outlier_stats"] if kw["outlier"] is not None else None))
                 continue
             pc1, pc2 = _cloud(fix), _cloud(mov)
+            _check_outlier_size(kw["outlier"], pc1.num_points)
             SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
             obs = np.array(kw["rbp_observed_values"], dtype=float)
             obs[:3] = obs[:3] * np.pi / 180
@@ -152,19 +163,21 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
             pc2._upload(ctx, _lib.MOV, background=True)
             ctx.upload_wait(_lib.FIX)
             _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel0, H, kw["correspondences"], kw["neighbors"],
-                              kw["max_overlap_distance"], info=_quiet, max_normal_angle=kw["max_normal_angle"], voxel=kw["voxel"])
+                              kw["max_overlap_distance"], info=_quiet, max_normal_angle=kw["max_normal_angle"], voxel=kw["voxel"],
+                              outlier=kw["outlier"], outlier_stats=kw["outlier_stats"])
         except (SimpleICPException, PointCloudException, _lib.BackendError) as e:
             # what run() would raise for this pair (no overlap, a non-finite coordinate, ...): the pair's error, the others go on
             out[i] = BatchResult(error=e)
             continue
         members.append((ctx, _member_kwargs(obs, ow, kw)))
-        prepared.append((i, ctx, pc2, msel, obs, ow, None, kw["evaluate"]))
+        prepared.append((i, ctx, pc2, msel, obs, ow, None, kw["evaluate"], kw["outlier_stats"] if kw["outlier"] is not None else None))
 
     t1 = time.time()
     runs, fallback = members[0][0].icp_run_batch(members) if members else ([], 0)
     t2 = time.time()
-    for (i, ctx, pc2, msel, obs, ow, dev, eval_d), r in zip(prepared, runs):
+    for (i, ctx, pc2, msel, obs, ow, dev, eval_d, ostats), r in zip(prepared, runs):
         out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev, eval_d)
+        out[i].outlier = ostats
     last_run_info.clear()
     last_run_info.update(pairs=len(pairs), fallback=fallback, prepare_s=t1 - t0, batch_s=t2 - t1, results_s=time.time() - t2)
     n_err = sum(1 for o in out if o.error is not None)

@@ -32,6 +32,10 @@ def build_parser():
     ap.add_argument("--voxel-size", type=float, default=None,
                     help="keep at most one point of the fixed cloud per voxel of this size before the correspondences are selected "
                          "(off by default)")
+    ap.add_argument("--outlier-neighbors", type=int, default=None,
+                    help="drop points of the fixed cloud whose mean distance to this many nearest neighbours is above the cloud's "
+                         "mean + ratio * std before the correspondences are selected (off by default)")
+    ap.add_argument("--outlier-std-ratio", type=float, default=2.0, help="the ratio of --outlier-neighbors (default 2.0)")
     ap.add_argument("--evaluate-distance", type=float, default=None,
                     help="after the run, score every point of the fixed cloud under the result within this distance and print "
                          "fitness and inlier RMSE (off by default)")
@@ -50,6 +54,8 @@ def main(argv=None) -> int:
         icp = SimpleICP(verbose=not args.quiet)
         icp.voxel_size = args.voxel_size
         icp.evaluate_distance = args.evaluate_distance
+        icp.outlier_neighbors = args.outlier_neighbors
+        icp.outlier_std_ratio = args.outlier_std_ratio
         icp.add_point_clouds(PointCloud(X_fix, columns=["x", "y", "z"]), PointCloud(X_mov, columns=["x", "y", "z"]))
         H, X_out, _, _ = icp.run(
             correspondences=args.correspondences, neighbors=args.neighbors, min_planarity=args.min_planarity,

@@ -181,6 +181,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_COMM_TIMEOUT_S")) { const double v = std::atof(e); if (v > 0) c->xchg_timeout_s = 2.0 * v; }    // (a record wait with collectives in flight: twice the rendezvous deadline)
     if (const char *e = std::getenv("SICP_FSCAN")) c->fscan_variant = !std::strcmp(e, "inline") ? 1 : 0;
     if (const char *e = std::getenv("SICP_FSCAN_CAP")) c->fscan_cap = std::atol(e);
+    if (const char *e = std::getenv("SICP_OUTLIER_CHUNK")) c->outlier_chunk = std::atol(e);
     // SICP_SOLVE_TRACE: per-iteration traces on stderr -- any value: the tail's cycle counters; "host": the host's enqueue timings too;
     // "sel" / "eval": the fine splits of a -DSICP_SEL_FINE_TRACE / -DSICP_EVAL_FINE_TRACE build (build.build_variant)
     if (const char *e = std::getenv("SICP_SOLVE_TRACE")) {
@@ -225,6 +226,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->sel_blk.release(); c->sel_pos.release();
     c->vx_tab.release(); c->vx_slot.release(); c->vx_rows.release(); c->vx_keep.release(); c->vx_cnt.release();
     c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
+    c->ol_d.release(); c->ol_part.release(); c->ol_rows.release(); c->ol_keep.release(); c->ol_cnt.release(); c->ol_small.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

@@ -305,6 +305,14 @@ struct sicp_ctx {
     // way out; grown, never shrunk, gone with the ctx
     DevBuf<double> ev_part, ev_out;
     DevBuf<long long> ev_cnt;
+    // outlier filters (sicp_outlier.hip): d_i per position, the candidate rows, the staged verdicts and counts, the trees' partials,
+    // [0..2] mean / std / threshold [4] kept [5] candidates of a mask; grown, never shrunk, gone with the ctx
+    DevBuf<double> ol_d, ol_part;
+    DevBuf<int64_t> ol_rows;
+    DevBuf<uint8_t> ol_keep;
+    DevBuf<uint32_t> ol_cnt;
+    DevBuf<unsigned long long> ol_small;
+    long outlier_chunk = 0;        // SICP_OUTLIER_CHUNK: candidates per search of the outlier filters (0: chosen per call; what a chunk holds is (chunk, k) distances)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

@@ -1,0 +1,532 @@
+// sicp_outlier.hip -- outlier removal (include/simpleicp_hip_outlier.h; contract (O)).
+//
+// Statistical filter: the candidates go through the slot's k-NN search (knnk_device: the one-sweep kernel on the grid, in cell
+// order) a chunk at a time, k_ol_mean turns a chunk's ranked (chunk, k) squared distances into d_i at the candidate's POSITION;
+// two trees over all positions (k_ol_partials / k_ol_fold: contract (E)'s adjacent-pair tree of one term, cut at the wave, the
+// workgroup and the launch as sicp_eval.hip cuts its ten) give mean and std, k_ol_verdict writes the bytes and counts them.
+// Radius filter: k_ball_count walks the grid rows of a candidate's ball with OL_GS lanes, counts d2 < r^2 and leaves at
+// min_points + 1.  Integer atomics count; no floating-point atomic takes part.
+#include "sicp_host.h"
+#include "sicp_grid_dev.h"
+#include "../../include/simpleicp_hip_outlier.h"
+
+namespace sicp {
+namespace {
+
+constexpr int OL_BLOCK = 256;
+constexpr int OL_WAVES = OL_BLOCK / 64;
+constexpr int OL_TILES = 4;                        // tiles a workgroup of k_ol_partials takes (a power of two): 1024 positions a partial
+constexpr long OL_SPAN = (long)OL_BLOCK * OL_TILES;
+constexpr int OL_FOLD = 1024;                      // threads of k_ol_fold = nodes of one of its steps
+constexpr int OL_FOLD_WAVES = OL_FOLD / 64;
+constexpr int OL_GS = 16;                          // lanes per candidate of k_ball_count (k_grid_nn16's share of a wave; the group talks through ballots and ds_bpermute)
+constexpr int OL_MAX_BLOCKS = 4096;
+
+// ---- the tree of contract (E), one term ------------------------------------------------------------------------------------------
+// one level inside the wave: element e of this lane and its partner's are the halves (J each) of one pair; a pair whose upper half
+// starts at or beyond P is no addition of the contract
+template <int J>
+__device__ __forceinline__ double ol_level(double v, long e, long P)
+{
+    const bool add = (e & ~(long)(2 * J - 1)) + J < P;
+    const double o = lane_xor_f64<J>(v);
+    return add ? v + o : v;
+}
+__device__ __forceinline__ double ol_wave(double v, long e, long P)
+{
+    v = ol_level<1>(v, e, P);  v = ol_level<2>(v, e, P);   v = ol_level<4>(v, e, P);
+    v = ol_level<8>(v, e, P);  v = ol_level<16>(v, e, P);  v = ol_level<32>(v, e, P);
+    return v;
+}
+// the levels above the wave: N wave sums in LDS, node i covering the 64 elements from base + 64 i; thread 0 folds them in pair
+// order and returns the sum.  Called by all threads.
+template <int N>
+__device__ __forceinline__ double ol_nodes(const double *node, long base, long P)
+{
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) {
+        double a[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) a[i] = node[i];
+#pragma unroll
+        for (int s = 1; s < N; s *= 2)
+#pragma unroll
+            for (int i = 0; i < N; i += 2 * s)
+                a[i] = base + 64L * (i + s) < P ? a[i] + a[i + s] : a[i];
+        r = a[0];
+    }
+    __syncthreads();
+    return r;
+}
+
+// st: [0] mean [1] std [2] threshold.  SQ false: term = d (non-candidates hold +0.0 there); true: (d - mean)^2 of the candidates
+template <bool SQ>
+__global__ __launch_bounds__(OL_BLOCK) void k_ol_partials(const double *__restrict__ d, const uint8_t *__restrict__ mask, long n, long P,
+                                                          const double *__restrict__ st, double *__restrict__ part)
+{
+    __shared__ double node[OL_TILES * OL_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long base = (long)blockIdx.x * OL_SPAN;
+    const double mean = SQ ? st[0] : 0.0;
+#pragma unroll
+    for (int t = 0; t < OL_TILES; ++t) {
+        const long e = base + (long)t * OL_BLOCK + threadIdx.x;
+        double v = 0.0;
+        if (e < n) {
+            const double di = d[e];
+            if (SQ) {
+                const double c = di - mean;
+                v = (!mask || mask[e] != 0) ? c * c : 0.0;
+            } else {
+                v = di;
+            }
+        }
+        v = ol_wave(v, e, P);
+        if (lane == 0) node[t * OL_WAVES + wave] = v;
+    }
+    const double s = ol_nodes<OL_TILES * OL_WAVES>(node, base, P);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// One workgroup: the tree over the nb partials, 1024 nodes a step, level after level between the buffers a and b; then the
+// statistics.  SQ false: st[0] = sum / m; true: st[1] = sqrt(sum / (m - 1)) (m == 1: 0), st[2] = st[0] + ratio * st[1].
+template <bool SQ>
+__global__ __launch_bounds__(OL_FOLD) void k_ol_fold(double *a, double *b, long nb, double m, double ratio, double *__restrict__ st)
+{
+    __shared__ double node[OL_FOLD_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long P = 1;
+    while (P < nb) P *= 2;
+    long cnt = nb;
+    while (P > 1) {
+        const long tiles = (cnt + OL_FOLD - 1) / OL_FOLD;
+        for (long t = 0; t < tiles; ++t) {
+            const long e = t * OL_FOLD + threadIdx.x;
+            double v = e < cnt ? a[e] : 0.0;
+            v = ol_wave(v, e, P);
+            if (lane == 0) node[wave] = v;
+            const double s = ol_nodes<OL_FOLD_WAVES>(node, t * OL_FOLD, P);
+            if (threadIdx.x == 0) b[t] = s;
+        }
+        __syncthreads();
+        cnt = tiles;
+        P = P > OL_FOLD ? P / OL_FOLD : 1;
+        double *p = a; a = b; b = p;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double sum = a[0];
+        if (!SQ) {
+            st[0] = sum / m;
+        } else {
+            const double sd = m > 1.0 ? sqrt(sum / (m - 1.0)) : 0.0;
+            const double w = ratio * sd;
+            st[1] = sd;
+            st[2] = st[0] + w;
+        }
+    }
+}
+
+// d_i of the Q candidates of a chunk from their ranked squared distances: d[pos] = (sqrt(d2_0) + ... + sqrt(d2_(k-1))) / k
+__global__ __launch_bounds__(OL_BLOCK) void k_ol_mean(const double *__restrict__ d2, long Q, int k, const int64_t *__restrict__ pos,
+                                                      double *__restrict__ d)
+{
+    const long q = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    if (q >= Q) return;
+    const double *row = d2 + q * k;
+    double s = sqrt(row[0]);
+    for (int j = 1; j < k; ++j) s = s + sqrt(row[j]);
+    d[pos ? pos[q] : q] = s / (double)k;
+}
+
+// keep[e] = candidate and d[e] <= threshold; cnt[0] += the kept
+__global__ __launch_bounds__(OL_BLOCK) void k_ol_verdict(const double *__restrict__ d, const uint8_t *__restrict__ mask, long n,
+                                                         const double *__restrict__ st, uint8_t *__restrict__ keep,
+                                                         unsigned long long *__restrict__ cnt)
+{
+    const double thr = st[2];
+    const long stride = (long)gridDim.x * OL_BLOCK;
+    unsigned long long mine = 0;
+    for (long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x; e < n; e += stride) {
+        const bool k = (!mask || mask[e] != 0) && d[e] <= thr;
+        keep[e] = k ? 1 : 0;
+        mine += k ? 1ull : 0ull;
+    }
+    mine = wsum_u64(mine);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(cnt, mine);
+}
+
+// rows[0 .. *cnt) = the points whose mask byte is set (in no particular order: every result lands at the point's own position)
+__global__ __launch_bounds__(OL_BLOCK) void k_ol_compact(const uint8_t *__restrict__ mask, long n, int64_t *__restrict__ rows,
+                                                         unsigned long long *__restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const long stride = (long)gridDim.x * OL_BLOCK;
+    const long rounds = (n + stride - 1) / stride;             // (every lane of a wave takes every round: the ballot is wave-wide)
+    for (long r = 0; r < rounds; ++r) {
+        const long e = r * stride + (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+        const bool set = e < n && mask[e] != 0;
+        const unsigned long long b = __ballot(set);
+        if (b == 0ull) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(cnt, (unsigned long long)__popcll((long long)b));
+        base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32)) << 32) |
+               (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);      // (lane 0 is active: every lane is)
+        if (set) rows[base + (unsigned long long)__popcll((long long)(b & ((1ull << lane) - 1ull)))] = e;
+    }
+}
+
+// ---- the radius filter -----------------------------------------------------------------------------------------------------------
+// OL_GS lanes per candidate.  The ball's box of cells is walked row by row ((cy, cz) rows are contiguous in the cell order): the
+// lanes of a group fetch the record ranges of OL_GS rows at once, culled to the ball along x as k_grid_nn culls its own, then take
+// the records of one row after the other, two per lane and step.  A candidate leaves as soon as its count reaches cap.
+// pos: where candidate q's results go (null: q); order: the candidates in cell order (the grid is a multiple of 8 blocks then).
+__global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                         const double *__restrict__ qz, const uint32_t *__restrict__ order,
+                                                         const int64_t *__restrict__ pos, const uint32_t *__restrict__ cell_start,
+                                                         const double4 *__restrict__ rec, long Q, GridGeom G, double r, double r2,
+                                                         unsigned cap, uint8_t *__restrict__ keep, uint32_t *__restrict__ cnt_out,
+                                                         unsigned long long *__restrict__ kept_total, unsigned long long *__restrict__ work)
+{
+    constexpr int GPB = OL_BLOCK / OL_GS;
+    const int lane = threadIdx.x & 63, sub = lane & (OL_GS - 1), gbase = lane & ~(OL_GS - 1);
+    long blk = blockIdx.x;
+    if (order) {                                               // one contiguous eighth of the ordered candidates per XCD
+        const long per_xcd = gridDim.x >> 3;
+        blk = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    }
+    const long slot = blk * GPB + (threadIdx.x / OL_GS);
+    const bool active = slot < Q;
+    bool kept = false;
+    unsigned long long n_cand = 0, n_rows = 0;
+    if (active) {
+        const long q = order ? (long)order[slot] : slot;
+        const double ax = qx[q], ay = qy[q], az = qz[q];
+        const double c3[3] = {ax, ay, az};
+        // d2 < r2 implies |difference| < r along every axis up to the rounding of the difference itself: the ball that is culled with
+        // is wider by that, and by the rounding of c - rr
+        const double rr = r + (1e-9 * r + 1e-15 * (fabs(ax) + fabs(ay) + fabs(az) + r));
+        const double rr2 = rr * rr, etol = 1e-6 * G.h;
+        int lo[3], hi[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double fl = floor((c3[a] - rr - G.mn[a]) * G.inv_h - 1e-6);
+            const double fh = floor((c3[a] + rr - G.mn[a]) * G.inv_h + 1e-6);
+            lo[a] = fl < 0.0 ? 0 : (fl > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fl);
+            hi[a] = fh < 0.0 ? 0 : (fh > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fh);
+        }
+        const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+        const int nrows = ny * nz;                             // (the host bounds the box: SICP_OUTLIER_MAX_BOX_CELLS)
+        unsigned count = 0;
+        for (int rb = 0; rb < nrows && count < cap; rb += OL_GS) {
+            uint32_t b = 0, len = 0;
+            const int rw = rb + sub;
+            if (rw < nrows) {
+                const int oz = rw / ny, oy = rw - oz * ny;
+                const int cy = lo[1] + oy, cz = lo[2] + oz;
+                const long row = ((long)cz * G.dim[1] + cy) * G.dim[0];
+                const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
+                const double dy = fmax(fmax(yl - etol - ay, ay - (yl + G.h + etol)), 0.0);
+                const double dz = fmax(fmax(zl - etol - az, az - (zl + G.h + etol)), 0.0);
+                const double rem = rr2 - fma(dy, dy, dz * dz);
+                if (rem >= 0.0) {
+                    const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
+                    const double fl = floor((ax - hw - G.mn[0]) * G.inv_h - 1e-6);
+                    const double fh = floor((ax + hw - G.mn[0]) * G.inv_h + 1e-6);
+                    const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
+                    const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
+                    const int xl = tl > lo[0] ? tl : lo[0], xh = th < hi[0] ? th : hi[0];
+                    if (xh >= xl) {
+                        b = cell_start[row + xl];
+                        len = cell_start[row + xh + 1] - b;
+                    }
+                }
+            }
+            unsigned todo = (unsigned)(__ballot(len > 0) >> gbase) & ((1u << OL_GS) - 1u);
+            if (work) n_rows += len > 0 ? 1 : 0;
+            while (todo && count < cap) {
+                const int j = __ffs((int)todo) - 1;
+                todo &= todo - 1u;
+                const uint32_t bj = (uint32_t)__shfl((int)b, gbase + j), lj = (uint32_t)__shfl((int)len, gbase + j);
+                for (uint32_t o = 0; o < lj && count < cap; o += 2 * OL_GS) {
+                    const uint32_t i0 = o + (uint32_t)sub, i1 = i0 + OL_GS;
+                    const bool ok0 = i0 < lj, ok1 = i1 < lj;
+                    const double4 P0 = rec[ok0 ? bj + i0 : bj], P1 = rec[ok1 ? bj + i1 : bj];
+                    const double dx0 = P0.x - ax, dy0 = P0.y - ay, dz0 = P0.z - az;
+                    const double dx1 = P1.x - ax, dy1 = P1.y - ay, dz1 = P1.z - az;
+                    const bool h0 = ok0 && fma(dz0, dz0, fma(dy0, dy0, dx0 * dx0)) < r2;
+                    const bool h1 = ok1 && fma(dz1, dz1, fma(dy1, dy1, dx1 * dx1)) < r2;
+                    const unsigned m0 = (unsigned)(__ballot(h0) >> gbase) & ((1u << OL_GS) - 1u);
+                    const unsigned m1 = (unsigned)(__ballot(h1) >> gbase) & ((1u << OL_GS) - 1u);
+                    count += (unsigned)__popc(m0) + (unsigned)__popc(m1);
+                    if (work) n_cand += (ok0 ? 1 : 0) + (ok1 ? 1 : 0);
+                }
+            }
+        }
+        if (count > cap) count = cap;
+        kept = count >= cap;                                   // count_i > min_points
+        if (sub == 0) {
+            const long p = pos ? (long)pos[q] : q;
+            keep[p] = kept ? 1 : 0;
+            cnt_out[p] = count;
+        }
+    }
+    const unsigned long long kb = __ballot(active && sub == 0 && kept);
+    if (lane == 0 && kb) atomicAdd(kept_total, (unsigned long long)__popcll((long long)kb));
+    if (work) {
+        n_cand = wsum_u64(n_cand); n_rows = wsum_u64(n_rows);
+        if (lane == 0) { atomicAdd(work, n_cand); atomicAdd(work + 1, n_rows); }
+    }
+}
+
+}  // namespace
+}  // namespace sicp
+
+namespace {
+
+enum { OL_MEAN = 0, OL_STD = 1, OL_THR = 2, OL_KEPT = 4, OL_NCAND = 5, OL_WORDS = 8 };
+
+// which of the three candidate forms a call takes, and what both filters check alike
+struct Candidates {
+    const int64_t *d_rows = nullptr;   // device: the candidates' rows (null: rows lo, lo + 1, ...)
+    const uint8_t *d_mask = nullptr;   // the masked form's mask
+    long count = 0;                    // candidates
+    long positions = 0;                // entries of every output
+    bool by_position = false;          // results go to the candidate's ROW (masked form), not to its place in the list
+};
+
+int ol_common(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, const void *keep_out, const char *who)
+{
+    CHK(check_slot(c, slot, true));
+    if (!keep_out) return fail(SICP_ERR_INVALID, "keep_out is null");
+    if (rows && mask) return fail(SICP_ERR_INVALID, "rows and mask are mutually exclusive");
+    if (c->collective())
+        return fail(SICP_ERR_INVALID, "%s is not supported with an exchange (a point's neighbours may live on another rank)", who);
+    const Cloud &cl = c->cloud[slot];
+    if (cl.idx_base != 0) return fail(SICP_ERR_INVALID, "%s is not supported on a shard (a point's neighbours may live on another rank)", who);
+    if (cl.n >= (1LL << 31)) return fail(SICP_ERR_INVALID, "%s takes clouds of fewer than 2^31 points", who);
+    if (rows && (m <= 0 || m >= (1LL << 31))) return fail(SICP_ERR_INVALID, "m must be in [1, 2^31)");
+    if (rows) CHK(check_rows(rows, m, cl.n, "rows"));
+    return SICP_OK;
+}
+
+// the candidates on the device: the list uploaded, or the mask's set bytes collected; c->ol_small cleared
+int ol_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, Candidates *K)
+{
+    const Cloud &cl = c->cloud[slot];
+    CHK(c->ol_small.reserve(OL_WORDS));
+    HIPCHK(hipMemsetAsync(c->ol_small.p, 0, OL_WORDS * sizeof(unsigned long long), c->stream));
+    if (rows) {
+        CHK(c->ol_rows.reserve((size_t)m));
+        HIPCHK(hipMemcpyAsync(c->ol_rows.p, rows, (size_t)m * sizeof(int64_t), hipMemcpyDefault, c->stream));
+        K->d_rows = c->ol_rows.p; K->count = (long)m; K->positions = (long)m;
+    } else if (mask) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, mask) != hipSuccess || at.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            return fail(SICP_ERR_INVALID, "mask is not device memory");
+        }
+        if (at.device != c->device) return fail(SICP_ERR_INVALID, "mask is memory of device %d, the ctx is on device %d", at.device, c->device);
+        CHK(c->ol_rows.reserve((size_t)cl.n));
+        const unsigned g = (unsigned)std::min<long>((cl.n + OL_BLOCK - 1) / OL_BLOCK, OL_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_ol_compact, dim3(g), dim3(OL_BLOCK), 0, c->stream, mask, (long)cl.n, c->ol_rows.p, c->ol_small.p + OL_NCAND);
+        HIPCHK(hipGetLastError());
+        unsigned long long *h = (unsigned long long *)(c->h_small + 208);
+        HIPCHK(hipMemcpyAsync(h, c->ol_small.p + OL_NCAND, sizeof *h, hipMemcpyDeviceToHost, c->stream));
+        CHK(sync(c));
+        K->d_rows = c->ol_rows.p; K->d_mask = mask; K->count = (long)*h; K->positions = (long)cl.n; K->by_position = true;
+    } else {
+        K->count = (long)cl.n; K->positions = (long)cl.n;
+    }
+    return SICP_OK;
+}
+
+// candidates per search: the ctx's switch, else as many as keep a chunk's (chunk, k) distances and indices at 256 MiB
+long ol_chunk(const sicp_ctx *c, int k)
+{
+    if (c->outlier_chunk > 0) return c->outlier_chunk;
+    return std::max<long>(65536, (1L << 24) / std::max(k, 1));
+}
+
+// a chunk's candidates as query columns (c->kq): rows [lo, lo + cnt) of the list, or of the cloud itself
+void ol_gather(sicp_ctx *c, const Cloud &cl, const Candidates &K, long lo, long cnt, long qpad)
+{
+    if (K.d_rows) launch_gather_queries(c->stream, cl.x(), cl.y(), cl.z(), K.d_rows + lo, cnt, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
+    else launch_gather_queries(c->stream, cl.x() + lo, cl.y() + lo, cl.z() + lo, nullptr, cnt, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
+}
+
+// the outputs leave through staging buffers: host or device memory alike, and keep_out may alias the mask
+int ol_deliver(sicp_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, c->stream));
+    return SICP_OK;
+}
+
+// extent of the ball's box of cells on a grid of cell size h, per axis and in all
+long ol_box_cells(const GridGeom &G, double radius, int64_t ext[3])
+{
+    long cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        const double w = std::floor(2.0 * radius * G.inv_h) + 3.0;
+        ext[a] = w < (double)G.dim[a] ? (int64_t)w : (int64_t)G.dim[a];
+        cells = cells > (1L << 40) ? cells : cells * (long)ext[a];
+    }
+    return cells;
+}
+
+// the grid level the radius filter walks: the slot's own grid, always (a coarse twin would admit 512 x the volume per cell counted:
+// the limit on the box is what bounds a candidate's work, so it is taken on the grid the points were binned for)
+int ol_level(sicp_ctx *c, int slot, double radius, GridLevel *lv, int64_t ext[3], long *cells)
+{
+    CHK(grid_build(c, slot));
+    Cloud &cl = c->cloud[slot];
+    lv->g = cl.grid.g; lv->cell_start = cl.grid.cell_start.p; lv->rec = cl.grid.rec.p;
+    *cells = ol_box_cells(lv->g, radius, ext);
+    return SICP_OK;
+}
+
+}  // namespace
+
+SICP_EXPORT int sicp_outlier_version(void) { return SICP_OUTLIER_VERSION; }
+
+SICP_EXPORT int sicp_outlier_statistical(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, int k,
+                                         double std_ratio, uint8_t *keep_out, double *mean_dist_out, sicp_outlier_stats *out)
+{
+    CHK(ol_common(c, slot, rows, m, mask, keep_out, "the statistical filter"));
+    if (!out) return fail(SICP_ERR_INVALID, "out is null");
+    Cloud &cl = c->cloud[slot];
+    if (k < 2) return fail(SICP_ERR_INVALID, "k must be >= 2 (%d given)", k);
+    if (k > SICP_OUTLIER_MAX_K) return fail(SICP_ERR_INVALID, "k must be <= %d (%d given)", SICP_OUTLIER_MAX_K, k);
+    if (k > cl.n) return fail(SICP_ERR_INVALID, "k (%d) exceeds the number of points (%lld)", k, (long long)cl.n);
+    if (!std::isfinite(std_ratio)) return fail(SICP_ERR_INVALID, "std_ratio must be finite");
+    HIPCHK(hipSetDevice(c->device));
+    auto body = [&]() -> int {
+        Candidates K;
+        CHK(ol_candidates(c, slot, rows, m, mask, &K));
+        const long N = K.positions;
+        CHK(c->ol_keep.reserve((size_t)N));
+        CHK(c->ol_d.reserve((size_t)N));
+        std::memset(out, 0, sizeof *out);
+        if (K.count == 0) {                                        // an all-zero mask
+            HIPCHK(hipMemsetAsync(c->ol_keep.p, 0, (size_t)N, c->stream));
+            HIPCHK(hipMemsetAsync(c->ol_d.p, 0, (size_t)N * sizeof(double), c->stream));
+            CHK(ol_deliver(c, keep_out, c->ol_keep.p, (size_t)N));
+            CHK(ol_deliver(c, mean_dist_out, c->ol_d.p, (size_t)N * sizeof(double)));
+            return sync(c);
+        }
+        if (K.by_position) HIPCHK(hipMemsetAsync(c->ol_d.p, 0, (size_t)N * sizeof(double), c->stream));   // +0.0 where no candidate is
+        const long chunk = ol_chunk(c, k);
+        const long qpad_max = round_up(std::min(chunk, K.count), QPAD);
+        CHK(c->kq.reserve((size_t)3 * qpad_max));
+        CHK(c->k_d2.reserve((size_t)std::min(chunk, K.count) * k));
+        CHK(c->k_idx.reserve((size_t)std::min(chunk, K.count) * k));
+        for (long lo = 0; lo < K.count; lo += chunk) {
+            const long cnt = std::min(chunk, K.count - lo), qpad = round_up(cnt, QPAD);
+            ol_gather(c, cl, K, lo, cnt, qpad);
+            CHK(knnk_device(c, slot, c->kq.p, cnt, qpad, k, c->k_d2.p, c->k_idx.p));
+            hipLaunchKernelGGL(k_ol_mean, dim3((unsigned)((cnt + OL_BLOCK - 1) / OL_BLOCK)), dim3(OL_BLOCK), 0, c->stream, c->k_d2.p, cnt, k,
+                               K.by_position ? K.d_rows + lo : nullptr, K.by_position ? c->ol_d.p : c->ol_d.p + lo);
+            HIPCHK(hipGetLastError());
+        }
+        // the two trees over all positions, then the verdicts
+        const long nb = (N + OL_SPAN - 1) / OL_SPAN, nb2 = (nb + OL_FOLD - 1) / OL_FOLD;
+        long P = 1;
+        while (P < N) P *= 2;
+        CHK(c->ol_part.reserve((size_t)(nb + nb2)));
+        double *st = (double *)c->ol_small.p;
+        const double md = (double)K.count;
+        hipLaunchKernelGGL(k_ol_partials<false>, dim3((unsigned)nb), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, P, st, c->ol_part.p);
+        hipLaunchKernelGGL(k_ol_fold<false>, dim3(1), dim3(OL_FOLD), 0, c->stream, c->ol_part.p, c->ol_part.p + nb, nb, md, std_ratio, st);
+        hipLaunchKernelGGL(k_ol_partials<true>, dim3((unsigned)nb), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, P, st, c->ol_part.p);
+        hipLaunchKernelGGL(k_ol_fold<true>, dim3(1), dim3(OL_FOLD), 0, c->stream, c->ol_part.p, c->ol_part.p + nb, nb, md, std_ratio, st);
+        const unsigned g = (unsigned)std::min<long>((N + OL_BLOCK - 1) / OL_BLOCK, OL_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_ol_verdict, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, st, c->ol_keep.p, c->ol_small.p + OL_KEPT);
+        HIPCHK(hipGetLastError());
+        unsigned long long *h = (unsigned long long *)(c->h_small + 208);
+        HIPCHK(hipMemcpyAsync(h, c->ol_small.p, OL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(ol_deliver(c, keep_out, c->ol_keep.p, (size_t)N));
+        CHK(ol_deliver(c, mean_dist_out, c->ol_d.p, (size_t)N * sizeof(double)));
+        CHK(sync(c));
+        out->n_candidates = (int64_t)K.count;
+        out->n_kept = (int64_t)h[OL_KEPT];
+        std::memcpy(&out->mean, h + OL_MEAN, sizeof(double));
+        std::memcpy(&out->std, h + OL_STD, sizeof(double));
+        std::memcpy(&out->threshold, h + OL_THR, sizeof(double));
+        return SICP_OK;
+    };
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+SICP_EXPORT int sicp_outlier_radius_cells(sicp_ctx *c, int slot, double radius, int64_t out4[4])
+{
+    CHK(check_slot(c, slot, true));
+    if (!out4) return fail(SICP_ERR_INVALID, "out4 is null");
+    if (!std::isfinite(radius) || !(radius > 0.0)) return fail(SICP_ERR_INVALID, "radius must be finite and > 0");
+    if (c->cloud[slot].n >= (1LL << 31)) return fail(SICP_ERR_INVALID, "the radius filter takes clouds of fewer than 2^31 points");
+    HIPCHK(hipSetDevice(c->device));
+    GridLevel lv; long cells = 0;
+    CHK(ol_level(c, slot, radius, &lv, out4, &cells));
+    out4[3] = (int64_t)cells;
+    return SICP_OK;
+}
+
+SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, double radius,
+                                    int64_t min_points, uint8_t *keep_out, uint32_t *count_out, int64_t *kept_out)
+{
+    CHK(ol_common(c, slot, rows, m, mask, keep_out, "the radius filter"));
+    if (!kept_out) return fail(SICP_ERR_INVALID, "kept_out is null");
+    if (!std::isfinite(radius) || !(radius > 0.0)) return fail(SICP_ERR_INVALID, "radius must be finite and > 0");
+    if (min_points < 0) return fail(SICP_ERR_INVALID, "min_points must be >= 0");
+    Cloud &cl = c->cloud[slot];
+    HIPCHK(hipSetDevice(c->device));
+    auto body = [&]() -> int {
+        GridLevel lv; int64_t ext[3]; long cells = 0;
+        CHK(ol_level(c, slot, radius, &lv, ext, &cells));
+        if (cells > SICP_OUTLIER_MAX_BOX_CELLS)
+            return fail(SICP_ERR_INVALID, "radius %g spans a box of %lld x %lld x %lld = %lld grid cells (cell size %g): at most %d -- choose a "
+                        "smaller radius", radius, (long long)ext[0], (long long)ext[1], (long long)ext[2], (long long)cells, lv.g.h,
+                        SICP_OUTLIER_MAX_BOX_CELLS);
+        Candidates K;
+        CHK(ol_candidates(c, slot, rows, m, mask, &K));
+        const long N = K.positions;
+        CHK(c->ol_keep.reserve((size_t)N));
+        CHK(c->ol_cnt.reserve((size_t)N));
+        if (K.by_position) {
+            HIPCHK(hipMemsetAsync(c->ol_keep.p, 0, (size_t)N, c->stream));
+            HIPCHK(hipMemsetAsync(c->ol_cnt.p, 0, (size_t)N * sizeof(uint32_t), c->stream));
+        }
+        const double r2 = radius * radius;
+        const unsigned cap = (unsigned)std::min<int64_t>(min_points, (1LL << 31) - 1) + 1u;      // counts stay below 2^31
+        const long chunk = c->outlier_chunk > 0 ? c->outlier_chunk : (1L << 22);
+        CHK(c->kq.reserve((size_t)3 * round_up(std::min(chunk, std::max<long>(K.count, 1)), QPAD)));
+        for (long lo = 0; lo < K.count; lo += chunk) {
+            const long cnt = std::min(chunk, K.count - lo), qpad = round_up(cnt, QPAD);
+            ol_gather(c, cl, K, lo, cnt, qpad);
+            const uint32_t *order = nullptr;
+            if (c->order_min_q > 0 && cnt >= c->order_min_q) {
+                CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, 2.0 * lv.g.h, 1L << 22, c->k_order));
+                order = c->k_order.p;
+            }
+            unsigned g = (unsigned)((cnt + (OL_BLOCK / OL_GS) - 1) / (OL_BLOCK / OL_GS));
+            if (order) g = (g + 7u) & ~7u;
+            hipLaunchKernelGGL(k_ball_count, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, order,
+                               K.by_position ? K.d_rows + lo : nullptr, lv.cell_start, (const double4 *)lv.rec, cnt, lv.g, radius, r2, cap,
+                               K.by_position ? c->ol_keep.p : c->ol_keep.p + lo, K.by_position ? c->ol_cnt.p : c->ol_cnt.p + lo,
+                               c->ol_small.p + OL_KEPT, c->count_work ? c->match_work.p : nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        unsigned long long *h = (unsigned long long *)(c->h_small + 208);
+        HIPCHK(hipMemcpyAsync(h, c->ol_small.p, OL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(ol_deliver(c, keep_out, c->ol_keep.p, (size_t)N));
+        CHK(ol_deliver(c, count_out, c->ol_cnt.p, (size_t)N * sizeof(uint32_t)));
+        CHK(sync(c));
+        *kept_out = (int64_t)h[OL_KEPT];
+        return SICP_OK;
+    };
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}

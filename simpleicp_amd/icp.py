@@ -91,6 +91,49 @@ def _evaluate_distance_of(evaluate_distance):
     return evaluation._distance_of(evaluate_distance, SimpleICPException, "evaluate_distance")
 
 
+def _outlier_of(outlier_neighbors, outlier_std_ratio=2.0):
+    """outlier_neighbors (None = no outlier removal) and outlier_std_ratio -> (k, std_ratio) of contract (O), checked once."""
+    if outlier_neighbors is None:
+        return None
+    k, ok = 0, not isinstance(outlier_neighbors, (bool, str, bytes, float))
+    if ok:
+        try:
+            k = int(outlier_neighbors)
+            ok = k == outlier_neighbors and 2 <= k <= _lib.OUTLIER_MAX_K
+        except (TypeError, ValueError):
+            ok = False
+    if not ok:
+        raise SimpleICPException(f"outlier_neighbors must be an integer >= 2 and <= {_lib.OUTLIER_MAX_K}.")
+    try:
+        ratio = float(outlier_std_ratio)
+        ok = not isinstance(outlier_std_ratio, (bool, str, bytes)) and math.isfinite(ratio)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise SimpleICPException("outlier_std_ratio must be a finite number.")
+    return k, ratio
+
+
+def _check_outlier_size(outlier, n_fix):
+    """The neighbour count against the fixed cloud's size: refused like the option's other argument errors, before any upload."""
+    if outlier is not None and outlier[0] > n_fix:
+        raise SimpleICPException(f"outlier_neighbors ({outlier[0]}) exceeds the number of points of the fixed point cloud ({n_fix}).")
+
+
+def _need_outlier_backend(ctx, outlier):
+    if outlier is not None and not hasattr(ctx, "outlier_statistical"):
+        raise _lib.BackendError("this backend has no outlier removal")
+
+
+def _stats_dict(st):
+    return st.as_dict() if hasattr(st, "as_dict") else dict(st)
+
+
+def _log_outliers(info, st):
+    info(f"Remove statistical outliers ... kept {st['n_kept']} of {st['n_candidates']} points "
+         f"(mean {st['mean']:.5f}, std {st['std']:.5f}, threshold {st['threshold']:.5f})")
+
+
 def _need_voxel_backend(ctx, voxel):
     if voxel is not None and not hasattr(ctx, "voxel_select"):
         raise _lib.BackendError("this backend has no voxel selection")
@@ -113,12 +156,14 @@ def _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle):
 
 
 def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors, max_overlap_distance,
-                      info=None, max_normal_angle=None, voxel=None):
+                      info=None, max_normal_angle=None, voxel=None, outlier=None, outlier_stats=None):
     """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass
-    under the initial H, one point per voxel (voxel: (cell, origin) or None), select_n_points, normals (or pc1's nx, ny, nz,
+    under the initial H, statistical outlier removal (outlier: (k, std_ratio) or None; its statistics go into the dict
+    outlier_stats), one point per voxel (voxel: (cell, origin) or None), select_n_points, normals (or pc1's nx, ny, nz,
     planarity columns), the movable cloud's selected subset and its planarity column, sicp_icp_setup.  Returns the selected rows of pc1.  info: where the progress lines go (the log)."""
     info = info or _log.info
     _need_voxel_backend(ctx, voxel)
+    _need_outlier_backend(ctx, outlier)
     if np.isfinite(max_overlap_distance):
         info("Consider partial overlap of point clouds ...")
         if sel is _ALL or len(sel):
@@ -127,6 +172,18 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
             sel = pc1._keep_selected(sel, near)
         if not len(sel) > 0:
             raise _no_overlap(max_overlap_distance)
+
+    if outlier is not None:
+        # after the overlap pre-pass (only points that can take part are judged), before the voxel step (a voxel's representative
+        # is then always an inlier); the neighbours are searched among ALL points of the fixed cloud
+        if not (sel is _ALL or len(sel)):
+            raise SimpleICPException("The fixed point cloud has no selected points left for the outlier removal.")
+        keep, _, st = ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], rows=None if sel is _ALL else sel)
+        st = _stats_dict(st)
+        _log_outliers(info, st)
+        if outlier_stats is not None:
+            outlier_stats.update(st)
+        sel = pc1._keep_selected(sel, keep)
 
     if voxel is not None:
         # after the overlap pre-pass, so that a voxel's representative always lies inside the overlap
@@ -162,18 +219,29 @@ def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, cor
 
 
 def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None, max_normal_angle=None,
-                             voxel=None):
+                             voxel=None, outlier=None, outlier_stats=None):
     """_select_and_setup for clouds uploaded from device memory (run_tensors, run_batch's device pairs; every point selected, no
     normals or planarity columns): the same steps with every array they hand on left in device memory -- the overlap verdicts, the
     kept rows and the picks of select_n_points (sicp_select_n_device), the normals.  alloc(shape, kind) returns a device buffer
     (kind "u8" / "i64" / "f32") and its address; the buffers are returned and must outlive the run's sicp_icp_setup."""
     info = info or _log.info
     _need_voxel_backend(ctx, voxel)
+    _need_outlier_backend(ctx, outlier)
     mask = mask_p = None
     if np.isfinite(max_overlap_distance):
         info("Consider partial overlap of point clouds ...")
         mask, mask_p = alloc((n_fix,), "u8")
         ctx.select_in_range_into(_lib.FIX, _lib.MOV, H, float(max_overlap_distance), mask_p)
+    if outlier is not None:
+        if mask is None:
+            mask, mask_p = alloc((n_fix,), "u8")
+            st = ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], keep_ptr=mask_p)
+        else:
+            st = ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], mask_ptr=mask_p, keep_ptr=mask_p)   # (the verdicts replace the mask)
+        st = _stats_dict(st)
+        _log_outliers(info, st)
+        if outlier_stats is not None:
+            outlier_stats.update(st)
     if voxel is not None:
         info("Keep one point per voxel ...")
         if mask is None:
@@ -293,6 +361,12 @@ class SimpleICP:
     # searched as that subset.  H, rbp, the residuals and the transformed cloud are the same bits either way.  An attribute for
     # the same reason as max_normal_angle.
     evaluate_distance: Optional[float] = None
+    # Statistical outlier removal: a neighbour count, None = off.  After the overlap pre-pass and before the
+    # voxel step the fixed cloud's selection loses every point whose mean distance to its outlier_neighbors nearest points of the
+    # fixed cloud (itself included) exceeds mean + outlier_std_ratio * std over the selection -- contract (O).  The statistics go to
+    # ``last_run_info["outlier"]``.  The movable cloud is thinned by the caller.  Attributes for the same reason as max_normal_angle.
+    outlier_neighbors: Optional[int] = None
+    outlier_std_ratio: float = 2.0
 
     def __init__(self, verbose: bool = True) -> None:
         self.pc1: Optional[PointCloud] = None
@@ -326,8 +400,10 @@ class SimpleICP:
         _cos_of_max_angle(self.max_normal_angle)
         voxel = _voxel_of(self.voxel_size, self.voxel_origin)
         eval_d = _evaluate_distance_of(self.evaluate_distance)
+        outlier = _outlier_of(self.outlier_neighbors, self.outlier_std_ratio)
         t_start = time.time()
         pc1, pc2 = self.pc1, self.pc2
+        _check_outlier_size(outlier, pc1.num_points)
         ctx = backend.get_context()
         ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
         import os
@@ -335,6 +411,9 @@ class SimpleICP:
         if sharded and voxel is not None:
             raise SimpleICPException("voxel_size does not run in a torch.distributed job: thin the clouds with one process first")
         _need_voxel_backend(ctx, voxel)
+        if sharded and outlier is not None:
+            raise SimpleICPException("outlier_neighbors does not run in a torch.distributed job: thin the clouds with one process first")
+        _need_outlier_backend(ctx, outlier)
         if eval_d is not None:
             if sharded:
                 raise SimpleICPException("evaluate_distance does not run in a torch.distributed job: score the result with one process")
@@ -398,7 +477,7 @@ class SimpleICP:
         try:
             return self._run_uploaded(ctx, sharded, msel, n_search, upload_movable, sel0, t_start, obs, ow, H,
                                       correspondences, neighbors, min_planarity, max_overlap_distance, min_change,
-                                      max_iterations, distance_weights, debug_dirpath, voxel, eval_d)
+                                      max_iterations, distance_weights, debug_dirpath, voxel, eval_d, outlier)
         except BaseException:
             # ANY way out of a sharded run that is not its normal end (a backend error, a host-side exception between two
             # collectives, KeyboardInterrupt, MemoryError) may leave this rank out of step with its peers: never revive the
@@ -413,13 +492,15 @@ class SimpleICP:
 
     def _run_uploaded(self, ctx, sharded, msel, n_search, upload_movable, sel, t_start, obs, ow, H, correspondences, neighbors,
                       min_planarity, max_overlap_distance, min_change, max_iterations, distance_weights, debug_dirpath, voxel=None,
-                      eval_d=None):
+                      eval_d=None, outlier=None):
         pc1, pc2 = self.pc1, self.pc2
+        outlier_stats = {}
         if debug_dirpath:
             X_fix, X_mov = pc1.X, pc2.X
 
         sel = _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors,
-                                max_overlap_distance, max_normal_angle=self.max_normal_angle, voxel=voxel)
+                                max_overlap_distance, max_normal_angle=self.max_normal_angle, voxel=voxel, outlier=outlier,
+                                outlier_stats=outlier_stats)
 
         hooks = None
         if debug_dirpath:
@@ -453,6 +534,8 @@ class SimpleICP:
         self.last_run_info.update(angle_info)
         if eval_d is not None:
             self.last_run_info["evaluation"] = self.evaluation
+        if outlier is not None:
+            self.last_run_info["outlier"] = outlier_stats
         if sharded:
             # how the shards' winners met: "records_allgather" / "key_allreduces" (cloud shards) / "query_slices", and how often
             xi = ctx.exchange_info()

@@ -55,6 +55,8 @@ def voxel_arguments(voxel_size, origin=None, exc=ValueError):
 
 
 class PointCloud(pd.DataFrame):
+    last_outlier_stats = None             # select_statistical_inliers leaves its statistics here (a dict)
+
     def __init__(self, *args, **kwargs) -> None:
         kwargs.pop("remapping", None)     # accepted and ignored, like the reference (pointcloud.py:25)
         super().__init__(*args, **kwargs)
@@ -277,6 +279,49 @@ class PointCloud(pd.DataFrame):
             return
         self._upload(ctx, _lib.FIX)
         keep = ctx.voxel_select(_lib.FIX, c, o, None if len(cur) == self._num_points else cur)
+        self._set_idx_selected(cur[keep])
+
+    def select_statistical_inliers(self, neighbors: int = 20, std_ratio: float = 2.0, _ctx=None) -> None:
+        """Keeps, among the selected points, those whose mean distance to their ``neighbors`` nearest points of the cloud (ALL its
+        points, the point itself included) is at most mean + ``std_ratio`` * std over the selected points, and deselects the rest
+        (contract (O)).  The statistics of the call (n_candidates, n_kept, mean, std, threshold) are left in
+        ``last_outlier_stats``.  Not in the reference; composes with select_in_range, select_voxels and select_n_points."""
+        if isinstance(neighbors, (bool, float, str, bytes)) or int(neighbors) != neighbors or not 2 <= neighbors <= _lib.OUTLIER_MAX_K:
+            raise PointCloudException(f"neighbors must be an integer >= 2 and <= {_lib.OUTLIER_MAX_K}.")
+        try:
+            ratio = float(std_ratio)
+            ok = not isinstance(std_ratio, (bool, str, bytes)) and np.isfinite(ratio)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise PointCloudException("std_ratio must be a finite number.")
+        ctx = _ctx or backend.get_context()
+        cur = self.idx_selected
+        if len(cur) == 0:
+            return
+        self._upload(ctx, _lib.FIX)
+        keep, _, st = ctx.outlier_statistical(_lib.FIX, int(neighbors), ratio, rows=None if len(cur) == self._num_points else cur)
+        self.last_outlier_stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
+        self._set_idx_selected(cur[keep])
+
+    def select_radius_inliers(self, radius: float, min_points: int, _ctx=None) -> None:
+        """Keeps, among the selected points, those with more than ``min_points`` points of the cloud (ALL its points, the point
+        itself included) strictly closer than ``radius``, and deselects the rest (contract (O))."""
+        try:
+            r = float(radius)
+            ok = not isinstance(radius, (bool, str, bytes)) and np.isfinite(r) and r > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise PointCloudException("radius must be a finite number > 0.")
+        if isinstance(min_points, (bool, float, str, bytes)) or int(min_points) != min_points or min_points < 0:
+            raise PointCloudException("min_points must be an integer >= 0.")
+        ctx = _ctx or backend.get_context()
+        cur = self.idx_selected
+        if len(cur) == 0:
+            return
+        self._upload(ctx, _lib.FIX)
+        keep, _, _ = ctx.outlier_radius(_lib.FIX, r, int(min_points), rows=None if len(cur) == self._num_points else cur)
         self._set_idx_selected(cur[keep])
 
     # ---- attributes (pointcloud.py:173-203) ---------------------------------------------

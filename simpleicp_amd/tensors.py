@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib, backend, dist
 from . import evaluation
 from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _evaluate_distance_of, _iterate, _rbp_and_residuals,
-                  _select_and_setup_device, _voxel_of)
+                  _check_outlier_size, _outlier_of, _select_and_setup_device, _voxel_of)
 from .rbp import H_from_params
 
 _log = logging.getLogger(__name__)
@@ -38,7 +38,8 @@ def _is_device_tensor(c) -> bool:
     return type(c).__module__.startswith("torch") and bool(getattr(c, "is_cuda", False))
 
 
-def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None):
+def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None,
+                    outlier_neighbors=None, outlier_std_ratio=2.0):
     """run()'s keyword arguments with run()'s defaults, refused as run() / run_batch refuse them."""
     from .batch import _RUN_DEFAULTS
     unknown = set(run_kwargs) - set(_RUN_DEFAULTS)
@@ -53,6 +54,7 @@ def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, vox
     kw["max_normal_angle"] = max_normal_angle
     kw["voxel"] = _voxel_of(voxel_size, voxel_origin)
     kw["evaluate"] = _evaluate_distance_of(evaluate_distance)
+    kw["outlier"] = _outlier_of(outlier_neighbors, outlier_std_ratio)
     return kw
 
 
@@ -97,7 +99,7 @@ def prepare(ctx, X_fix, X_mov, kw, info):
     _upload(ctx, _lib.MOV, X_mov)
     scratch = _select_and_setup_device(ctx, X_fix.shape[0], H, kw["correspondences"], kw["neighbors"],
                                        kw["max_overlap_distance"], alloc, info=info, max_normal_angle=kw.get("max_normal_angle"),
-                                       voxel=kw.get("voxel"))
+                                       voxel=kw.get("voxel"), outlier=kw.get("outlier"), outlier_stats=kw.get("outlier_stats"))
     return obs, ow, H, scratch
 
 
@@ -109,7 +111,8 @@ def transformed(ctx, X_mov, H):
     return out
 
 
-def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None, **run_kwargs):
+def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None,
+                outlier_neighbors=None, outlier_std_ratio=2.0, **run_kwargs):
     """Registers X_mov to X_fix -- (n, 3) float32 / float64 torch tensors on the GPU of the library's context, any strides -- with
     ``run()``'s keyword arguments.  Returns a BatchResult (path "device") that unpacks as ``(H, X_mov_transformed, rbp,
     residuals)``: H, rbp and residuals are run()'s host values, X_mov_transformed a new device tensor; it also carries
@@ -118,15 +121,21 @@ def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_orig
     ``voxel_size`` / ``voxel_origin`` (None = off / zeros): SimpleICP's attributes of those names, applied to the fixed cloud on the
     device; the movable cloud is thinned by the caller (``X_mov[voxel_keep(X_mov, c)]``).
     ``evaluate_distance`` (None = off): SimpleICP's attribute of that name -- every fixed point is scored under the final H on the
-    device, the Evaluation is the result's ``evaluation``."""
+    device, the Evaluation is the result's ``evaluation``.
+    ``outlier_neighbors`` / ``outlier_std_ratio`` (None = off / 2.0): SimpleICP's attributes of those names, applied to the fixed
+    cloud on the device (contract (O)); the statistics are the result's ``outlier``.  The movable cloud is thinned by the caller
+    (``X_mov[outlier_keep(X_mov, neighbors=20)]``)."""
     from .batch import BatchResult
     t_start = time.time()
-    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle, voxel_size, voxel_origin, evaluate_distance)
+    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle, voxel_size, voxel_origin, evaluate_distance,
+                         outlier_neighbors, outlier_std_ratio)
+    kw["outlier_stats"] = {}
     if dist.is_distributed():
         raise SimpleICPException("run_tensors does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     device = backend.default_device()
     _check_cloud("X_fix", X_fix, device)
     _check_cloud("X_mov", X_mov, device)
+    _check_outlier_size(kw["outlier"], X_fix.shape[0])
     ctx = backend.get_context()
     ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
     dist.detach(ctx)
@@ -143,7 +152,7 @@ def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_orig
     _log.info(f"Finished in {time.time() - t_start:.3f} seconds!")
     return BatchResult(H, X_new, rbp, residuals, iterations=it + 1, n_kept=int(R.n_kept) if R is not None else 0,
                        res_mean=R.res_mean if R is not None else np.nan, res_std=R.res_std if R is not None else np.nan,
-                       path="device", evaluation=ev)
+                       path="device", evaluation=ev, outlier=kw["outlier_stats"] if kw["outlier"] is not None else None)
 
 
 def voxel_keep(X, voxel_size, origin=None, mask=None):
@@ -180,4 +189,64 @@ def voxel_keep(X, voxel_size, origin=None, mask=None):
     else:
         ctx.voxel_select_masked(_lib.FIX, m8.data_ptr(), n, voxel[0], voxel[1], keep_ptr=keep.data_ptr())
     del m8                                               # (the call returned complete: nothing reads it any more)
+    return keep.view(torch.bool)
+
+
+def outlier_keep(X, *, neighbors=None, std_ratio=2.0, radius=None, min_points=None, mask=None):
+    """The keep verdicts of contract (O) for X -- an (n, 3) float32 / float64 torch tensor on the GPU of the
+    library's context, any strides; float32 is widened exactly first -- as a torch.bool tensor (n,).  Exactly one filter is named:
+    ``neighbors`` (with ``std_ratio``): the statistical one -- True where the mean distance to the ``neighbors`` nearest points of X
+    (the point itself included) is at most mean + std_ratio * std over the candidates; ``radius`` (with ``min_points``): True where
+    more than ``min_points`` points of X, the point itself included, lie strictly within ``radius``.  ``mask`` (a bool / uint8 (n,)
+    tensor on the same device): only the points it marks are candidates -- every other point is False --, while neighbours are
+    searched among all of X.  Ingest and stream rule are run_tensors'.  ``X[outlier_keep(X, neighbors=20)]`` is the cleaned cloud;
+    the library's fixed slot holds X afterwards."""
+    import torch
+    if (neighbors is None) == (radius is None):
+        raise ValueError("outlier_keep takes exactly one of neighbors= (statistical filter) and radius= (radius filter)")
+    if neighbors is not None:
+        if min_points is not None:
+            raise ValueError("min_points belongs to the radius filter (radius=)")
+        try:
+            outlier = _outlier_of(neighbors, std_ratio)
+        except SimpleICPException as e:
+            raise ValueError(str(e).replace("outlier_neighbors", "neighbors").replace("outlier_std_ratio", "std_ratio")) from None
+    else:
+        try:
+            r = float(radius)
+            ok = not isinstance(radius, (bool, str, bytes)) and np.isfinite(r) and r > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("radius must be a finite number > 0.")
+        if min_points is None or isinstance(min_points, (bool, float, str, bytes)) or int(min_points) != min_points or min_points < 0:
+            raise ValueError("min_points must be an integer >= 0.")
+    if dist.is_distributed():
+        raise SimpleICPException("outlier_keep does not run in a torch.distributed job: thin the clouds with one process first")
+    device = backend.default_device()
+    _check_cloud("X", X, device)
+    n = X.shape[0]
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
+            raise TypeError("mask must be a bool or uint8 torch.Tensor of shape (n,)")
+        if mask.device != X.device:
+            raise ValueError(f"mask is on {mask.device}, X on {X.device}")
+    if n == 0:
+        return torch.zeros(0, dtype=torch.bool, device=X.device)
+    ctx = backend.get_context()
+    ctx._corr_owner = None
+    dist.detach(ctx)
+    if not hasattr(ctx, "outlier_statistical"):
+        raise _lib.BackendError("this backend has no outlier removal")
+    # (as in voxel_keep: torch's own work for this call is queued before the library's stream is made to wait for torch's)
+    m8 = None if mask is None else mask.contiguous().view(torch.uint8)
+    keep = torch.empty(n, dtype=torch.uint8, device=X.device)
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=X.device).wait_stream(torch.cuda.current_stream(X.device))
+    _upload(ctx, _lib.FIX, X)
+    mp = None if m8 is None else m8.data_ptr()
+    if neighbors is not None:
+        ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], mask_ptr=mp, keep_ptr=keep.data_ptr())
+    else:
+        ctx.outlier_radius(_lib.FIX, r, int(min_points), mask_ptr=mp, keep_ptr=keep.data_ptr())
+    del m8
     return keep.view(torch.bool)
