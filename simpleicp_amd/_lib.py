@@ -62,6 +62,9 @@ EVAL_VERSION = 1
 # include/simpleicp_hip_outlier.h: the statistical and the radius outlier filter, the same kind of companion
 OUTLIER_EXPORTS = ["sicp_outlier_version", "sicp_outlier_statistical", "sicp_outlier_radius", "sicp_outlier_radius_cells"]
 OUTLIER_VERSION = 1
+# include/simpleicp_hip_chain.h: what the device-chained loop of the last run did
+CHAIN_EXPORTS = ["sicp_chain_version", "sicp_chain_info"]
+CHAIN_VERSION = 1
 OUTLIER_MAX_K = 128
 OUTLIER_MAX_BOX_CELLS = 4096
 
@@ -226,6 +229,10 @@ def load():
         L.sicp_outlier_radius.argtypes = [vp, cint, vp, i64, vp, dbl, i64, vp, vp, C.POINTER(i64)]
         L.sicp_outlier_radius_cells.argtypes = [vp, cint, dbl, vp]
         for name in OUTLIER_EXPORTS:
+            getattr(L, name).restype = cint
+    if all(hasattr(L, name) for name in CHAIN_EXPORTS):
+        L.sicp_chain_info.argtypes = [vp, vp]
+        for name in CHAIN_EXPORTS:
             getattr(L, name).restype = cint
     _lib = L
     return L
@@ -966,6 +973,13 @@ class Context:
         d = C.c_uint64(0)
         self._chk(self._L.sicp_match_deferred(self._h, C.byref(d)))
         return {"candidates": int(out[0]), "rows": int(out[1]), "launches": int(out[2]), "deferred": int(d.value)}
+
+    def chain_info(self):
+        """Matches launched early (the tail -> match hand-over, include/simpleicp_hip_chain.h) in the last chained run / since the
+        context was created; 0 = the single-stream chain."""
+        out = np.zeros(2, dtype=np.int64)
+        self._chk(self._L.sicp_chain_info(self._h, _ptr(out)))
+        return {"last_run": int(out[0]), "total": int(out[1])}
 
     def tail_cycles(self):
         """k_icp_tail's own clock over its phases in the last iteration it ran (shader cycles)."""

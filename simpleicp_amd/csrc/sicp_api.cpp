@@ -3,6 +3,7 @@
 // that the fused GPU reductions feed.  No CPU compute fallback exists: without a gfx950 device
 // sicp_ctx_create fails with SICP_ERR_NO_DEVICE.
 #include "sicp_host.h"
+#include "../../include/simpleicp_hip_chain.h"
 
 namespace sicph {
 
@@ -153,6 +154,12 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (rc == SICP_OK) rc = c->ne_partial.reserve((size_t)NE_MAX_GRID * 64);
     if (rc == SICP_OK) rc = c->ticket.reserve(4);
     if (rc == SICP_OK) rc = c->icp_dev.reserve(1);
+    // the hand-over's second stream (like the first: non-blocking, default priority -- HIP maps streams onto the hardware queues the
+    // process already has, a stream adds none), its once-per-run event and the ticket words
+    if (rc == SICP_OK && hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) rc = SICP_ERR_HIP;
+    if (rc == SICP_OK && hipEventCreateWithFlags(&c->pre_ev, hipEventDisableTiming) != hipSuccess) rc = SICP_ERR_HIP;
+    if (rc == SICP_OK) rc = c->pre_tkt.reserve(PRE_TKT_WORDS);
+    if (rc == SICP_OK && hipMemsetAsync(c->pre_tkt.p, 0, PRE_TKT_WORDS * sizeof(unsigned long long), c->stream) != hipSuccess) rc = SICP_ERR_HIP;
     if (rc == SICP_OK) rc = c->lm_dev.reserve(1);
     if (rc == SICP_OK && hipHostMalloc((void **)&c->h_lm, sizeof(LmDev), hipHostMallocDefault) != hipSuccess) rc = SICP_ERR_HIP;
     if (rc == SICP_OK) rc = c->match_work.reserve(8);
@@ -175,6 +182,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_LM")) c->lm_one_launch = std::strcmp(e, "launches") != 0;
     if (const char *e = std::getenv("SICP_HSEL_WINDOW")) c->hsel_window = std::atoi(e) != 0;
     if (const char *e = std::getenv("SICP_TAIL_WINDOW")) c->tail_window = std::atoi(e) != 0;
+    if (const char *e = std::getenv("SICP_CHAIN_PRELAUNCH")) c->chain_prelaunch = std::atoi(e) != 0;
     if (const char *e = std::getenv("SICP_TEST_BARRIER_FAULT")) c->test_barrier_fault = std::atoi(e);
     if (const char *e = std::getenv("SICP_NN_GROUP")) { const int v = std::atoi(e); if (v == 8 || v == 16) c->nn_group = v; }
     if (const char *e = std::getenv("SICP_XCHG_KEYS_MIN_Q")) c->xkeys_min_q = std::atol(e);
@@ -205,6 +213,9 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     if (c->h_bg) { (void)hipHostFree(c->h_bg); c->h_bg = nullptr; }
     c->stage_bg.release(); c->bg_small.release();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); c->stream2 = nullptr; }
+    if (c->pre_ev) { (void)hipEventDestroy(c->pre_ev); c->pre_ev = nullptr; }
+    c->pre_tkt.release();
     if (c->comm) { (void)rccl()->CommDestroy(c->comm); c->comm = nullptr; }
     if (c->h_dl && !c->dl_shared) (void)hipHostFree(c->h_dl);
     c->h_dl = nullptr;
@@ -294,6 +305,13 @@ SICP_EXPORT int sicp_tail_cycles(sicp_ctx *c, double out5[5])
 {
     if (!c || !out5) return fail(SICP_ERR_INVALID, "null argument");
     std::memcpy(out5, c->last_tail_cycles, sizeof c->last_tail_cycles);
+    return SICP_OK;
+}
+SICP_EXPORT int sicp_chain_version(void) { return SICP_CHAIN_VERSION; }
+SICP_EXPORT int sicp_chain_info(sicp_ctx *c, int64_t out2[2])
+{
+    if (!c || !out2) return fail(SICP_ERR_INVALID, "null argument");
+    out2[0] = c->pre_last_run; out2[1] = c->pre_total;
     return SICP_OK;
 }
 SICP_EXPORT int sicp_tail_selection(sicp_ctx *c, int64_t out3[3])

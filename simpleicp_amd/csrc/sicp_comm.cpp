@@ -93,7 +93,16 @@ int wait_ticket(sicp_ctx *c, const double *flag_word, double seq)
         std::atomic_thread_fence(std::memory_order_acquire);
         seen = *flag == seq;
     }
-    if (!seen) return sync(c);
+    if (!seen) {
+        // the launch is slow (a shared GPU, a first-launch stall) or stuck: wait for the stream it is on -- during a run that hands
+        // over early (pre_running) that may be the second one, and `stream` may have nothing queued behind it -- then look again:
+        // a record that still carries another ticket was never written and must not be read
+        CHK(sync(c));
+        if (c->pre_running && c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (*flag != seq) return fail(SICP_ERR_HIP, "a launch ended without publishing its result (ticket %.0f, expected %.0f)", (double)*flag, seq);
+        return SICP_OK;
+    }
     if (c->timing) collect_ready(c);
     return SICP_OK;
 }

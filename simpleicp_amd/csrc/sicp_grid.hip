@@ -19,6 +19,7 @@
 // (corrpts.py:131, simpleicp.py:188-202).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstddef>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -311,6 +312,8 @@ __global__ __launch_bounds__(256) void k_grid_nn(
     const int lane = threadIdx.x & 63;
     const int tight = flags & NN_TIGHT;
     const bool approx = (flags & NN_APPROX) != 0;
+    constexpr bool WAIT = false;
+    unsigned long long *const tkt = nullptr; const unsigned long long wait_seq = 0ull;
   auto one = [&](const long q) {
 #include "sicp_grid_nn_one.inc"
   };
@@ -331,6 +334,42 @@ __global__ __launch_bounds__(256) void k_grid_nn(
         q = order[q];
     }
     if (q >= Q) return;                                   // whole wave leaves together
+    one(q);
+}
+
+// The chained match LAUNCHED EARLY ("The tail -> match hand-over"): k_grid_nn<true, true, EXT>'s search -- one wave per
+// query in launch order, no redo list -- enqueued on the context's other stream while the previous iteration's tail still runs.
+// Its waves fetch what is constant over the run, then wait until tkt[0] (the ticket that tail publishes behind its last
+// device-memory write) reaches wait_seq, and only then read the loop state and the previous match (sicp_grid_nn_one.inc, WAIT).
+// A kernel of its own -- not a template flag of k_grid_nn -- so that every existing instantiation keeps its name, its argument
+// list and its register allocation.
+template <bool EXT>
+__global__ __launch_bounds__(256) void k_grid_nn_wait(
+    IcpDev *__restrict__ st,
+    const double *__restrict__ qx, const double *__restrict__ qy, const double *__restrict__ qz,
+    const double *prev_p2 /* nullable; written by the previous match, read after the ticket */,
+    const uint32_t *__restrict__ cell_start, const double4 *__restrict__ rec,
+    unsigned long long *tkt /* [0] the ticket, [PRE_ERR_WORD] set when a wait gives up */,
+    long Q, GridGeom G, double rmax, int64_t idx_base,
+    double *__restrict__ d2_out, int64_t *__restrict__ idx_out, double *p2_out, int flags, PostMatch post,
+    unsigned long long wait_seq, const unsigned long long *__restrict__ cell_box_arg, GridGeom G2,
+    const uint32_t *__restrict__ cell_start2_arg, const double4 *__restrict__ rec2)
+{
+    constexpr bool XFORM = true, CHAINED = true, WAIT = true;
+    const unsigned long long *const cell_box = EXT ? cell_box_arg : nullptr;
+    const uint32_t *const cell_start2 = EXT ? cell_start2_arg : nullptr;
+    const uint32_t *const redo_list = nullptr;
+    unsigned long long *const work = nullptr;
+    const double max_d2 = __builtin_inf();
+    Xf H, Hinv;                                           // (from the loop state, behind the ticket)
+    const int lane = threadIdx.x & 63;
+    const int tight = flags & NN_TIGHT;
+    const bool approx = (flags & NN_APPROX) != 0;
+  auto one = [&](const long q) {
+#include "sicp_grid_nn_one.inc"
+  };
+    const long q = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (q >= Q) return;                                   // whole wave leaves together (before the workgroup's barrier: ended waves are not waited for)
     one(q);
 }
 
@@ -1886,7 +1925,8 @@ __global__ __launch_bounds__(256) void k_grid_nn_batch(const BatchMember *__rest
     if (launch >= M.max_it) return;
     const long q0 = (long)(blockIdx.x - M.blk0) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (q0 >= (long)M.A.Q) return;                        // whole wave leaves together
-    constexpr bool XFORM = true, CHAINED = true;
+    constexpr bool XFORM = true, CHAINED = true, WAIT = false;
+    unsigned long long *const tkt = nullptr; const unsigned long long wait_seq = 0ull;
     const IcpDev *const st = M.st;
     const double *const qx = M.qx, *const qy = M.qy, *const qz = M.qz;
     const double *const prev_p2 = launch > 0 ? M.m_p2 : M.prev0;
@@ -1910,6 +1950,19 @@ __global__ __launch_bounds__(256) void k_grid_nn_batch(const BatchMember *__rest
 #include "sicp_grid_nn_one.inc"
   };
     one(q0);
+}
+
+// k_grid_nn_wait for the search launch_grid_nn(s, S, NN_WAVE) would run from the chain's loop state (S.st set; no order, no work
+// tallies): EXT as there
+void launch_grid_nn_wait(hipStream_t s, const GridSearch &S, unsigned long long *tkt, unsigned long long wait_seq)
+{
+    const PostMatch pm = S.post ? *S.post : PostMatch{};
+    const GridLevel *c2 = S.coarse;
+    const bool ext = S.cell_box != nullptr || c2 != nullptr;
+    const auto kernel = ext ? k_grid_nn_wait<true> : k_grid_nn_wait<false>;
+    hipLaunchKernelGGL(kernel, dim3(cdiv(S.Q, 4)), dim3(256), 0, s, const_cast<IcpDev *>(S.st), S.qx, S.qy, S.qz, S.prev_p2, S.cell_start,
+                       (const double4 *)S.rec, tkt, S.Q, S.G, S.rmax, S.idx_base, S.d2, S.idx, S.p2, S.flags, pm, wait_seq, S.cell_box,
+                       c2 ? c2->g : S.G, c2 ? c2->cell_start : nullptr, c2 ? (const double4 *)c2->rec : nullptr);
 }
 
 void launch_grid_nn_batch(hipStream_t s, const BatchMember *tab, const uint32_t *blk_member, long blocks, long launch)

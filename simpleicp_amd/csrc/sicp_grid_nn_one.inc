@@ -2,13 +2,63 @@
 // k_grid_nn (sicp_grid.hip) and by the batched match k_grid_nn_batch, so that both compile the same tokens (a shared __device__
 // function changed k_grid_nn's register allocation).  Names it uses: the kernel's parameters (st, qx, qy, qz, prev_p2, cell_start,
 // rec, G, H, Hinv, rmax, max_d2, idx_base, d2_out, idx_out, p2_out, work, post, G2, rec2), the locals lane, tight, approx,
-// cell_box, cell_start2, redo_list, and q, the query.  XFORM, CHAINED: the kernel's template parameters.
+// cell_box, cell_start2, redo_list, and q, the query.  XFORM, CHAINED: the kernel's template parameters.  WAIT (a compile-time
+// constant, with tkt and wait_seq): the launch was enqueued BEFORE the tail it follows has ended and waits for that tail's ticket
+// (k_grid_nn_wait, sicp_grid.hip) -- everywhere else false, and the text below compiles to what it was.
     const double ax = qx[q], ay = qy[q], az = qz[q];      // (issued before the loop state is waited for)
     double px0 = 0, py0 = 0, pz0 = 0;
-    if (prev_p2) { px0 = prev_p2[3 * q]; py0 = prev_p2[3 * q + 1]; pz0 = prev_p2[3 * q + 2]; }
+    if constexpr (!WAIT) { if (prev_p2) { px0 = prev_p2[3 * q]; py0 = prev_p2[3 * q + 1]; pz0 = prev_p2[3 * q + 2]; } }
     float pnx = 0.f, pny = 0.f, pnz = 0.f, ppl = 0.f;     // the query's normal and planarity (wave-uniform; in flight during the search)
     if (post.dist) { pnx = post.normals[3 * q]; pny = post.normals[3 * q + 1]; pnz = post.normals[3 * q + 2]; ppl = post.planarity[q]; }
-    if (CHAINED) {
+    if constexpr (WAIT) {
+        // The loads above are constant over a run (queries, normals, planarity: written before the run, and this launch's stream
+        // waited for that) -- they are in flight while lane 0 of the workgroup's first wave polls the ticket; the other waves wait
+        // at the barrier (waves past Q have ended: the barrier counts the live ones).  Bounded like grid_barrier's polling: a launch
+        // that is never released stops the run (the tails behind it report status 4) instead of hanging the queue.
+        if (threadIdx.x == 0) {
+            long spins = 0;
+            while (__hip_atomic_load(tkt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < wait_seq) {
+                __builtin_amdgcn_s_sleep(4);
+                if (++spins > (1L << 21)) {
+                    // the stop flag first, complete before the error word: a poller that leaves on the error word finds stop set
+                    __hip_atomic_store(reinterpret_cast<unsigned long long *>(const_cast<int *>(&st->done_iters)), 1ull << 32,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __hip_atomic_store(tkt + PRE_ERR_WORD, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    break;
+                }
+                if ((spins & 1023) == 0 && __hip_atomic_load(tkt + PRE_ERR_WORD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) break;
+            }
+        }
+        __syncthreads();
+        // What an earlier launch wrote while this one was already running -- the loop state (H, its inverse, the stop flag: the
+        // tail's agent-scope stores) and the previous match (its plain stores, written back when that kernel ended, before the tail
+        // that published the ticket began) -- is read with agent-scope loads, performed at the coherence point: this XCD's L2 and
+        // the scalar cache may hold lines from before the data existed (the wave's start-of-kernel invalidate came too early).
+        // One load instruction each: lane l takes word l, the values reach the scalar registers by v_readlane.  Everything else the
+        // search reads (the grid, the movable cloud's planarity) is as old as the run.
+        static_assert(offsetof(IcpDev, H) == 96 && offsetof(IcpDev, Hinv) == 192 && offsetof(IcpDev, stop) == 316 && sizeof(Xf) == 96,
+                      "the words lanes 0..27 load");
+        const unsigned long long *sw = reinterpret_cast<const unsigned long long *>(st) + 12;
+        const unsigned long long wv = __hip_atomic_load(sw + (lane < 28 ? lane : 27), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned long long pv = 0ull;
+        if (prev_p2) pv = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(prev_p2) + 3 * q + (lane < 3 ? lane : 2),
+                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned wlo = (unsigned)wv, whi = (unsigned)(wv >> 32);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            H.m[i] = __hiloint2double(__builtin_amdgcn_readlane((int)whi, i), __builtin_amdgcn_readlane((int)wlo, i));
+            Hinv.m[i] = __hiloint2double(__builtin_amdgcn_readlane((int)whi, 12 + i), __builtin_amdgcn_readlane((int)wlo, 12 + i));
+        }
+        if (__builtin_amdgcn_readlane((int)whi, 27) != 0) return;              // IcpDev::stop
+        if (prev_p2) {
+            const unsigned plo = (unsigned)pv, phi = (unsigned)(pv >> 32);
+            px0 = __hiloint2double(__builtin_amdgcn_readlane((int)phi, 0), __builtin_amdgcn_readlane((int)plo, 0));
+            py0 = __hiloint2double(__builtin_amdgcn_readlane((int)phi, 1), __builtin_amdgcn_readlane((int)plo, 1));
+            pz0 = __hiloint2double(__builtin_amdgcn_readlane((int)phi, 2), __builtin_amdgcn_readlane((int)plo, 2));
+        }
+    } else if (CHAINED) {
         H = st->H; Hinv = st->Hinv;
         if (st->stop) return;
     }

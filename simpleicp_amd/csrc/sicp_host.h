@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/simpleicp_hip.h"
+#include "sicp_handover.h"
 #include "sicp_internal.h"
 
 using namespace sicp;
@@ -142,6 +143,7 @@ struct NormalAngle {
 
 struct EventPair { hipEvent_t a, b; int kernel; };
 constexpr int REC_RING = 16;     // records in flight + being read
+static_assert(REC_RING == HANDOVER_RING, "sicp_handover.h indexes the same ring");
 
 inline long round_up(long v, long g) { return (v + g - 1) / g * g; }
 inline double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -282,6 +284,14 @@ struct sicp_ctx {
     long hsel_run_launches = 0;    // chained rejection launches since the last setup (the window needs two of them behind it)
     bool hsel_dirty = false;
     int nn_group = 0;              // SICP_NN_GROUP=8|16: lanes per query of the many-queries search (0: chosen per launch)
+    // the tail -> match hand-over of a small-Q chain: iterations alternate between `stream` and `stream2`, the match of
+    // iteration i + 1 is launched early and waits for the ticket tail i publishes in pre_tkt (PRE_TKT_WORDS words, zeroed at creation)
+    hipStream_t stream2 = nullptr;
+    hipEvent_t pre_ev = nullptr;       // a run's setup + first match are enqueued on `stream`: stream2 waits for it once per run
+    DevBuf<unsigned long long> pre_tkt;
+    bool chain_prelaunch = true;       // SICP_CHAIN_PRELAUNCH=0: the single-stream chain (A/B, tests)
+    bool pre_running = false;          // a run that hands over early is between its first launch and its last record: wait_ticket's slow path waits for both streams
+    int64_t pre_last_run = 0, pre_total = 0;   // matches launched early in the last chained run / since the context was created
     int chain_depth = 4;           // iterations enqueued ahead of the last record read (two are not enough, four are: profiles/r2/ab_chain_depth.txt)
     // sicp_icp_run_batch with this ctx as its FIRST member (sicp_batch.hip): the member table, the match's block -> member map followed
     // by the tail buckets' member lists, and the pinned ring the members' records land in (B x REC_RING x REC_DOUBLES); grown, never shrunk

@@ -356,7 +356,16 @@ struct ChainRun {
     bool over = false;
     int depth;                    // iterations enqueued ahead of the record being read
     int rc = SICP_OK;             // the run's verdict: the last failing record's
+    HandOver ho;                  // the tail -> match hand-over (sicp_handover.h): ho.road, the run launches its matches early
 };
+
+// The largest query set whose chain hands over early.  While match i + 2 waits (from the end of tail i to the ticket of tail i + 1)
+// its workgroups hold their registers, and tail i + 1 needs a CU to run on: 256 VGPRs + 70 AGPRs per lane at 4 correspondences per
+// lane (328 of a SIMD's 512 registers) fit next to ONE waiting match wave (160 registers with the tight boxes, 136 without), not
+// next to two -- and at 8 correspondences per lane (Q > 1024: 480 registers) next to none.  With at most one match workgroup per CU
+// (Q / 4 <= the device's CUs, dealt evenly to the XCDs) every XCD has a CU that holds at most one of them: the tail always finds
+// a place.  Larger Q keeps the single-stream chain.  (profiles/prelaunch/resource_usage_this.txt)
+constexpr long PRELAUNCH_MAX_Q = 1024;
 
 // one iteration's match, decided (plan_match gives the reasons)
 struct MatchPlan {
@@ -417,8 +426,22 @@ MatchPlan plan_match(const sicp_ctx *c, bool grid, int64_t iteration, bool cold_
     return p;
 }
 
+// does a chained run take the hand-over's road ("The tail -> match hand-over")?  One GPU, the grid search with one wave
+// per query and its distance epilogue, nothing between match and tail, no timing events between the launches (they would order
+// the two streams' kernels again), no work tallies; `later`: the plan of the run's iterations after the first
+bool takes_prelaunch(const sicp_ctx *c, const MatchPlan &later, int64_t max_it)
+{
+    const Cloud &cl = c->cloud[SICP_MOV];
+    return c->chain_prelaunch && c->stream2 != nullptr && max_it > 1 && c->Q <= PRELAUNCH_MAX_Q
+           && (c->Q + 3) / 4 <= (long)c->prop.multiProcessorCount
+           && !c->timing && !c->count_work && !c->collective() && !normal_angle_on(c) && !cl.grid.nonuniform
+           && later.grid && !later.qshard && !later.many_q && !later.ordered && !later.coarse && !later.filt && later.post_done
+           && !later.pack && !later.pack_idx && later.cnt == c->Q;
+}
+
 // the match of one chained iteration as planned: companions of the grid, then the launches
-int enqueue_match(sicp_ctx *c, const TailArgs &A, const double xcur[6], MatchPlan &p)
+// ho (null: the single-stream chain): the iteration's place in a run that hands over early -- a waiting match goes to ITS stream
+int enqueue_match(sicp_ctx *c, const TailArgs &A, const double xcur[6], MatchPlan &p, const HandOverStep *ho = nullptr)
 {
     const long Q = c->Q, lo = p.lo, cnt = p.cnt;
     Cloud &cl = c->cloud[SICP_MOV];
@@ -472,6 +495,11 @@ int enqueue_match(sicp_ctx *c, const TailArgs &A, const double xcur[6], MatchPla
     S.prev_p2 = p.coarse ? c->bound_p2.p + 3 * lo : (prev ? prev + 3 * lo : nullptr);
     S.flags = p.coarse ? NN_TIGHT : 0;
     S.post = (p.post_done || p.pack || p.pack_idx) ? &pm : nullptr;
+    if (ho && ho->wait) {
+        // (takes_prelaunch: one wave per query, no order, cnt = Q > 0; the grid's companions were built by the first iteration)
+        launch_grid_nn_wait(ho->stream ? c->stream2 : c->stream, S, c->pre_tkt.p, ho->wait_seq);
+        return SICP_OK;
+    }
     if (cnt > 0) launch_grid_nn(c->stream, S, !p.many_q ? NN_WAVE : p.eight ? NN_LANES8 : NN_LANES16);
     return SICP_OK;
 }
@@ -577,6 +605,28 @@ int enqueue_iteration(sicp_ctx *c, ChainRun &L)
     const auto h0 = std::chrono::steady_clock::now();
     MatchPlan p = plan_match(c, L.grid, L.launched, L.cold_start, L.last_move);
     if (p.grid) c->last_match_kernel = p.kernel;
+    if (L.ho.road) {
+        // the hand-over: iteration i on stream i mod 2, its match (i > 0) waiting for tail i - 1's ticket
+        L.A.seq = (double)(++c->solve_seq);
+        const HandOverStep s = L.ho.next(L.A.seq);
+        hipStream_t const str = s.stream ? c->stream2 : c->stream;
+        if (s.first_on_second) HIPCHK(hipStreamWaitEvent(c->stream2, c->pre_ev, 0));
+        CHK(enqueue_match(c, L.A, L.xcur, p, &s));
+        HIPCHK(hipGetLastError());
+        // (the run's setup -- icp_setup's copies, the grid and its companions, the loop state -- and the first match: what the
+        // second stream's first launch must find complete before it STARTS, whatever it waits for afterwards)
+        if (L.launched == 0) HIPCHK(hipEventRecord(c->pre_ev, c->stream));
+        c->have_prev_match = true;
+        L.seqs[s.slot] = L.A.seq;
+        launch_icp_tail_pre(str, c->q.p, c->q.p + c->qpad, c->q.p + 2 * c->qpad, c->normals.p, c->m_p2.p, L.A, c->icp_dev.p, c->dist.p,
+                            c->flag.p, c->keep.p, c->resid.p, c->h_rec + s.slot * REC_DOUBLES, c->pre_tkt.p);
+        HIPCHK(hipGetLastError());
+        ++L.launched;
+        if (c->host_trace)
+            std::fprintf(stderr, "[host] iteration %lld enqueued in %.1f us (stream %d)\n", (long long)L.launched,
+                         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count(), s.stream);
+        return SICP_OK;
+    }
     CHK(enqueue_match(c, L.A, L.xcur, p));
     HIPCHK(hipGetLastError());
     c->have_prev_match = true;          // (after an exchange: the job-wide winner's coordinates -- still a valid bound)
@@ -616,6 +666,12 @@ int pump_record(sicp_ctx *c, const sicp_iter_params *P0, ChainRun &L, sicp_iter_
         // run is not poisoned by this one (the error word is sticky on the device by design: every later phase must see it)
         L.over = true;
         (void)hipStreamSynchronize(c->stream);
+        if (L.ho.road) {
+            // ... or a match launched early was never released (its tail found no CU: another process holds them).  Both streams
+            // drain (the launches behind it see the stop flag), then the error word is cleared for the next run
+            (void)hipStreamSynchronize(c->stream2);
+            HIPCHK(hipMemsetAsync(c->pre_tkt.p + PRE_ERR_WORD, 0, sizeof(unsigned long long), c->stream));
+        }
         CHK(reset_barrier_state(c));
         c->have_iter = false;
         L.rc = fail(SICP_ERR_HIP, "a device-wide barrier of iteration %lld timed out (blocks not co-resident: is another process "
@@ -642,11 +698,26 @@ int run_device_tail(sicp_ctx *c, const sicp_iter_params *P0, int64_t max_it, dou
     L.A = tail_args(c, P0, min_change);
     std::memcpy(L.xcur, P0->x, sizeof L.xcur);
     L.cold_start = !c->have_prev_match;
+    L.ho.road = small_q && L.grid && takes_prelaunch(c, plan_match(c, L.grid, 1, L.cold_start, L.last_move), max_it);
+    c->pre_last_run = 0;
+    c->pre_running = L.ho.road;
+    int rc = SICP_OK;
     while (true) {
-        while (L.launched < max_it && L.launched - L.completed < L.depth && !L.over) CHK(enqueue_iteration(c, L));
-        if (L.completed == L.launched) break;
-        CHK(pump_record(c, P0, L, results, done_out));
+        while (L.launched < max_it && L.launched - L.completed < L.depth && !L.over)
+            if ((rc = enqueue_iteration(c, L)) != SICP_OK) break;
+        if (rc != SICP_OK || L.completed == L.launched) break;
+        if ((rc = pump_record(c, P0, L, results, done_out)) != SICP_OK) break;
     }
+    c->pre_running = false;
+    if (L.ho.road) {
+        c->pre_last_run = L.ho.early; c->pre_total += L.ho.early;
+        // Every record of the run has been taken, so every launch has finished its device-memory writes -- but a tail on the
+        // second stream may not have ENDED yet, and its keep mask and residuals reach memory for good when it does.  What runs next
+        // on `stream` and reads them (sicp_icp_get_state's copies, sicp_icp_uncertainties, the operator exports, the next run's
+        // first tail) is ordered behind `stream` alone: wait for the second stream here, once per run.
+        if (L.ho.second_used) { const hipError_t e = hipStreamSynchronize(c->stream2); if (rc == SICP_OK) HIPCHK(e); }
+    }
+    if (rc != SICP_OK) return rc;
     return L.rc;
 }
 

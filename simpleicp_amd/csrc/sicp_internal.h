@@ -77,6 +77,14 @@ constexpr int REC_DOUBLES = 64;
 void launch_icp_tail(hipStream_t s, const double *qx, const double *qy, const double *qz, const float *normals,
                      const double *p2, const TailArgs &A, IcpDev *st, const double *dist, const uint8_t *flag,
                      uint8_t *keep, double *resid, double *rec);
+// ---- the tail -> match hand-over of a small-Q chain: the next match runs early on a second stream and waits for a
+// ticket the tail publishes in device memory.  tkt: PRE_TKT_WORDS 64-bit words, [0] the ticket (the TailArgs::seq of the last tail
+// that finished its device-memory writes), [PRE_ERR_WORD] (a cache line of its own) non-zero once a waiting match has given up.
+constexpr int PRE_ERR_WORD = 16;
+constexpr int PRE_TKT_WORDS = 32;
+void launch_icp_tail_pre(hipStream_t s, const double *qx, const double *qy, const double *qz, const float *normals,
+                         const double *p2, const TailArgs &A, IcpDev *st, const double *dist, const uint8_t *flag,
+                         uint8_t *keep, double *resid, double *rec, unsigned long long *tkt);
 
 // solver state of the multi-workgroup evaluation chain (sicp_lm.hip, Q > SOLVE_MAX_Q)
 struct LmDev {
@@ -176,6 +184,7 @@ struct GridSearch {
 // an empty list costs a launch that exits at once
 enum NnFlavour { NN_WAVE, NN_LANES16, NN_LANES8, NN_REDO };
 void launch_grid_nn(hipStream_t s, const GridSearch &S, NnFlavour flavour);
+void launch_grid_nn_wait(hipStream_t s, const GridSearch &S, unsigned long long *tkt, unsigned long long wait_seq);
 // sicp_gridf.hip: the grid's lazily built companions and the filtered many-queries search
 void launch_recf(hipStream_t s, const void *rec, long n, const double c0[3], void *recf);
 void launch_cell_boxes(hipStream_t s, const uint32_t *cell_start, const void *rec, long ncells, const GridGeom &G, unsigned long long *cell_box);

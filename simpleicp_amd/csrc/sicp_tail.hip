@@ -25,6 +25,7 @@
 //   * record and loop state leave the kernel as ONE store instruction each (lanes of wave 0).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstddef>
 
 #include "sicp_internal.h"
 #include "sicp_lanes.h"
@@ -534,10 +535,37 @@ __device__ __forceinline__ void eval_ne_mfma(TailShared &S, const double (&x)[6]
 // (vmcnt(0)), then the ticket as one more such store.  No fence: the host reads nothing else this kernel wrote.  (Round 5 issued
 // __threadfence_system() AND a release store; measured side by side in round 6, profiles/r6: the same 13.0 us per launch -- the
 // kernel's end writes the L2 back anyway -- so the simpler form stays.)
+// AGENT: workgroups of the next match are already running on other XCDs and read these words before this kernel ends -- each word
+// is stored at the coherence point (the convention of grid_barrier, sicp_lanes.h: no cache write-back / invalidate fences)
+template <bool AGENT>
 __device__ __forceinline__ void flush_state(TailShared &S, double *dst, int count)
 {
     const int lane = threadIdx.x & 63;
-    if (lane < count) dst[lane] = S.out2[lane];
+    if constexpr (AGENT) {
+        if (lane < count) __hip_atomic_store(dst + lane, S.out2[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        if (lane < count) dst[lane] = S.out2[lane];
+    }
+}
+// ---- the hand-over to a match that is already running (k_grid_nn_wait, sicp_grid.hip) ----
+// every thread: this wave's device-memory stores are complete (gfx9 counts stores in vmcnt), then the workgroup meets
+__device__ __forceinline__ void drain_block()
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+// one lane: an early exit's stop flag, as the waiting match reads it (done_iters | stop share a 64-bit word; done_iters is not read
+// again once stop is set: every later launch of the run leaves at once, the next run starts from loop_state_init's copy)
+__device__ __forceinline__ void store_stop(IcpDev *st)
+{
+    static_assert(offsetof(IcpDev, stop) == offsetof(IcpDev, done_iters) + 4 && offsetof(IcpDev, done_iters) % 8 == 0, "one word");
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(&st->done_iters), 1ull << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// one lane: the ticket -- the LAST device-memory write of the launch, behind this lane's own earlier stores
+__device__ __forceinline__ void publish_ticket(unsigned long long *tkt, double seq)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(tkt, (unsigned long long)seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void flush_rec(TailShared &S, double *rec, int count)
 {
@@ -565,7 +593,37 @@ __global__ __launch_bounds__(TB, 1) void k_icp_tail(
     const float *__restrict__ normals, uint8_t *__restrict__ keep, double *__restrict__ resid, double *__restrict__ rec, TailArgs A)
 {
     __shared__ TailShared S;
+    constexpr bool PRE = false;
+    unsigned long long *const tkt = nullptr;
 #include "sicp_tail_body.inc"
+}
+
+// The tail of a chain whose next match is launched early on the context's other stream ("The tail -> match hand-over"):
+// the same body, publishing its ticket in tkt[0].  A kernel of its own so that k_icp_tail keeps its argument list and its code.
+template <int EPT>
+__global__ __launch_bounds__(TB, 1) void k_icp_tail_pre(
+    IcpDev *__restrict__ st, const double *__restrict__ dist, const uint8_t *__restrict__ flag,
+    const double *__restrict__ p2, const double *__restrict__ qx, const double *__restrict__ qy, const double *__restrict__ qz,
+    const float *__restrict__ normals, uint8_t *__restrict__ keep, double *__restrict__ resid, double *__restrict__ rec, TailArgs A,
+    unsigned long long *__restrict__ tkt)
+{
+    __shared__ TailShared S;
+    constexpr bool PRE = true;
+#include "sicp_tail_body.inc"
+}
+
+void launch_icp_tail_pre(hipStream_t s, const double *qx, const double *qy, const double *qz, const float *normals,
+                         const double *p2, const TailArgs &A, IcpDev *st, const double *dist, const uint8_t *flag,
+                         uint8_t *keep, double *resid, double *rec, unsigned long long *tkt)
+{
+    if (A.Q <= TB)
+        hipLaunchKernelGGL(k_icp_tail_pre<1>, dim3(1), dim3(TB), 0, s, st, dist, flag, p2, qx, qy, qz, normals, keep, resid, rec, A, tkt);
+    else if (A.Q <= 2 * TB)
+        hipLaunchKernelGGL(k_icp_tail_pre<2>, dim3(1), dim3(TB), 0, s, st, dist, flag, p2, qx, qy, qz, normals, keep, resid, rec, A, tkt);
+    else if (A.Q <= 4 * TB)
+        hipLaunchKernelGGL(k_icp_tail_pre<4>, dim3(1), dim3(TB), 0, s, st, dist, flag, p2, qx, qy, qz, normals, keep, resid, rec, A, tkt);
+    else
+        hipLaunchKernelGGL(k_icp_tail_pre<8>, dim3(1), dim3(TB), 0, s, st, dist, flag, p2, qx, qy, qz, normals, keep, resid, rec, A, tkt);
 }
 
 void launch_icp_tail(hipStream_t s, const double *qx, const double *qy, const double *qz, const float *normals,
@@ -602,6 +660,8 @@ __global__ __launch_bounds__(TB, 1) void k_icp_tail_batch(const BatchMember *__r
     double *const rec = M.ring + (long)slot * REC_DOUBLES;
     TailArgs A = M.A;
     A.seq = seq;
+    constexpr bool PRE = false;
+    unsigned long long *const tkt = nullptr;
 #include "sicp_tail_body.inc"
 }
 

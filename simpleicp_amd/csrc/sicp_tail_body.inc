@@ -1,7 +1,10 @@
 // sicp_tail_body.inc -- the body of the single-workgroup tail: included textually by k_icp_tail (sicp_tail.hip) and by the
 // batched tail k_icp_tail_batch (one member per workgroup), so that both compile the same tokens (a shared __device__ function
 // changed k_icp_tail's register allocation).  Names it uses: S (the kernel's LDS), st, dist, flag, p2, qx, qy, qz, normals, keep,
-// resid, rec, A (TailArgs) and the template parameter EPT.
+// resid, rec, A (TailArgs), the template parameter EPT, and the hand-over's PRE / tkt: PRE (a compile-time constant) = the next
+// match may already be running and waits for this launch's ticket (DESIGN.md, "The tail -> match hand-over"): the loop state leaves
+// through agent-scope stores, and EVERY exit stores A.seq in tkt[0] once all of the launch's device-memory writes are complete --
+// after that only the record to pinned host memory follows.  tkt[PRE_ERR_WORD]: a waiting match gave up (the run stops, status 4).
     const int tid = threadIdx.x, wid = tid >> 6;
     const int Q = A.Q;
     long long tk[6]; tk[0] = clock64();
@@ -22,7 +25,9 @@
     for (int j = 0; j < 6; ++j) { x[j] = st->x[j]; sc[j] = st->sc[j]; }
     const double w_state = st->w, prev_mean = st->prev_mean, prev_std = st->prev_std;
     const int done_iters = st->done_iters;
-    const int stop = st->stop;
+    int stop_in = st->stop;
+    if constexpr (PRE) { if (tkt[PRE_ERR_WORD] != 0ull) stop_in = 2; }
+    const int stop = stop_in;
     const double pmed = st->sel_med, pmad = st->sel_mad;               // the last launch's median and MAD (0: none) ...
     const int pcnt = st->sel_m;                                        // ... of this many distances
     Corr<EPT> C;
@@ -40,7 +45,8 @@
     if (tid < 64) S.out[tid] = 0.0;
     if (stop) {
         // the run ended in an earlier launch (converged / failed): nothing to do but tell the host
-        if (tid == 0) __hip_atomic_store(rec + REC_STATUS, 3.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if constexpr (PRE) { if (tid == 0) publish_ticket(tkt, A.seq); }      // (this launch wrote nothing to device memory)
+        if (tid == 0) __hip_atomic_store(rec + REC_STATUS, (PRE && stop == 2) ? 4.0 : 3.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (wid == 0) publish(rec, A.seq);
         return;
     }
@@ -86,7 +92,11 @@
             S.out[1] = __builtin_nan(""); S.out[2] = __builtin_nan("");
             for (int k = 0; k < 6; ++k) S.out[10 + k] = x[k];
             S.out[REC_STATUS] = 1.0;
-            st->stop = 1;
+            if constexpr (!PRE) st->stop = 1;
+        }
+        if constexpr (PRE) {
+            drain_block();                    // keep mask and residuals of all four waves are written
+            if (tid == 0) { store_stop(st); publish_ticket(tkt, A.seq); }
         }
         if (wid == 0) { flush_rec(S, rec, REC_TICKET); publish(rec, A.seq); }
         return;
@@ -173,7 +183,11 @@
         if (tid == 0) {
             for (int k = 0; k < 6; ++k) S.out[10 + k] = x[k];
             S.out[REC_STATUS] = 1.0;
-            st->stop = 1;
+            if constexpr (!PRE) st->stop = 1;
+        }
+        if constexpr (PRE) {
+            drain_block();                    // keep mask and residuals of all four waves are written
+            if (tid == 0) { store_stop(st); publish_ticket(tkt, A.seq); }
         }
         if (wid == 0) { flush_rec(S, rec, REC_TICKET); publish(rec, A.seq); }
         return;
@@ -285,7 +299,7 @@
         const double cs = prev_std == 0.0 ? (rstd == 0.0 ? 0.0 : __builtin_inf()) : fabs((rstd - prev_std) / prev_std * 100.0);
         conv = cm < A.min_change && cs < A.min_change;
     }
-    if (wid > 1) return;
+    if constexpr (!PRE) { if (wid > 1) return; }
     if (wid == 1) {
         // ---- wave 1: the next iteration's start (estimate, its sin / cos, H(x) and the rigid inverse [R^T | -R^T t]) leaves as one
         //      store -- while wave 0 assembles and publishes the record (every lane of every wave holds the same estimate) ----
@@ -310,8 +324,15 @@
 #pragma unroll
             for (int j = 0; j < ST_DOUBLES; ++j) S.out2[j] = src[j];
         }
-        flush_state(S, reinterpret_cast<double *>(st), ST_DOUBLES);
-        return;
+        flush_state<PRE>(S, reinterpret_cast<double *>(st), ST_DOUBLES);
+        if constexpr (!PRE) return;
+    }
+    if constexpr (PRE) {
+        // the hand-over: residuals and keep mask of all four waves and the new loop state are complete (each wave drains its own
+        // stores, then the barrier), wave 1 publishes the ticket -- the waiting match starts -- while wave 0 assembles the record
+        drain_block();
+        if (tid == 64) publish_ticket(tkt, A.seq);
+        if (wid != 0) return;
     }
     // ---- wave 0: the record (pinned host memory) ----
     if (tid < 30) {
@@ -336,6 +357,7 @@
         S.out[REC_STATUS] = finite ? 0.0 : 2.0;
         S.out[REC_CONVERGED] = conv ? 1.0 : 0.0;
         tk[5] = clock64();
+#pragma unroll
         for (int k = 0; k < 5; ++k) S.out[50 + k] = (double)(tk[k + 1] - tk[k]);
         S.out[59] = (double)t_eval; S.out[60] = (double)t_step; S.out[62] = (double)t_acc;
         S.out[55] = (double)(tsel - tk[1]); S.out[56] = rounds[0]; S.out[57] = (double)(tk[2] - tsel); S.out[58] = rounds[1];
