@@ -34,7 +34,7 @@ import torch
 
 import bench
 import simpleicp_amd
-from simpleicp_amd import _lib, backend, tensors
+from simpleicp_amd import _lib, backend, batch, tensors
 
 ap = argparse.ArgumentParser()
 ap.add_argument("mode", choices=["cost", "icp"])
@@ -124,8 +124,8 @@ def icp():
         ang, tr = h_distance(res.H, H_true)
         rec = {"mode": "icp", "way": name, "n_fixed": len(Tf), "n_movable": len(mov), "cell": cell if extra else None,
                "iterations": res.iterations, "n_kept": res.n_kept, "H_rotation_error_deg": ang, "H_translation_error": tr}
-        kw = tensors._checked_kwargs({"correspondences": 10_000}, "voxel_probe", None, extra.get("voxel_size"))
-        _, _, _, scratch = tensors.prepare(ctx, Tf, mov, kw, lambda *a: None)
+        kw, extras = batch.merged_keywords("voxel_probe", dict(batch._EXTRA_DEFAULTS, **extra), {"correspondences": 10_000})
+        _, _, scratch = tensors.prepare(ctx, Tf, mov, kw, extras, lambda *a: None)
         rec["Q"] = ctx._Q
         x = np.array(ctx.icp_run(z, z, z, 0.3, 1.0, max_iterations=12, min_change=0.0)[-1].x[:])      # settle (untimed)
         per = []

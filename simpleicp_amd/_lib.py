@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
+from functools import partial
 from pathlib import Path
 
 import numpy as np
@@ -114,6 +116,42 @@ class BatchMember(C.Structure):
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 
+_vp, _i64, _dbl, _cint = C.c_void_p, C.c_int64, C.c_double, C.c_int
+
+
+# one companion header: its exports (the version function first), the header's file name, the noun of its entry points in the
+# messages, the version this binding needs (None: _feature_version reports whatever the library says), the argtypes of the exports
+# that take arguments
+_Feature = namedtuple("_Feature", "exports header noun version argtypes")
+
+FEATURES = {
+    "batch": _Feature(BATCH_EXPORTS, "simpleicp_hip_batch.h", "batch", None, {
+        "sicp_icp_run_batch": [C.POINTER(BatchMember), _i64, C.POINTER(_i64)],
+        "sicp_ctx_lean": [_vp]}),
+    "device": _Feature(DEVICE_EXPORTS, "simpleicp_hip_device.h", "device-cloud", DEVICE_VERSION, {
+        "sicp_cloud_upload_strided": [_vp, _cint, _vp, _cint, _i64, _i64, _i64, _i64],
+        "sicp_select_n_device": [_vp, _vp, _i64, _i64, _vp, C.POINTER(_i64)],
+        "sicp_select_positions": [_i64, _i64, _vp, C.POINTER(_i64)],
+        "sicp_cloud_write_strided": [_vp, _cint, _vp, _vp, _cint, _i64, _i64]}),
+    "normals": _Feature(NORMALS_EXPORTS, "simpleicp_hip_normals.h", "normal-angle", NORMALS_VERSION, {
+        "sicp_cloud_set_normals": [_vp, _cint, _vp, _vp, _i64, _i64],
+        "sicp_normal_angle_set": [_vp, _dbl, _cint],
+        "sicp_corr_reject_normal_angle": [_vp, _dbl, _cint, _vp, _vp, C.POINTER(_i64)],
+        "sicp_normal_angle_info": [_vp, _vp],
+        "sicp_normal_cache_read": [_vp, _vp, _vp]}),
+    "voxel": _Feature(VOXEL_EXPORTS, "simpleicp_hip_voxel.h", "voxel", VOXEL_VERSION, {
+        "sicp_voxel_select": [_vp, _cint, _vp, _i64, _dbl, _vp, _vp, C.POINTER(_i64)],
+        "sicp_voxel_select_masked": [_vp, _cint, _vp, _i64, _dbl, _vp, _vp, C.POINTER(_i64)]}),
+    "evaluation": _Feature(EVAL_EXPORTS, "simpleicp_hip_eval.h", "evaluation", EVAL_VERSION, {
+        "sicp_evaluate": [_vp, _cint, _cint, _vp, _i64, _vp, _dbl, C.POINTER(EvalRecord)]}),
+    "outlier": _Feature(OUTLIER_EXPORTS, "simpleicp_hip_outlier.h", "outlier", OUTLIER_VERSION, {
+        "sicp_outlier_statistical": [_vp, _cint, _vp, _i64, _vp, _cint, _dbl, _vp, _vp, C.POINTER(OutlierStats)],
+        "sicp_outlier_radius": [_vp, _cint, _vp, _i64, _vp, _dbl, _i64, _vp, _vp, C.POINTER(_i64)],
+        "sicp_outlier_radius_cells": [_vp, _cint, _dbl, _vp]}),
+    "chain": _Feature(CHAIN_EXPORTS, "simpleicp_hip_chain.h", "chain", CHAIN_VERSION, {
+        "sicp_chain_info": [_vp, _vp]}),
+}
+
 _lib = None
 
 
@@ -133,7 +171,7 @@ def load():
         L = C.CDLL(str(LIB_PATH))
     except OSError as exc:
         raise BackendError(f"cannot load {LIB_PATH}: {exc}") from exc
-    vp, i64, dbl, cint = C.c_void_p, C.c_int64, C.c_double, C.c_int
+    vp, i64, dbl, cint = _vp, _i64, _dbl, _cint
     L.sicp_abi_version.restype = cint
     if L.sicp_abi_version() != ABI_VERSION:
         # (SICP_LIBRARY makes it easy to point at a stale build: its entry points would be called with the wrong arguments)
@@ -194,46 +232,13 @@ def load():
     for name in EXPORTS:
         if name != "sicp_last_error":
             getattr(L, name).restype = cint
-    if all(hasattr(L, name) for name in BATCH_EXPORTS):
-        L.sicp_batch_version.restype = cint
-        L.sicp_icp_run_batch.argtypes = [C.POINTER(BatchMember), i64, C.POINTER(i64)]
-        L.sicp_icp_run_batch.restype = cint
-        L.sicp_ctx_lean.argtypes = [vp]
-        L.sicp_ctx_lean.restype = cint
-    if all(hasattr(L, name) for name in DEVICE_EXPORTS):
-        L.sicp_cloud_upload_strided.argtypes = [vp, cint, vp, cint, i64, i64, i64, i64]
-        L.sicp_select_n_device.argtypes = [vp, vp, i64, i64, vp, C.POINTER(i64)]
-        L.sicp_select_positions.argtypes = [i64, i64, vp, C.POINTER(i64)]
-        L.sicp_cloud_write_strided.argtypes = [vp, cint, vp, vp, cint, i64, i64]
-        for name in DEVICE_EXPORTS:
-            getattr(L, name).restype = cint
-    if all(hasattr(L, name) for name in NORMALS_EXPORTS):
-        L.sicp_cloud_set_normals.argtypes = [vp, cint, vp, vp, i64, i64]
-        L.sicp_normal_angle_set.argtypes = [vp, dbl, cint]
-        L.sicp_corr_reject_normal_angle.argtypes = [vp, dbl, cint, vp, vp, C.POINTER(i64)]
-        L.sicp_normal_angle_info.argtypes = [vp, vp]
-        L.sicp_normal_cache_read.argtypes = [vp, vp, vp]
-        for name in NORMALS_EXPORTS:
-            getattr(L, name).restype = cint
-    if all(hasattr(L, name) for name in VOXEL_EXPORTS):
-        L.sicp_voxel_select.argtypes = [vp, cint, vp, i64, dbl, vp, vp, C.POINTER(i64)]
-        L.sicp_voxel_select_masked.argtypes = [vp, cint, vp, i64, dbl, vp, vp, C.POINTER(i64)]
-        for name in VOXEL_EXPORTS:
-            getattr(L, name).restype = cint
-    if all(hasattr(L, name) for name in EVAL_EXPORTS):
-        L.sicp_evaluate.argtypes = [vp, cint, cint, vp, i64, vp, dbl, C.POINTER(EvalRecord)]
-        for name in EVAL_EXPORTS:
-            getattr(L, name).restype = cint
-    if all(hasattr(L, name) for name in OUTLIER_EXPORTS):
-        L.sicp_outlier_statistical.argtypes = [vp, cint, vp, i64, vp, cint, dbl, vp, vp, C.POINTER(OutlierStats)]
-        L.sicp_outlier_radius.argtypes = [vp, cint, vp, i64, vp, dbl, i64, vp, vp, C.POINTER(i64)]
-        L.sicp_outlier_radius_cells.argtypes = [vp, cint, dbl, vp]
-        for name in OUTLIER_EXPORTS:
-            getattr(L, name).restype = cint
-    if all(hasattr(L, name) for name in CHAIN_EXPORTS):
-        L.sicp_chain_info.argtypes = [vp, vp]
-        for name in CHAIN_EXPORTS:
-            getattr(L, name).restype = cint
+    for feature in FEATURES.values():
+        # (a library that predates a companion header loads all the same: _feature_version reports it when the feature is asked for)
+        if all(hasattr(L, name) for name in feature.exports):
+            for name in feature.exports:
+                getattr(L, name).restype = cint
+                if name in feature.argtypes:
+                    getattr(L, name).argtypes = feature.argtypes[name]
     _lib = L
     return L
 
@@ -265,79 +270,27 @@ def params_to_H(x):
     return H.reshape(4, 4)
 
 
-def batch_version():
-    """SICP_BATCH_VERSION of the loaded library; BackendError when it has no batch entry points."""
-    L = load()
-    missing = [name for name in BATCH_EXPORTS if not hasattr(L, name)]
+def _feature_version(name):
+    """The version the loaded library reports for the companion header FEATURES[name]; BackendError when it lacks one of the
+    header's entry points, or implements another version than this binding needs."""
+    L, f = load(), FEATURES[name]
+    missing = [export for export in f.exports if not hasattr(L, export)]
     if missing:
-        raise BackendError(f"{LIB_PATH} has no batch entry points ({', '.join(missing)}): it predates include/simpleicp_hip_batch.h; "
+        raise BackendError(f"{LIB_PATH} has no {f.noun} entry points ({', '.join(missing)}): it predates include/{f.header}; "
                            "rebuild with `python -m simpleicp_amd.build`")
-    return L.sicp_batch_version()
-
-
-def device_version():
-    """SICP_DEVICE_VERSION of the loaded library; BackendError when it has no device-cloud entry points."""
-    L = load()
-    missing = [name for name in DEVICE_EXPORTS if not hasattr(L, name)]
-    if missing:
-        raise BackendError(f"{LIB_PATH} has no device-cloud entry points ({', '.join(missing)}): it predates "
-                           "include/simpleicp_hip_device.h; rebuild with `python -m simpleicp_amd.build`")
-    v = L.sicp_device_version()
-    if v != DEVICE_VERSION:
-        raise BackendError(f"{LIB_PATH} implements device version {v}, this binding needs {DEVICE_VERSION}")
+    v = getattr(L, f.exports[0])()
+    if f.version is not None and v != f.version:
+        raise BackendError(f"{LIB_PATH} implements {name} version {v}, this binding needs {f.version}")
     return v
 
 
-def normals_version():
-    """SICP_NORMALS_VERSION of the loaded library; BackendError when it has no normal-angle entry points."""
-    L = load()
-    missing = [name for name in NORMALS_EXPORTS if not hasattr(L, name)]
-    if missing:
-        raise BackendError(f"{LIB_PATH} has no normal-angle entry points ({', '.join(missing)}): it predates "
-                           "include/simpleicp_hip_normals.h; rebuild with `python -m simpleicp_amd.build`")
-    v = L.sicp_normals_version()
-    if v != NORMALS_VERSION:
-        raise BackendError(f"{LIB_PATH} implements normals version {v}, this binding needs {NORMALS_VERSION}")
-    return v
-
-
-def voxel_version():
-    """SICP_VOXEL_VERSION of the loaded library; BackendError when it has no voxel entry points."""
-    L = load()
-    missing = [name for name in VOXEL_EXPORTS if not hasattr(L, name)]
-    if missing:
-        raise BackendError(f"{LIB_PATH} has no voxel entry points ({', '.join(missing)}): it predates "
-                           "include/simpleicp_hip_voxel.h; rebuild with `python -m simpleicp_amd.build`")
-    v = L.sicp_voxel_version()
-    if v != VOXEL_VERSION:
-        raise BackendError(f"{LIB_PATH} implements voxel version {v}, this binding needs {VOXEL_VERSION}")
-    return v
-
-
-def eval_version():
-    """SICP_EVAL_VERSION of the loaded library; BackendError when it has no evaluation entry points."""
-    L = load()
-    missing = [name for name in EVAL_EXPORTS if not hasattr(L, name)]
-    if missing:
-        raise BackendError(f"{LIB_PATH} has no evaluation entry points ({', '.join(missing)}): it predates "
-                           "include/simpleicp_hip_eval.h; rebuild with `python -m simpleicp_amd.build`")
-    v = L.sicp_eval_version()
-    if v != EVAL_VERSION:
-        raise BackendError(f"{LIB_PATH} implements evaluation version {v}, this binding needs {EVAL_VERSION}")
-    return v
-
-
-def outlier_version():
-    """SICP_OUTLIER_VERSION of the loaded library; BackendError when it has no outlier entry points."""
-    L = load()
-    missing = [name for name in OUTLIER_EXPORTS if not hasattr(L, name)]
-    if missing:
-        raise BackendError(f"{LIB_PATH} has no outlier entry points ({', '.join(missing)}): it predates "
-                           "include/simpleicp_hip_outlier.h; rebuild with `python -m simpleicp_amd.build`")
-    v = L.sicp_outlier_version()
-    if v != OUTLIER_VERSION:
-        raise BackendError(f"{LIB_PATH} implements outlier version {v}, this binding needs {OUTLIER_VERSION}")
-    return v
+# SICP_<X>_VERSION of the loaded library; BackendError when it lacks the header's entry points or implements another version
+batch_version = partial(_feature_version, "batch")             # (any version: icp_run_batch checks it)
+device_version = partial(_feature_version, "device")
+normals_version = partial(_feature_version, "normals")
+voxel_version = partial(_feature_version, "voxel")
+eval_version = partial(_feature_version, "evaluation")
+outlier_version = partial(_feature_version, "outlier")
 
 
 def select_positions(m, Q):

@@ -15,13 +15,14 @@ from __future__ import annotations
 import inspect
 import logging
 import time
+from collections import namedtuple
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib, backend, dist, evaluation
-from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _evaluate_distance_of, _rbp_and_residuals, _select_and_setup,
-                  _check_outlier_size, _outlier_of, _voxel_of)
+from .icp import (EXTRA_DEFAULTS as _EXTRA_DEFAULTS, RunExtras, RunKeywords, SimpleICP, SimpleICPException, _HostSelection,
+                  _movable_rows, _prepare, _rbp_and_residuals, _start_pose)
 from .pointcloud import PointCloud, PointCloudException
 from .rbp import H_from_params
 
@@ -32,9 +33,26 @@ last_run_info: dict = {}
 
 # run()'s keyword arguments and their defaults, read off its signature (a default changed there is the batch's as well)
 _RUN_DEFAULTS = {name: prm.default for name, prm in inspect.signature(SimpleICP.run).parameters.items() if name != "self"}
-# keywords of run_batch / run_tensors / the per_pair dicts that are not run()'s (SimpleICP carries them as attributes)
-_EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None, "evaluate_distance": None,
-                   "outlier_neighbors": None, "outlier_std_ratio": 2.0}
+# (_EXTRA_DEFAULTS, icp.EXTRA_DEFAULTS: the keywords of run_batch / run_tensors / the per_pair dicts that are not run()'s)
+
+
+def merged_keywords(who, extras, run_kwargs, pair=None, check_arguments=True):
+    """What one pair of ``who`` (run_batch / run_tensors) runs with: run()'s defaults and the call's options ``extras`` (the names
+    of _EXTRA_DEFAULTS), overridden by the call's keywords, overridden by the pair's own (a dict or None) -- as (RunKeywords,
+    RunExtras), refused as run() refuses them.  check_arguments False: RunKeywords.check() is left to the caller (run_batch
+    reports a bad argument of run() as the pair's error, not as its own)."""
+    kw = dict(_RUN_DEFAULTS, **extras)
+    for src in (run_kwargs, pair or {}):
+        unknown = set(src) - set(kw)
+        if unknown:
+            raise TypeError(f"{who} got unexpected keyword argument(s) {sorted(unknown)}")
+        kw.update(src)
+    if kw["debug_dirpath"]:
+        raise SimpleICPException(f"{who} writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
+    run_kw = RunKeywords(**{name: kw[name] for name in _RUN_DEFAULTS})
+    if check_arguments:
+        run_kw.check()
+    return run_kw, RunExtras.checked(**{name: kw[name] for name in _EXTRA_DEFAULTS})
 
 
 class BatchResult(tuple):
@@ -53,6 +71,13 @@ class BatchResult(tuple):
         self.outlier = outlier
         self.path = path          # "batched" / "fallback" (the pair ran through sicp_icp_run: Q > 2048 and the like) / "device" (run_tensors)
         return self
+
+    @classmethod
+    def of_run(cls, values, R, iterations, path, evaluation=None, outlier=None):
+        """From what run() returns (``values``), the last iteration's record R (None: no iteration ran) and their number."""
+        return cls(*values, iterations=iterations, n_kept=int(R.n_kept) if R is not None else 0,
+                   res_mean=R.res_mean if R is not None else np.nan, res_std=R.res_std if R is not None else np.nan,
+                   path=path, evaluation=evaluation, outlier=outlier)
 
     H = property(lambda self: self[0])
     X_mov_transformed = property(lambda self: self[1])
@@ -95,23 +120,10 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
         raise ValueError(f"per_pair has {len(per_pair)} entries for {len(pairs)} pairs")
     if dist.is_distributed():
         raise SimpleICPException("run_batch does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
-    kws = []
-    for i in range(len(pairs)):
-        kw = dict(_RUN_DEFAULTS, max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin,
-                  evaluate_distance=evaluate_distance, outlier_neighbors=outlier_neighbors, outlier_std_ratio=outlier_std_ratio)
-        for src in (run_kwargs, (per_pair[i] or {}) if per_pair is not None else {}):
-            unknown = set(src) - set(_RUN_DEFAULTS) - set(_EXTRA_DEFAULTS)
-            if unknown:
-                raise TypeError(f"run_batch got unexpected keyword argument(s) {sorted(unknown)}")
-            kw.update(src)
-        if kw["debug_dirpath"]:
-            raise SimpleICPException("run_batch writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
-        _cos_of_max_angle(kw["max_normal_angle"])
-        kw["voxel"] = _voxel_of(kw["voxel_size"], kw["voxel_origin"])
-        kw["evaluate"] = _evaluate_distance_of(kw["evaluate_distance"])
-        kw["outlier"] = _outlier_of(kw["outlier_neighbors"], kw["outlier_std_ratio"])
-        kw["outlier_stats"] = {}
-        kws.append(kw)
+    options = dict(max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin,
+                   evaluate_distance=evaluate_distance, outlier_neighbors=outlier_neighbors, outlier_std_ratio=outlier_std_ratio)
+    checked = [merged_keywords("run_batch", options, run_kwargs, per_pair[i] if per_pair is not None else None, check_arguments=False)
+               for i in range(len(pairs))]
     if not pairs:
         return []
     on_device = [_device_pair(fix, mov) for fix, mov in pairs]
@@ -124,66 +136,58 @@ def run_batch(pairs: Sequence, *, per_pair: Optional[Sequence[Optional[dict]]] =
 
     ctxs = backend.get_batch_contexts(len(pairs))
     out = [None] * len(pairs)
-    prepared = []          # (pair index, ctx, pc2, msel, obs, ow, device pair: (X_mov, its scratch) or None, evaluate_distance or None, outlier statistics or None)
+    prepared = []
     members = []
-    for i, ((fix, mov), kw) in enumerate(zip(pairs, kws)):
+    for i, ((fix, mov), (kw, extras)) in enumerate(zip(pairs, checked)):
         ctx = ctxs[i]
         ctx._corr_owner = None
         try:
-            if kw["evaluate"] is not None:
+            # (the evaluation's entry point is asked for before the pair's clouds are looked at, the other options' by _prepare)
+            if extras.evaluate is not None:
                 evaluation.need_backend(ctx)
             if on_device[i]:
-                SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
-                _check_outlier_size(kw["outlier"], fix.shape[0])
-                obs, ow, _, scratch = tensors.prepare(ctx, fix, mov, kw, _quiet)
-                members.append((ctx, _member_kwargs(obs, ow, kw)))
-                prepared.append((i, ctx, None, None, obs, ow, (mov, scratch), kw["evaluate"],
-                                 kw["outlier_stats"] if kw["outlier"] is not None else None))
-                continue
-            pc1, pc2 = _cloud(fix), _cloud(mov)
-            _check_outlier_size(kw["outlier"], pc1.num_points)
-            SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
-            obs = np.array(kw["rbp_observed_values"], dtype=float)
-            obs[:3] = obs[:3] * np.pi / 180
-            ow = np.array(kw["rbp_observation_weights"], dtype=float)
-            H = H_from_params(obs)
-            # SimpleICP.run's uploads on one GPU (the fixed cloud behind the caller, the movable one behind it)
-            pc1._upload(ctx, _lib.FIX, background=True)
-            partial = not bool(pc2["selected"].to_numpy().all())
-            msel = pc2.idx_selected if partial else None
-            if partial and not len(msel):
-                raise SimpleICPException("The movable point cloud has no selected points.")
-            n_search = len(msel) if partial else pc2.num_points
-
-            def upload_movable(rows=None, pc2=pc2, ctx=ctx):
-                n = pc2.num_points if rows is None else len(rows)
-                pc2._upload(ctx, _lib.MOV, 0, n, index_base=0, rows=rows)
-
-            sel0 = pc1._selection()
-            pc2._upload(ctx, _lib.MOV, background=True)
-            ctx.upload_wait(_lib.FIX)
-            _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel0, H, kw["correspondences"], kw["neighbors"],
-                              kw["max_overlap_distance"], info=_quiet, max_normal_angle=kw["max_normal_angle"], voxel=kw["voxel"],
-                              outlier=kw["outlier"], outlier_stats=kw["outlier_stats"])
+                kw.check()
+                extras.check_fixed_size(fix.shape[0])
+                pose, stats, scratch = tensors.prepare(ctx, fix, mov, kw, extras, _quiet)
+                pc2, msel, dev = None, None, (mov, scratch)
+            else:
+                pc1, pc2 = _cloud(fix), _cloud(mov)
+                extras.check_fixed_size(pc1.num_points)
+                kw.check()
+                pose = _start_pose(kw)
+                # SimpleICP.run's uploads on one GPU (the fixed cloud behind the caller, the movable one behind it)
+                pc1._upload(ctx, _lib.FIX, background=True)
+                selection = _HostSelection(ctx, pc1, pc2, *_movable_rows(pc2))
+                pc2._upload(ctx, _lib.MOV, background=True)
+                ctx.upload_wait(_lib.FIX)
+                stats = _prepare(selection, kw, extras, pose[2], _quiet)
+                msel, dev = selection.msel, None
         except (SimpleICPException, PointCloudException, _lib.BackendError) as e:
             # what run() would raise for this pair (no overlap, a non-finite coordinate, ...): the pair's error, the others go on
             out[i] = BatchResult(error=e)
             continue
-        members.append((ctx, _member_kwargs(obs, ow, kw)))
-        prepared.append((i, ctx, pc2, msel, obs, ow, None, kw["evaluate"], kw["outlier_stats"] if kw["outlier"] is not None else None))
+        obs, ow, _ = pose
+        members.append((ctx, dict(x=obs.copy(), obs=obs, obs_weight=ow, min_planarity=kw.min_planarity, distance_weight=kw.distance_weights,
+                                  max_iterations=kw.max_iterations, min_change=kw.min_change)))
+        prepared.append(_Prepared(i, ctx, pc2, msel, obs, ow, dev, extras.evaluate, stats))
 
     t1 = time.time()
     runs, fallback = members[0][0].icp_run_batch(members) if members else ([], 0)
     t2 = time.time()
-    for (i, ctx, pc2, msel, obs, ow, dev, eval_d, ostats), r in zip(prepared, runs):
-        out[i] = _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev, eval_d)
-        out[i].outlier = ostats
+    for p, r in zip(prepared, runs):
+        out[p.i] = _result(p, r, return_transformed)
     last_run_info.clear()
     last_run_info.update(pairs=len(pairs), fallback=fallback, prepare_s=t1 - t0, batch_s=t2 - t1, results_s=time.time() - t2)
     n_err = sum(1 for o in out if o.error is not None)
     _log.info(f"run_batch: {len(pairs)} pairs ({len(members) - fallback} batched, {fallback} fallback, {n_err} failed) "
               f"in {time.time() - t0:.3f} seconds")
     return out
+
+
+# a pair whose preparation went through, as its epilogue needs it -- i: its index; pc2, msel: its movable PointCloud and the rows of
+# it that were searched (None: all); dev: (X_mov, scratch) of a device pair, else None; evaluate: its evaluate_distance or None;
+# outlier: the statistics of its outlier removal or None
+_Prepared = namedtuple("_Prepared", "i ctx pc2 msel obs ow dev evaluate outlier")
 
 
 def _device_pair(fix, mov) -> bool:
@@ -194,14 +198,10 @@ def _device_pair(fix, mov) -> bool:
     return d[0]
 
 
-def _member_kwargs(obs, ow, kw) -> dict:
-    return dict(x=obs.copy(), obs=obs, obs_weight=ow, min_planarity=kw["min_planarity"], distance_weight=kw["distance_weights"],
-                max_iterations=kw["max_iterations"], min_change=kw["min_change"])
-
-
-def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None, eval_d=None) -> BatchResult:
-    """SimpleICP.run's epilogue for one member: what it returns, or the exception it raises.  dev: (X_mov, scratch) of a device pair
-    (run_tensors' epilogue: the transformed cloud is a new device tensor).  eval_d: the pair's evaluate_distance (None: off)."""
+def _result(p, r, return_transformed) -> BatchResult:
+    """SimpleICP.run's epilogue for the prepared member p and its BatchRun r: what run() returns, or the exception it raises (for a
+    device pair run_tensors' epilogue: the transformed cloud is a new device tensor)."""
+    ctx, obs = p.ctx, p.obs
     path = "fallback" if r.path == _lib.BATCH_PATH_FALLBACK else "batched"
     whole = r.results
     if r.status != _lib.OK:
@@ -211,24 +211,23 @@ def _result(ctx, pc2, msel, obs, ow, r, return_transformed, dev=None, eval_d=Non
             err = _lib.BackendError(r.error, r.status)
             err.results = whole
         last = whole[-1] if whole else None
-        return BatchResult(iterations=len(whole), n_kept=int(last.n_kept) if last else 0, error=err, path=path)
+        return BatchResult(iterations=len(whole), n_kept=int(last.n_kept) if last else 0, error=err, path=path, outlier=p.outlier)
     R = whole[-1] if whole else None
     H, x_start, x = H_from_params(obs), None, None
     if R is not None:
         x_start = np.array(whole[-2].x[:]) if len(whole) > 1 else obs.copy()
         x = np.array(R.x[:])
         H = np.array(R.H[:]).reshape(4, 4)
-    rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
+    rbp, residuals = _rbp_and_residuals(ctx, R, obs, p.ow, x_start, x)
     # (before the movable slot is uploaded again / transformed below: both clouds are as the loop left them)
-    ev = evaluation.after_run(ctx, H, eval_d) if eval_d is not None else None
+    ev = evaluation.after_run(ctx, H, p.evaluate) if p.evaluate is not None else None
     X_new = None
-    if return_transformed and dev is not None:
+    if return_transformed and p.dev is not None:
         from . import tensors
-        X_new = tensors.transformed(ctx, dev[0], H)
+        X_new = tensors.transformed(ctx, p.dev[0], H)
     elif return_transformed:
-        if msel is not None:
-            pc2._upload(ctx, _lib.MOV)
+        if p.msel is not None:
+            p.pc2._upload(ctx, _lib.MOV)
         ctx.transform(_lib.MOV, H)
         X_new, _ = ctx.download_both(_lib.MOV)     # (through the lean contexts' shared pinned ring, like run()'s download)
-    return BatchResult(H, X_new, rbp, residuals, iterations=len(whole), n_kept=int(R.n_kept) if R else 0,
-                       res_mean=R.res_mean if R else np.nan, res_std=R.res_std if R else np.nan, path=path, evaluation=ev)
+    return BatchResult.of_run((H, X_new, rbp, residuals), R, len(whole), path, ev, p.outlier)

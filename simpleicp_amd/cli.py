@@ -48,14 +48,14 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     from . import PointCloud, SimpleICP, SimpleICPException, io
     from ._lib import BackendError
+    from .icp import EXTRA_DEFAULTS
     try:
         X_fix = io.read_xyz(args.fixed)
         X_mov = io.read_xyz(args.movable)
         icp = SimpleICP(verbose=not args.quiet)
-        icp.voxel_size = args.voxel_size
-        icp.evaluate_distance = args.evaluate_distance
-        icp.outlier_neighbors = args.outlier_neighbors
-        icp.outlier_std_ratio = args.outlier_std_ratio
+        for name in EXTRA_DEFAULTS:                      # (the options that have a switch here: their attributes are named alike)
+            if hasattr(args, name):
+                setattr(icp, name, getattr(args, name))
         icp.add_point_clouds(PointCloud(X_fix, columns=["x", "y", "z"]), PointCloud(X_mov, columns=["x", "y", "z"]))
         H, X_out, _, _ = icp.run(
             correspondences=args.correspondences, neighbors=args.neighbors, min_planarity=args.min_planarity,

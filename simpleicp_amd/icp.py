@@ -16,10 +16,13 @@ Differences by design (documented in DESIGN.md):
 """
 from __future__ import annotations
 
+import inspect
 import logging
 import math
+import os
 import time
-from dataclasses import fields
+from collections import namedtuple
+from dataclasses import dataclass, fields
 from pathlib import Path
 from typing import Optional, Tuple
 
@@ -32,6 +35,11 @@ from .rbp import H_from_params, RigidBodyParameters
 _log = logging.getLogger(__name__)
 _PKG_LOG = logging.getLogger(__package__)
 _ATTRS = ("nx", "ny", "nz", "planarity")
+
+# the options that are not run()'s arguments (its signature is the reference's): SimpleICP's attributes of these names, keywords of
+# run_batch / run_tensors and keys of the per_pair dicts, with the values those keywords default to
+EXTRA_DEFAULTS = {"max_normal_angle": None, "voxel_size": None, "voxel_origin": None, "evaluate_distance": None,
+                  "outlier_neighbors": None, "outlier_std_ratio": 2.0}
 
 
 class SimpleICPException(Exception):
@@ -120,30 +128,73 @@ def _check_outlier_size(outlier, n_fix):
         raise SimpleICPException(f"outlier_neighbors ({outlier[0]}) exceeds the number of points of the fixed point cloud ({n_fix}).")
 
 
-def _need_outlier_backend(ctx, outlier):
-    if outlier is not None and not hasattr(ctx, "outlier_statistical"):
-        raise _lib.BackendError("this backend has no outlier removal")
+@dataclass(frozen=True)
+class RunExtras:
+    """The checked values of the options of EXTRA_DEFAULTS: what a run gets besides run()'s arguments, on every road."""
+    max_normal_angle: Optional[float] = None
+    cos_max: Optional[float] = None           # of max_normal_angle, contract (N); None = no such rejection
+    voxel: Optional[tuple] = None             # (cell, origin) of contract (V); None = no voxel selection
+    evaluate: Optional[float] = None          # the search bound of contract (E); None = no evaluation
+    outlier: Optional[tuple] = None           # (k, std_ratio) of contract (O); None = no outlier removal
+
+    @classmethod
+    def checked(cls, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None, outlier_neighbors=None,
+                outlier_std_ratio=2.0):
+        """From the raw values (the names of EXTRA_DEFAULTS).  Of several bad ones the first in this order is reported: the angle,
+        the voxels, the evaluation, the outliers."""
+        return cls(max_normal_angle, _cos_of_max_angle(max_normal_angle), _voxel_of(voxel_size, voxel_origin),
+                   _evaluate_distance_of(evaluate_distance), _outlier_of(outlier_neighbors, outlier_std_ratio))
+
+    def check_fixed_size(self, n_fix):
+        _check_outlier_size(self.outlier, n_fix)
+
+    def refuse_sharded(self):
+        """In a torch.distributed job none of the three runs."""
+        for on, name, instead in ((self.voxel, "voxel_size", "thin the clouds with one process first"),
+                                  (self.outlier, "outlier_neighbors", "thin the clouds with one process first"),
+                                  (self.evaluate, "evaluate_distance", "score the result with one process")):
+            if on is not None:
+                raise SimpleICPException(f"{name} does not run in a torch.distributed job: {instead}")
+
+    def need_backend(self, ctx):
+        """A backend (a stand-in) without the entry point of an option that is on is an error, never a run without the option.
+        (The rejection by the angle between normals is refused where it is set: _set_normal_angle.)"""
+        for on, entry, what in ((self.voxel, "voxel_select", "voxel selection"), (self.outlier, "outlier_statistical", "outlier removal")):
+            if on is not None and not hasattr(ctx, entry):
+                raise _lib.BackendError(f"this backend has no {what}")
+        if self.evaluate is not None:
+            evaluation.need_backend(ctx)
+
+
+def _start_pose(kw):
+    """(obs, ow, H): the observed parameter values in radians, their weights, and the pose the run starts from."""
+    obs = np.array(kw.rbp_observed_values, dtype=float)
+    obs[:3] = obs[:3] * np.pi / 180                       # degree -> rad (simpleicp.py:146-148)
+    ow = np.array(kw.rbp_observation_weights, dtype=float)
+    return obs, ow, H_from_params(obs)
+
+
+def _movable_rows(pc2):
+    """(msel, n_search): the rows of the movable cloud that are searched (None: all of them) and their number.  CorrPts.match
+    searches pc2.X_selected only and maps the hits through pc2.idx_selected (corrpts.py:131-135); a movable cloud with a partial
+    `selected` mask (e.g. the fixed cloud of an earlier run) is uploaded as that subset, after the overlap pre-pass, which looks at
+    ALL its points (simpleicp.py:157: pc2.X)."""
+    partial = not bool(pc2["selected"].to_numpy().all())
+    msel = pc2.idx_selected if partial else None
+    if partial and not len(msel):
+        raise SimpleICPException("The movable point cloud has no selected points.")
+    return msel, (len(msel) if partial else pc2.num_points)
 
 
 def _stats_dict(st):
     return st.as_dict() if hasattr(st, "as_dict") else dict(st)
 
 
-def _log_outliers(info, st):
-    info(f"Remove statistical outliers ... kept {st['n_kept']} of {st['n_candidates']} points "
-         f"(mean {st['mean']:.5f}, std {st['std']:.5f}, threshold {st['threshold']:.5f})")
-
-
-def _need_voxel_backend(ctx, voxel):
-    if voxel is not None and not hasattr(ctx, "voxel_select"):
-        raise _lib.BackendError("this backend has no voxel selection")
-
-
-def _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle):
-    """The context's normal-angle setting for the run about to start -- set on every run, off included, so that a pooled context
-    never inherits it --, with pc2's own nx, ny, nz columns when it has them (of the selected subset when pc2 is partially selected;
-    without them the normals are estimated on the device among the points of the movable slot, i.e. of that subset)."""
-    cos_max = _cos_of_max_angle(max_normal_angle)
+def _set_normal_angle(ctx, cos_max, neighbors, pc2=None, msel=None, n_search=0):
+    """The context's normal-angle setting for the run about to start -- set on every run, off (cos_max None) included, so that a
+    pooled context never inherits it --, with pc2's own nx, ny, nz columns when it has them (of the selected subset when pc2 is
+    partially selected; without them the normals are estimated on the device among the points of the movable slot, i.e. of that
+    subset)."""
     if not hasattr(ctx, "normal_angle_set"):
         # (a stand-in backend that predates the setting has nothing to switch off; asked to switch it on, it cannot)
         if cos_max is not None:
@@ -155,120 +206,151 @@ def _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle):
     ctx.normal_angle_set(cos_max, neighbors)
 
 
-def _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors, max_overlap_distance,
-                      info=None, max_normal_angle=None, voxel=None, outlier=None, outlier_stats=None):
-    """What a run does between the uploads and its first iteration (shared by SimpleICP.run and run_batch): overlap pre-pass
-    under the initial H, statistical outlier removal (outlier: (k, std_ratio) or None; its statistics go into the dict
-    outlier_stats), one point per voxel (voxel: (cell, origin) or None), select_n_points, normals (or pc1's nx, ny, nz,
-    planarity columns), the movable cloud's selected subset and its planarity column, sicp_icp_setup.  Returns the selected rows of pc1.  info: where the progress lines go (the log)."""
-    info = info or _log.info
-    _need_voxel_backend(ctx, voxel)
-    _need_outlier_backend(ctx, outlier)
-    if np.isfinite(max_overlap_distance):
-        info("Consider partial overlap of point clouds ...")
-        if sel is _ALL or len(sel):
-            # both clouds are resident already: only the verdicts cross the host link
-            near = ctx.select_in_range(_lib.FIX, _lib.MOV, None if sel is _ALL else sel, H, float(max_overlap_distance))
-            sel = pc1._keep_selected(sel, near)
-        if not len(sel) > 0:
-            raise _no_overlap(max_overlap_distance)
+class _HostSelection:
+    """The fixed cloud's selection of a pair of PointClouds, for _prepare: pc1's `selected` column, carried along as ``sel``
+    (_ALL or an index array: every pass over the mask is a pass over N_f).  msel, n_search: _movable_rows(pc2).
+    upload_movable(rows): how a sharded run uploads the movable cloud's subset (None: one GPU, the whole subset)."""
 
-    if outlier is not None:
+    def __init__(self, ctx, pc1, pc2, msel, n_search, upload_movable=None):
+        self.ctx, self.pc1, self.pc2, self.msel, self.n_search = ctx, pc1, pc2, msel, n_search
+        self.upload_movable = upload_movable or (lambda rows: pc2._upload(ctx, _lib.MOV, rows=rows))
+        self.sel = pc1._selection()
+
+    def _rows(self):
+        return None if self.sel is _ALL else self.sel
+
+    def is_empty(self):
+        return not (self.sel is _ALL or len(self.sel) > 0)
+
+    def overlap(self, H, d):
+        if not self.is_empty():
+            # both clouds are resident already: only the verdicts cross the host link
+            self.sel = self.pc1._keep_selected(self.sel, self.ctx.select_in_range(_lib.FIX, _lib.MOV, self._rows(), H, d))
+
+    def outliers(self, k, std_ratio):
+        keep, _, st = self.ctx.outlier_statistical(_lib.FIX, k, std_ratio, rows=self._rows())
+        self.sel = self.pc1._keep_selected(self.sel, keep)
+        return st
+
+    def voxels(self, cell, origin):
+        if not self.is_empty():
+            self.sel = self.pc1._keep_selected(self.sel, self.ctx.voxel_select(_lib.FIX, cell, origin, self._rows()))
+
+    def pick_and_setup(self, kw, extras, info):
+        ctx, pc1, pc2, msel = self.ctx, self.pc1, self.pc2, self.msel
+        info("Select points for correspondences in fixed point cloud ...")
+        sel = self.sel = pc1.select_n_points(kw.correspondences, _cur=self.sel)
+        # (simpleicp.py:174,254 save and restore pc1's selection around every iteration because the
+        # reference's rejections edit it; here the masks live on the device and pc1 is never touched)
+        if not set(_ATTRS).issubset(pc1.columns):
+            info("Estimate normals of selected points ...")
+            pc1.estimate_normals(kw.neighbors, _ctx=ctx, _uploaded=True, _sel=sel)
+        normals, planarity = pc1._attributes_of(sel)
+        ctx.upload_wait(_lib.MOV)                # (the movable cloud's verdict -- a non-finite coordinate -- is raised here)
+        if msel is not None:
+            self.upload_movable(msel)            # from here on the searched cloud is pc2's selected subset
+        if "planarity" in pc2.columns:
+            # reject_wrt_planarity tests pc2's column as well when it exists (corrpts.py:158-163; NaN fails)
+            rows, vals = pc2._planarity_pairs(msel)
+            ctx.set_planarity(_lib.MOV, vals, rows=rows, n_global=self.n_search)
+        _set_normal_angle(ctx, extras.cos_max, kw.neighbors, pc2, msel, self.n_search)
+        ctx.icp_setup(sel, normals, planarity)
+
+
+class _DeviceSelection:
+    """The fixed cloud's selection of a pair uploaded from device memory (run_tensors, run_batch's device pairs; every point
+    selected to start with, no normals or planarity columns), for _prepare: a u8 mask in device memory (none: every point), so
+    that every array the steps hand on stays there -- the overlap verdicts, the kept rows and the picks of select_n_points
+    (sicp_select_n_device), the normals.  alloc(shape, kind) returns a device buffer (kind "u8" / "i64" / "f32") and its address;
+    the buffers of the pick are kept in ``scratch``, which must outlive the run's sicp_icp_setup."""
+
+    def __init__(self, ctx, n_fix, alloc):
+        self.ctx, self.n_fix, self.alloc = ctx, n_fix, alloc
+        self.mask = self.mask_p = self.scratch = None
+
+    def _new_mask(self):
+        self.mask, self.mask_p = self.alloc((self.n_fix,), "u8")
+        return self.mask_p
+
+    def is_empty(self):
+        return False                  # (not known on the host before the pick: pick_and_setup tells)
+
+    def overlap(self, H, d):
+        self.ctx.select_in_range_into(_lib.FIX, _lib.MOV, H, d, self._new_mask())
+
+    def outliers(self, k, std_ratio):
+        if self.mask is None:
+            return self.ctx.outlier_statistical(_lib.FIX, k, std_ratio, keep_ptr=self._new_mask())
+        return self.ctx.outlier_statistical(_lib.FIX, k, std_ratio, mask_ptr=self.mask_p, keep_ptr=self.mask_p)   # (the verdicts replace the mask)
+
+    def voxels(self, cell, origin):
+        if self.mask is None:
+            self.ctx.voxel_select(_lib.FIX, cell, origin, keep_ptr=self._new_mask())
+        else:
+            self.ctx.voxel_select_masked(_lib.FIX, self.mask_p, self.n_fix, cell, origin)      # (the verdicts replace the mask)
+
+    def pick_and_setup(self, kw, extras, info):
+        ctx, alloc = self.ctx, self.alloc
+        sel, sel_p = alloc((max(int(kw.correspondences), 1),), "i64")
+        Q = ctx.select_n_device(self.mask_p, self.n_fix, int(kw.correspondences), sel_p)
+        if self.mask is not None and Q == 0:
+            raise _no_overlap(kw.max_overlap_distance)
+        info("Select points for correspondences in fixed point cloud ...")
+        info("Estimate normals of selected points ...")
+        nv, nv_p = alloc((Q, 3), "f32")
+        pl, pl_p = alloc((Q,), "f32")
+        ctx.estimate_normals_into(_lib.FIX, sel_p, Q, int(kw.neighbors), nv_p, pl_p)
+        _set_normal_angle(ctx, extras.cos_max, kw.neighbors)
+        ctx.icp_setup_device(sel_p, Q, nv_p, pl_p)
+        self.mask = self.mask_p = None            # (every call returned complete: nothing reads the mask any more)
+        self.scratch = (sel, nv, pl)
+
+
+def _prepare(selection, kw, extras, H, info=None):
+    """What a run does between the uploads and its first iteration, on every road (SimpleICP.run, run_batch, run_tensors), in this
+    order: overlap pre-pass under the initial H, statistical outlier removal, one point per voxel, select_n_points, normals,
+    the normal-angle setting, sicp_icp_setup -- the last four behind selection.pick_and_setup.  selection: a _HostSelection or a
+    _DeviceSelection; info: where the progress lines go (the log).  Returns the statistics of the outlier removal (None: off)."""
+    info = info or _log.info
+    extras.need_backend(selection.ctx)
+    bounded = np.isfinite(kw.max_overlap_distance)
+    if bounded:
+        info("Consider partial overlap of point clouds ...")
+        selection.overlap(H, float(kw.max_overlap_distance))
+        if selection.is_empty():
+            raise _no_overlap(kw.max_overlap_distance)
+    stats = None
+    if extras.outlier is not None:
         # after the overlap pre-pass (only points that can take part are judged), before the voxel step (a voxel's representative
         # is then always an inlier); the neighbours are searched among ALL points of the fixed cloud
-        if not (sel is _ALL or len(sel)):
+        if selection.is_empty():
             raise SimpleICPException("The fixed point cloud has no selected points left for the outlier removal.")
-        keep, _, st = ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], rows=None if sel is _ALL else sel)
-        st = _stats_dict(st)
-        _log_outliers(info, st)
-        if outlier_stats is not None:
-            outlier_stats.update(st)
-        sel = pc1._keep_selected(sel, keep)
-
-    if voxel is not None:
+        stats = _stats_dict(selection.outliers(*extras.outlier))
+        info(f"Remove statistical outliers ... kept {stats['n_kept']} of {stats['n_candidates']} points "
+             f"(mean {stats['mean']:.5f}, std {stats['std']:.5f}, threshold {stats['threshold']:.5f})")
+    if extras.voxel is not None:
         # after the overlap pre-pass, so that a voxel's representative always lies inside the overlap
         info("Keep one point per voxel ...")
-        if sel is _ALL or len(sel):
-            keep = ctx.voxel_select(_lib.FIX, voxel[0], voxel[1], None if sel is _ALL else sel)
-            sel = pc1._keep_selected(sel, keep)
-        if not len(sel) > 0:
+        selection.voxels(*extras.voxel)
+        if selection.is_empty():
             # (reachable only with no selected point to start from; the exception an empty overlap raises, with words of its own)
-            if np.isfinite(max_overlap_distance):
-                raise _no_overlap(max_overlap_distance)
+            if bounded:
+                raise _no_overlap(kw.max_overlap_distance)
             raise SimpleICPException("The fixed point cloud has no selected points left for the voxel selection.")
-
-    info("Select points for correspondences in fixed point cloud ...")
-    sel = pc1.select_n_points(correspondences, _cur=sel)
-    # (simpleicp.py:174,254 save and restore pc1's selection around every iteration because the
-    # reference's rejections edit it; here the masks live on the device and pc1 is never touched)
-
-    if not set(_ATTRS).issubset(pc1.columns):
-        info("Estimate normals of selected points ...")
-        pc1.estimate_normals(neighbors, _ctx=ctx, _uploaded=True, _sel=sel)
-    normals, planarity = pc1._attributes_of(sel)
-    ctx.upload_wait(_lib.MOV)                # (the movable cloud's verdict -- a non-finite coordinate -- is raised here)
-    if msel is not None:
-        upload_movable(msel)                 # from here on the searched cloud is pc2's selected subset
-    if "planarity" in pc2.columns:
-        # reject_wrt_planarity tests pc2's column as well when it exists (corrpts.py:158-163; NaN fails)
-        rows, vals = pc2._planarity_pairs(msel)
-        ctx.set_planarity(_lib.MOV, vals, rows=rows, n_global=n_search)
-    _set_normal_angle(ctx, pc2, msel, n_search, neighbors, max_normal_angle)
-    ctx.icp_setup(sel, normals, planarity)
-    return sel
+    # The two roads differ from here on, and each keeps its ways.  The host road knows above whether anything is left (with words
+    # of its own where no overlap bound is to blame) and logs "Select points ..." before it picks.  The device road learns the
+    # count only from its pick: whatever emptied the mask, it raises _no_overlap then, and logs "Select points ..." after it.
+    selection.pick_and_setup(kw, extras, info)
+    return stats
 
 
-def _select_and_setup_device(ctx, n_fix, H, correspondences, neighbors, max_overlap_distance, alloc, info=None, max_normal_angle=None,
-                             voxel=None, outlier=None, outlier_stats=None):
-    """_select_and_setup for clouds uploaded from device memory (run_tensors, run_batch's device pairs; every point selected, no
-    normals or planarity columns): the same steps with every array they hand on left in device memory -- the overlap verdicts, the
-    kept rows and the picks of select_n_points (sicp_select_n_device), the normals.  alloc(shape, kind) returns a device buffer
-    (kind "u8" / "i64" / "f32") and its address; the buffers are returned and must outlive the run's sicp_icp_setup."""
-    info = info or _log.info
-    _need_voxel_backend(ctx, voxel)
-    _need_outlier_backend(ctx, outlier)
-    mask = mask_p = None
-    if np.isfinite(max_overlap_distance):
-        info("Consider partial overlap of point clouds ...")
-        mask, mask_p = alloc((n_fix,), "u8")
-        ctx.select_in_range_into(_lib.FIX, _lib.MOV, H, float(max_overlap_distance), mask_p)
-    if outlier is not None:
-        if mask is None:
-            mask, mask_p = alloc((n_fix,), "u8")
-            st = ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], keep_ptr=mask_p)
-        else:
-            st = ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], mask_ptr=mask_p, keep_ptr=mask_p)   # (the verdicts replace the mask)
-        st = _stats_dict(st)
-        _log_outliers(info, st)
-        if outlier_stats is not None:
-            outlier_stats.update(st)
-    if voxel is not None:
-        info("Keep one point per voxel ...")
-        if mask is None:
-            mask, mask_p = alloc((n_fix,), "u8")
-            ctx.voxel_select(_lib.FIX, voxel[0], voxel[1], keep_ptr=mask_p)
-        else:
-            ctx.voxel_select_masked(_lib.FIX, mask_p, n_fix, voxel[0], voxel[1])      # (the verdicts replace the mask)
-    sel, sel_p = alloc((max(int(correspondences), 1),), "i64")
-    Q = ctx.select_n_device(mask_p, n_fix, int(correspondences), sel_p)
-    if mask is not None and Q == 0:
-        raise _no_overlap(max_overlap_distance)
-    info("Select points for correspondences in fixed point cloud ...")
-    info("Estimate normals of selected points ...")
-    nv, nv_p = alloc((Q, 3), "f32")
-    pl, pl_p = alloc((Q,), "f32")
-    ctx.estimate_normals_into(_lib.FIX, sel_p, Q, int(neighbors), nv_p, pl_p)
-    _set_normal_angle(ctx, None, None, 0, neighbors, max_normal_angle)
-    ctx.icp_setup_device(sel_p, Q, nv_p, pl_p)
-    return sel, nv, pl
-
-
-def _iterate(ctx, obs, ow, H, min_planarity, distance_weights, max_iterations, min_change, hooks=None):
-    """The iterations of a run after sicp_icp_setup, with run()'s log lines.  hooks None: ONE sicp_icp_run (same convergence test)
+def _iterate(ctx, obs, ow, H, kw, hooks=None):
+    """The iterations of a run (kw: its RunKeywords) after sicp_icp_setup, with run()'s log lines.  hooks None: ONE sicp_icp_run (same convergence test)
     whose records are replayed; (before(it, H), after(it, H)): a debug run, one ABI call per iteration with the hooks around it.
     Returns (R, x_start, x, H, stats, it) of the last iteration (R None when none ran)."""
     x = obs.copy()
-    w = distance_weights
+    min_planarity, max_iterations, min_change = kw.min_planarity, kw.max_iterations, kw.min_change
+    w = kw.distance_weights
     stats = []            # (n, mean, std) of the residuals per iteration
     R = None
     x_start = None
@@ -396,51 +478,32 @@ class SimpleICP:
     ) -> Tuple[np.ndarray, np.ndarray, RigidBodyParameters, np.ndarray]:
         """See the reference docstring (simpleicp.py:88-133): identical arguments/returns.
         Returns (H, X_mov_transformed, rbp, distance_residuals)."""
-        self._check_arguments(distance_weights, rbp_observed_values, rbp_observation_weights)
-        _cos_of_max_angle(self.max_normal_angle)
-        voxel = _voxel_of(self.voxel_size, self.voxel_origin)
-        eval_d = _evaluate_distance_of(self.evaluate_distance)
-        outlier = _outlier_of(self.outlier_neighbors, self.outlier_std_ratio)
+        kw = RunKeywords(correspondences, neighbors, min_planarity, max_overlap_distance, min_change, max_iterations,
+                         distance_weights, rbp_observed_values, rbp_observation_weights, debug_dirpath)
+        kw.check()
+        extras = RunExtras.checked(**{name: getattr(self, name) for name in EXTRA_DEFAULTS})
         t_start = time.time()
         pc1, pc2 = self.pc1, self.pc2
-        _check_outlier_size(outlier, pc1.num_points)
+        extras.check_fixed_size(pc1.num_points)
         ctx = backend.get_context()
         ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
-        import os
         sharded = dist.is_distributed() or (os.environ.get("SICP_FORCE_EXCHANGE") == "1" and dist.is_initialized())
-        if sharded and voxel is not None:
-            raise SimpleICPException("voxel_size does not run in a torch.distributed job: thin the clouds with one process first")
-        _need_voxel_backend(ctx, voxel)
-        if sharded and outlier is not None:
-            raise SimpleICPException("outlier_neighbors does not run in a torch.distributed job: thin the clouds with one process first")
-        _need_outlier_backend(ctx, outlier)
-        if eval_d is not None:
-            if sharded:
-                raise SimpleICPException("evaluate_distance does not run in a torch.distributed job: score the result with one process")
-            evaluation.need_backend(ctx)
+        if sharded:
+            extras.refuse_sharded()
+        extras.need_backend(ctx)
         self.evaluation = None
 
         if debug_dirpath:
             _log.info(f'Write debug files to directory "{debug_dirpath}"')
             Path(debug_dirpath).mkdir(parents=True, exist_ok=True)
 
-        obs = np.array(rbp_observed_values, dtype=float)
-        obs[:3] = obs[:3] * np.pi / 180                       # degree -> rad (simpleicp.py:146-148)
-        ow = np.array(rbp_observation_weights, dtype=float)
-        H = H_from_params(obs)
+        pose = _start_pose(kw)
 
         # both clouds go to HBM once and stay there (straight from the frames' storage: no host gather).  One process: each travels
         # on the library's helper thread (a stream of its own) while this thread does what needs no device -- the masks -- and, behind
         # the movable cloud's upload, the fixed cloud's grid and normals; the first call that names a slot waits for its upload
         pc1._upload(ctx, _lib.FIX, background=not sharded)
-        # CorrPts.match searches pc2.X_selected only and maps the hits through pc2.idx_selected (corrpts.py:131-135);
-        # a movable cloud with a partial `selected` mask (e.g. the fixed cloud of an earlier run) is uploaded as
-        # that subset, after the overlap pre-pass, which looks at ALL its points (simpleicp.py:157: pc2.X)
-        partial = not bool(pc2["selected"].to_numpy().all())
-        msel = pc2.idx_selected if partial else None
-        if partial and not len(msel):
-            raise SimpleICPException("The movable point cloud has no selected points.")
-        n_search = len(msel) if partial else pc2.num_points
+        msel, n_search = _movable_rows(pc2)
         rank, world = dist.rank_world() if sharded else (0, 1)
 
         # what the ranks shard (DESIGN section 6): index ranges of the movable cloud by default; the QUERIES (cloud
@@ -460,7 +523,7 @@ class SimpleICP:
             lo, hi = (0, n) if qshard else dist.shard_bounds(n, rank, world)
             pc2._upload(ctx, _lib.MOV, lo, hi, index_base=lo, rows=rows)
 
-        sel0 = pc1._selection()           # carried along (_ALL or indices): every pass over the mask is a pass over N_f
+        selection = _HostSelection(ctx, pc1, pc2, msel, n_search, upload_movable)
         if sharded:
             upload_movable()
         else:
@@ -475,9 +538,7 @@ class SimpleICP:
         else:
             dist.detach(ctx)
         try:
-            return self._run_uploaded(ctx, sharded, msel, n_search, upload_movable, sel0, t_start, obs, ow, H,
-                                      correspondences, neighbors, min_planarity, max_overlap_distance, min_change,
-                                      max_iterations, distance_weights, debug_dirpath, voxel, eval_d, outlier)
+            return self._run_uploaded(selection, kw, extras, pose, sharded, t_start)
         except BaseException:
             # ANY way out of a sharded run that is not its normal end (a backend error, a host-side exception between two
             # collectives, KeyboardInterrupt, MemoryError) may leave this rank out of step with its peers: never revive the
@@ -490,17 +551,14 @@ class SimpleICP:
             # collective the other ranks never join
             dist.detach(ctx)
 
-    def _run_uploaded(self, ctx, sharded, msel, n_search, upload_movable, sel, t_start, obs, ow, H, correspondences, neighbors,
-                      min_planarity, max_overlap_distance, min_change, max_iterations, distance_weights, debug_dirpath, voxel=None,
-                      eval_d=None, outlier=None):
-        pc1, pc2 = self.pc1, self.pc2
-        outlier_stats = {}
+    def _run_uploaded(self, selection, kw, extras, pose, sharded, t_start):
+        ctx, pc1, pc2, msel = selection.ctx, self.pc1, self.pc2, selection.msel
+        obs, ow, H = pose
+        debug_dirpath = kw.debug_dirpath
         if debug_dirpath:
             X_fix, X_mov = pc1.X, pc2.X
 
-        sel = _select_and_setup(ctx, pc1, pc2, msel, n_search, upload_movable, sel, H, correspondences, neighbors,
-                                max_overlap_distance, max_normal_angle=self.max_normal_angle, voxel=voxel, outlier=outlier,
-                                outlier_stats=outlier_stats)
+        outlier_stats = _prepare(selection, kw, extras, H)
 
         hooks = None
         if debug_dirpath:
@@ -511,17 +569,17 @@ class SimpleICP:
 
             def after(it, H):
                 self._write_correspondences(ctx, Path(debug_dirpath).joinpath(
-                    f"iteration{it:03d}_preoptim_correspondences.xyz"), X_fix, X_mov if msel is None else X_mov[msel], sel, H)
+                    f"iteration{it:03d}_preoptim_correspondences.xyz"), X_fix, X_mov if msel is None else X_mov[msel], selection.sel, H)
             hooks = (before, after)
-        R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, min_planarity, distance_weights, max_iterations, min_change, hooks)
+        R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, kw, hooks)
         rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
         # (read before the final transform of the movable slot, which empties the cache of estimated normals)
         angle_info = ctx.normal_angle_info() if hasattr(ctx, "normal_angle_info") else {}
 
         self._log_result(H, rbp)
-        if eval_d is not None:
+        if extras.evaluate is not None:
             # (before the movable slot is uploaded again / transformed below: both clouds are as the loop left them)
-            self.evaluation = evaluation.after_run(ctx, H, eval_d, _log.info)
+            self.evaluation = evaluation.after_run(ctx, H, extras.evaluate, _log.info)
 
         # final transformation of the caller's movable cloud (simpleicp.py:316): all of its points
         if sharded or msel is not None:
@@ -532,9 +590,9 @@ class SimpleICP:
 
         self.last_run_info = {"iterations": it + 1, "stats": stats, "seconds": time.time() - t_start, **getattr(self, "_job", {})}
         self.last_run_info.update(angle_info)
-        if eval_d is not None:
+        if extras.evaluate is not None:
             self.last_run_info["evaluation"] = self.evaluation
-        if outlier is not None:
+        if outlier_stats is not None:
             self.last_run_info["outlier"] = outlier_stats
         if sharded:
             # how the shards' winners met: "records_allgather" / "key_allreduces" (cloud shards) / "query_slices", and how often
@@ -593,3 +651,10 @@ class SimpleICP:
             raise SimpleICPException("All elements of rbp_observation_weights must be >= 0.")
         if not any(np.isfinite(rbp_observation_weights)):
             raise SimpleICPException("At least one element in rbp_observation_weights must be finite.")
+
+
+class RunKeywords(namedtuple("RunKeywords", [name for name in inspect.signature(SimpleICP.run).parameters if name != "self"])):
+    """run()'s arguments as one record: run() fills it from its parameters, run_batch and run_tensors from their keywords."""
+
+    def check(self):
+        SimpleICP._check_arguments(self.distance_weights, self.rbp_observed_values, self.rbp_observation_weights)

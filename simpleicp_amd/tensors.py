@@ -24,9 +24,7 @@ import numpy as np
 
 from . import _lib, backend, dist
 from . import evaluation
-from .icp import (SimpleICP, SimpleICPException, _cos_of_max_angle, _evaluate_distance_of, _iterate, _rbp_and_residuals,
-                  _check_outlier_size, _outlier_of, _select_and_setup_device, _voxel_of)
-from .rbp import H_from_params
+from .icp import SimpleICP, SimpleICPException, _DeviceSelection, _iterate, _outlier_of, _prepare, _rbp_and_residuals, _start_pose, _voxel_of
 
 _log = logging.getLogger(__name__)
 
@@ -36,26 +34,6 @@ _KINDS = {"u8": "uint8", "i64": "int64", "f32": "float32"}
 def _is_device_tensor(c) -> bool:
     """A CUDA torch tensor (told without importing torch: a process that never imported it holds none)."""
     return type(c).__module__.startswith("torch") and bool(getattr(c, "is_cuda", False))
-
-
-def _checked_kwargs(run_kwargs, who, max_normal_angle=None, voxel_size=None, voxel_origin=None, evaluate_distance=None,
-                    outlier_neighbors=None, outlier_std_ratio=2.0):
-    """run()'s keyword arguments with run()'s defaults, refused as run() / run_batch refuse them."""
-    from .batch import _RUN_DEFAULTS
-    unknown = set(run_kwargs) - set(_RUN_DEFAULTS)
-    if unknown:
-        raise TypeError(f"{who} got unexpected keyword argument(s) {sorted(unknown)}")
-    kw = dict(_RUN_DEFAULTS)
-    kw.update(run_kwargs)
-    if kw["debug_dirpath"]:
-        raise SimpleICPException(f"{who} writes no debug files (debug_dirpath): run that pair with SimpleICP.run")
-    SimpleICP._check_arguments(kw["distance_weights"], kw["rbp_observed_values"], kw["rbp_observation_weights"])
-    _cos_of_max_angle(max_normal_angle)
-    kw["max_normal_angle"] = max_normal_angle
-    kw["voxel"] = _voxel_of(voxel_size, voxel_origin)
-    kw["evaluate"] = _evaluate_distance_of(evaluate_distance)
-    kw["outlier"] = _outlier_of(outlier_neighbors, outlier_std_ratio)
-    return kw
 
 
 def _check_cloud(name, t, device):
@@ -79,14 +57,12 @@ def _upload(ctx, slot, t):
     ctx.upload_strided(slot, t.data_ptr(), dt, t.shape[0], t.stride(0), t.stride(1))
 
 
-def prepare(ctx, X_fix, X_mov, kw, info):
-    """What a run does up to its first iteration, for a device pair on ctx: the stream wait, both uploads, the device road of
-    _select_and_setup.  Returns (obs, ow, H, scratch) -- scratch: device buffers that must live until the run is over."""
+def prepare(ctx, X_fix, X_mov, kw, extras, info):
+    """What a run (kw: its RunKeywords, extras: its RunExtras) does up to its first iteration, for a device pair on ctx: the stream
+    wait, both uploads, _prepare on a _DeviceSelection.  Returns ((obs, ow, H), the statistics of the outlier removal or None,
+    scratch) -- scratch: device buffers that must live until the run is over."""
     import torch
-    obs = np.array(kw["rbp_observed_values"], dtype=float)
-    obs[:3] = obs[:3] * np.pi / 180                       # degree -> rad (simpleicp.py:146-148)
-    ow = np.array(kw["rbp_observation_weights"], dtype=float)
-    H = H_from_params(obs)
+    pose = _start_pose(kw)
     dev = X_fix.device
     # the stream rule: the library's stream waits for torch's current stream before it reads anything
     torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
@@ -97,10 +73,9 @@ def prepare(ctx, X_fix, X_mov, kw, info):
 
     _upload(ctx, _lib.FIX, X_fix)
     _upload(ctx, _lib.MOV, X_mov)
-    scratch = _select_and_setup_device(ctx, X_fix.shape[0], H, kw["correspondences"], kw["neighbors"],
-                                       kw["max_overlap_distance"], alloc, info=info, max_normal_angle=kw.get("max_normal_angle"),
-                                       voxel=kw.get("voxel"), outlier=kw.get("outlier"), outlier_stats=kw.get("outlier_stats"))
-    return obs, ow, H, scratch
+    selection = _DeviceSelection(ctx, X_fix.shape[0], alloc)
+    stats = _prepare(selection, kw, extras, pose[2], info)
+    return pose, stats, selection.scratch
 
 
 def transformed(ctx, X_mov, H):
@@ -125,34 +100,64 @@ def run_tensors(X_fix, X_mov, max_normal_angle=None, voxel_size=None, voxel_orig
     ``outlier_neighbors`` / ``outlier_std_ratio`` (None = off / 2.0): SimpleICP's attributes of those names, applied to the fixed
     cloud on the device (contract (O)); the statistics are the result's ``outlier``.  The movable cloud is thinned by the caller
     (``X_mov[outlier_keep(X_mov, neighbors=20)]``)."""
-    from .batch import BatchResult
+    from .batch import BatchResult, merged_keywords
     t_start = time.time()
-    kw = _checked_kwargs(run_kwargs, "run_tensors", max_normal_angle, voxel_size, voxel_origin, evaluate_distance,
-                         outlier_neighbors, outlier_std_ratio)
-    kw["outlier_stats"] = {}
+    options = dict(max_normal_angle=max_normal_angle, voxel_size=voxel_size, voxel_origin=voxel_origin,
+                   evaluate_distance=evaluate_distance, outlier_neighbors=outlier_neighbors, outlier_std_ratio=outlier_std_ratio)
+    kw, extras = merged_keywords("run_tensors", options, run_kwargs)
     if dist.is_distributed():
         raise SimpleICPException("run_tensors does not run in a torch.distributed job: call SimpleICP.run on each rank instead")
     device = backend.default_device()
     _check_cloud("X_fix", X_fix, device)
     _check_cloud("X_mov", X_mov, device)
-    _check_outlier_size(kw["outlier"], X_fix.shape[0])
+    extras.check_fixed_size(X_fix.shape[0])
     ctx = backend.get_context()
     ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this run)
     dist.detach(ctx)
-    if kw["evaluate"] is not None:
+    # (the evaluation's entry point is asked for before anything is uploaded, the other options' by _prepare)
+    if extras.evaluate is not None:
         evaluation.need_backend(ctx)
-    obs, ow, H, scratch = prepare(ctx, X_fix, X_mov, kw, _log.info)
-    R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, kw["min_planarity"], kw["distance_weights"], kw["max_iterations"],
-                                           kw["min_change"])
+    (obs, ow, H), outlier_stats, scratch = prepare(ctx, X_fix, X_mov, kw, extras, _log.info)
+    R, x_start, x, H, stats, it = _iterate(ctx, obs, ow, H, kw)
     rbp, residuals = _rbp_and_residuals(ctx, R, obs, ow, x_start, x)
     SimpleICP._log_result(H, rbp)
-    ev = evaluation.after_run(ctx, H, kw["evaluate"], _log.info) if kw["evaluate"] is not None else None
+    ev = evaluation.after_run(ctx, H, extras.evaluate, _log.info) if extras.evaluate is not None else None
     X_new = transformed(ctx, X_mov, H)
     del scratch
     _log.info(f"Finished in {time.time() - t_start:.3f} seconds!")
-    return BatchResult(H, X_new, rbp, residuals, iterations=it + 1, n_kept=int(R.n_kept) if R is not None else 0,
-                       res_mean=R.res_mean if R is not None else np.nan, res_std=R.res_std if R is not None else np.nan,
-                       path="device", evaluation=ev, outlier=kw["outlier_stats"] if kw["outlier"] is not None else None)
+    return BatchResult.of_run((H, X_new, rbp, residuals), R, it + 1, "device", ev, outlier_stats)
+
+
+def _keep_opening(who, X, mask, needs=None):
+    """The common opening of voxel_keep and outlier_keep: X and mask checked, X in the library's fixed slot.  Returns (ctx, n, m8,
+    keep) -- the context, the number of points, the mask as contiguous uint8 (None: no mask) and the uint8 tensor (n,) the verdicts
+    go to; ctx None for an empty X, keep is the (empty) result then.  needs: (entry point, what it is in words) the context must
+    have."""
+    import torch
+    if dist.is_distributed():
+        raise SimpleICPException(f"{who} does not run in a torch.distributed job: thin the clouds with one process first")
+    device = backend.default_device()
+    _check_cloud("X", X, device)
+    n = X.shape[0]
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
+            raise TypeError("mask must be a bool or uint8 torch.Tensor of shape (n,)")
+        if mask.device != X.device:
+            raise ValueError(f"mask is on {mask.device}, X on {X.device}")
+    if n == 0:
+        return None, 0, None, torch.zeros(0, dtype=torch.bool, device=X.device)
+    ctx = backend.get_context()
+    ctx._corr_owner = None
+    dist.detach(ctx)
+    if needs is not None and not hasattr(ctx, needs[0]):
+        raise _lib.BackendError(f"this backend has no {needs[1]}")
+    # everything torch has to do for this call -- the contiguous copy of a strided mask -- is queued on its current stream BEFORE
+    # the library's stream is made to wait for that stream: the library never reads a buffer torch is still writing
+    m8 = None if mask is None else mask.contiguous().view(torch.uint8)
+    keep = torch.empty(n, dtype=torch.uint8, device=X.device)
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=X.device).wait_stream(torch.cuda.current_stream(X.device))
+    _upload(ctx, _lib.FIX, X)
+    return ctx, n, m8, keep
 
 
 def voxel_keep(X, voxel_size, origin=None, mask=None):
@@ -163,27 +168,9 @@ def voxel_keep(X, voxel_size, origin=None, mask=None):
     run_tensors'.  ``X[voxel_keep(X, c)]`` is the thinned cloud; the library's fixed slot holds X afterwards."""
     import torch
     voxel = _voxel_of(voxel_size, origin)
-    if dist.is_distributed():
-        raise SimpleICPException("voxel_keep does not run in a torch.distributed job: thin the clouds with one process first")
-    device = backend.default_device()
-    _check_cloud("X", X, device)
-    n = X.shape[0]
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
-            raise TypeError("mask must be a bool or uint8 torch.Tensor of shape (n,)")
-        if mask.device != X.device:
-            raise ValueError(f"mask is on {mask.device}, X on {X.device}")
-    if n == 0:
-        return torch.zeros(0, dtype=torch.bool, device=X.device)
-    ctx = backend.get_context()
-    ctx._corr_owner = None
-    dist.detach(ctx)
-    # everything torch has to do for this call -- the contiguous copy of a strided mask -- is queued on its current stream BEFORE
-    # the library's stream is made to wait for that stream: the library never reads a buffer torch is still writing
-    m8 = None if mask is None else mask.contiguous().view(torch.uint8)
-    keep = torch.empty(n, dtype=torch.uint8, device=X.device)
-    torch.cuda.ExternalStream(ctx.stream_ptr(), device=X.device).wait_stream(torch.cuda.current_stream(X.device))
-    _upload(ctx, _lib.FIX, X)
+    ctx, n, m8, keep = _keep_opening("voxel_keep", X, mask)
+    if ctx is None:
+        return keep
     if m8 is None:
         ctx.voxel_select(_lib.FIX, voxel[0], voxel[1], keep_ptr=keep.data_ptr())
     else:
@@ -221,28 +208,9 @@ def outlier_keep(X, *, neighbors=None, std_ratio=2.0, radius=None, min_points=No
             raise ValueError("radius must be a finite number > 0.")
         if min_points is None or isinstance(min_points, (bool, float, str, bytes)) or int(min_points) != min_points or min_points < 0:
             raise ValueError("min_points must be an integer >= 0.")
-    if dist.is_distributed():
-        raise SimpleICPException("outlier_keep does not run in a torch.distributed job: thin the clouds with one process first")
-    device = backend.default_device()
-    _check_cloud("X", X, device)
-    n = X.shape[0]
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
-            raise TypeError("mask must be a bool or uint8 torch.Tensor of shape (n,)")
-        if mask.device != X.device:
-            raise ValueError(f"mask is on {mask.device}, X on {X.device}")
-    if n == 0:
-        return torch.zeros(0, dtype=torch.bool, device=X.device)
-    ctx = backend.get_context()
-    ctx._corr_owner = None
-    dist.detach(ctx)
-    if not hasattr(ctx, "outlier_statistical"):
-        raise _lib.BackendError("this backend has no outlier removal")
-    # (as in voxel_keep: torch's own work for this call is queued before the library's stream is made to wait for torch's)
-    m8 = None if mask is None else mask.contiguous().view(torch.uint8)
-    keep = torch.empty(n, dtype=torch.uint8, device=X.device)
-    torch.cuda.ExternalStream(ctx.stream_ptr(), device=X.device).wait_stream(torch.cuda.current_stream(X.device))
-    _upload(ctx, _lib.FIX, X)
+    ctx, n, m8, keep = _keep_opening("outlier_keep", X, mask, needs=("outlier_statistical", "outlier removal"))
+    if ctx is None:
+        return keep
     mp = None if m8 is None else m8.data_ptr()
     if neighbors is not None:
         ctx.outlier_statistical(_lib.FIX, outlier[0], outlier[1], mask_ptr=mp, keep_ptr=keep.data_ptr())
