@@ -104,6 +104,72 @@ int check_rows(const int64_t *rows, int64_t m, int64_t n, const char *what)
     return SICP_OK;
 }
 
+// a candidate list handed over the ABI (null: none): its length and its rows
+int check_candidate_rows(const int64_t *rows, int64_t m, int64_t n)
+{
+    if (!rows) return SICP_OK;
+    if (m <= 0 || m >= (1LL << 31)) return fail(SICP_ERR_INVALID, "m must be in [1, 2^31)");
+    return check_rows(rows, m, n, "rows");
+}
+
+// device memory of the ctx's device (a host pointer, managed or foreign memory is refused)
+int check_device_ptr(sicp_ctx *c, const void *p, const char *what)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(SICP_ERR_INVALID, "%s is not device memory (host and managed pointers are refused: host data goes through the entries "
+                                      "that take host pointers)", what);
+    }
+    if (at.device != c->device) return fail(SICP_ERR_INVALID, "%s is memory of device %d, the ctx is on device %d", what, at.device, c->device);
+    return SICP_OK;
+}
+
+int check_no_exchange(const sicp_ctx *c, const char *who, const char *why)
+{
+    if (c->collective()) return fail(SICP_ERR_INVALID, "%s is not supported with an exchange (%s)", who, why);
+    return SICP_OK;
+}
+
+int check_below_2_31(const sicp_ctx *c, int slot, const char *who)
+{
+    if (c->cloud[slot].n >= (1LL << 31)) return fail(SICP_ERR_INVALID, "%s takes clouds of fewer than 2^31 points", who);
+    return SICP_OK;
+}
+
+int check_whole_cloud(const sicp_ctx *c, int slot, const char *who, const char *why)
+{
+    CHK(check_no_exchange(c, who, why));
+    if (c->cloud[slot].idx_base != 0) return fail(SICP_ERR_INVALID, "%s is not supported on a shard (%s)", who, why);
+    return check_below_2_31(c, slot, who);
+}
+
+// the candidates on the device: the list uploaded, or the mask checked and handed to by_mask, or the whole slot; c->cand_small
+// cleared.  The masked form synchronises (its count sizes what follows); K->d_rows is good until the next reserve of c->cand_rows.
+int take_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, MaskPass by_mask, Candidates *K)
+{
+    const long n = (long)c->cloud[slot].n;
+    *K = Candidates();
+    CHK(c->cand_small.reserve(CAND_WORDS));
+    HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+    if (rows) {
+        CHK(c->cand_rows.reserve((size_t)m));
+        HIPCHK(hipMemcpyAsync(c->cand_rows.p, rows, (size_t)m * sizeof(int64_t), hipMemcpyDefault, c->stream));
+        K->d_rows = c->cand_rows.p; K->count = (long)m; K->positions = (long)m;
+    } else if (mask) {
+        CHK(check_device_ptr(c, mask, "mask"));
+        CHK(by_mask(c, mask, n, c->cand_small.p + CAND_COUNT, &K->d_rows));
+        HIPCHK(hipGetLastError());
+        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND) + CAND_COUNT;
+        HIPCHK(hipMemcpyAsync(h, c->cand_small.p + CAND_COUNT, sizeof *h, hipMemcpyDeviceToHost, c->stream));
+        CHK(sync(c));
+        K->d_mask = mask; K->count = (long)*h; K->positions = n; K->by_position = true;
+    } else {
+        K->count = n; K->positions = n;
+    }
+    return SICP_OK;
+}
+
 }  // namespace sicph
 
 namespace sicph {
@@ -235,9 +301,9 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->na.cnt.release(); c->na.list_q.release(); c->na.list_m.release(); c->na.iota.release(); c->na.cov.release(); c->na.per_q.release();
     c->batch_tab.release(); c->batch_map.release();
     c->sel_blk.release(); c->sel_pos.release();
-    c->vx_tab.release(); c->vx_slot.release(); c->vx_rows.release(); c->vx_keep.release(); c->vx_cnt.release();
+    c->vx_tab.release(); c->vx_slot.release(); c->cand_rows.release(); c->cand_keep.release(); c->cand_small.release();
     c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
-    c->ol_d.release(); c->ol_part.release(); c->ol_rows.release(); c->ol_keep.release(); c->ol_cnt.release(); c->ol_small.release();
+    c->ol_d.release(); c->ol_part.release(); c->ol_cnt.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

@@ -22,8 +22,6 @@ constexpr int SEL_TILE = 4 * DV_BLOCK;       // mask bytes per block of the comp
 #define SICP_INGEST_BLOCKS 1024
 #endif
 
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
-
 // The strided (n, 3) view -> the slot's padded columns, widened exactly, and in the same pass what k_cloud_stats measures (min / max keys
 // per axis, the largest squared norm with the same fma order, a NaN / inf sticks): min / max reductions, exact in any order.  CONTIG
 // (row_stride 3, col_stride 1): a step's 3 x 512 elements are read as contiguous words through LDS, so every load instruction of a wave
@@ -240,20 +238,6 @@ void launch_egress(hipStream_t s, const double *x, const double *y, const double
 }  // namespace sicp
 
 namespace {
-
-// device memory of the ctx's device (a host pointer, managed or foreign memory is refused)
-int check_device_ptr(sicp_ctx *c, const void *p, const char *what)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SICP_ERR_INVALID, "%s is not device memory (a host pointer goes through sicp_cloud_upload / sicp_cloud_download)", what);
-    }
-    if (at.type != hipMemoryTypeDevice)
-        return fail(SICP_ERR_INVALID, "%s is not device memory (a host pointer goes through sicp_cloud_upload / sicp_cloud_download)", what);
-    if (at.device != c->device) return fail(SICP_ERR_INVALID, "%s is memory of device %d, the ctx is on device %d", what, at.device, c->device);
-    return SICP_OK;
-}
 
 int check_strides(int dtype, int64_t rs, int64_t cs)
 {

@@ -33,8 +33,6 @@
 
 namespace sicp {
 
-static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
-
 // One pass over a cloud: out[0..2] = min keys, out[3..5] = max keys (ordered-uint64 image of the doubles),
 // out[6] = bits of the largest squared norm (a NaN sticks: the upload rejects non-finite clouds).
 // Wave reductions are register moves, the block folds in LDS: 7 atomics per BLOCK.

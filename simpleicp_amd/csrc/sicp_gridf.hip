@@ -33,8 +33,6 @@
 
 namespace sicp {
 
-static inline unsigned cdivf(long a, long b) { return (unsigned)((a + b - 1) / b); }
-
 // ---- the grid's companions ---------------------------------------------------------------------------------------------------------
 // records -> (x - c0x, y - c0y, z - c0z) as float32 + the original row's low 32 bits (unused by the filter: it names candidates by
 // their position in cell order, which is also where the 32-byte record of the winner is)
@@ -84,11 +82,11 @@ __global__ __launch_bounds__(256) void k_cell_boxes(const uint32_t *__restrict__
 
 void launch_recf(hipStream_t s, const void *rec, long n, const double c0[3], void *recf)
 {
-    hipLaunchKernelGGL(k_recf, dim3(cdivf(n, 256)), dim3(256), 0, s, (const double4 *)rec, n, c0[0], c0[1], c0[2], (float4 *)recf);
+    hipLaunchKernelGGL(k_recf, dim3(cdiv(n, 256)), dim3(256), 0, s, (const double4 *)rec, n, c0[0], c0[1], c0[2], (float4 *)recf);
 }
 void launch_cell_boxes(hipStream_t s, const uint32_t *cell_start, const void *rec, long ncells, const GridGeom &G, unsigned long long *cell_box)
 {
-    hipLaunchKernelGGL(k_cell_boxes, dim3(cdivf(ncells, 256)), dim3(256), 0, s, cell_start, (const double4 *)rec, ncells, G, cell_box);
+    hipLaunchKernelGGL(k_cell_boxes, dim3(cdiv(ncells, 256)), dim3(256), 0, s, cell_start, (const double4 *)rec, ncells, G, cell_box);
 }
 
 // ---- the filter's margin ------------------------------------------------------------------------------------------------------------
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(256) void k_slot_queries(const double *__restrict__
 void launch_slot_queries(hipStream_t s, const double *qx, const double *qy, const double *qz, const uint32_t *order, const double *prev_p2,
                          long Q, void *qrec, void *pslot)
 {
-    hipLaunchKernelGGL(k_slot_queries, dim3(cdivf(Q, 256)), dim3(256), 0, s, qx, qy, qz, order, prev_p2, Q, (double4 *)qrec, (double4 *)pslot);
+    hipLaunchKernelGGL(k_slot_queries, dim3(cdiv(Q, 256)), dim3(256), 0, s, qx, qy, qz, order, prev_p2, Q, (double4 *)qrec, (double4 *)pslot);
 }
 
 // Behind a cloud-shard exchange: the slot's bound becomes the JOB-WIDE winner (the exchange left it in the by-query arrays).  The search
@@ -163,7 +161,7 @@ __global__ __launch_bounds__(256) void k_slot_bounds(const double4 *__restrict__
 }
 void launch_slot_bounds(hipStream_t s, const void *qrec, const int64_t *idx, const double *p2, long Q, void *pslot)
 {
-    hipLaunchKernelGGL(k_slot_bounds, dim3(cdivf(Q, 256)), dim3(256), 0, s, (const double4 *)qrec, idx, p2, Q, (double4 *)pslot);
+    hipLaunchKernelGGL(k_slot_bounds, dim3(cdiv(Q, 256)), dim3(256), 0, s, (const double4 *)qrec, idx, p2, Q, (double4 *)pslot);
 }
 
 // FAR = false: the flavour of a run's steady state -- a ball of a few rows, one batch of them, no hit-driven culling, no boxes; a
@@ -517,7 +515,7 @@ void launch_grid_nn16f(hipStream_t s, const GridSearch &S, int lanes_per_query, 
     for (int a = 0; a < 3; ++a) F.c0[a] = S.c0[a];
     F.eps_p = S.eps_p;
     const bool eight = lanes_per_query == 8, xcd_order = S.order != nullptr;
-    unsigned g = eight ? cdivf(S.Q, 32) : cdivf(S.Q, 16);
+    unsigned g = eight ? cdiv(S.Q, 32) : cdiv(S.Q, 16);
     if (xcd_order) g = (g + 7u) & ~7u;
     const auto kernel = eight ? (far ? k_grid_nn16f<8, true> : k_grid_nn16f<8, false>) : (far ? k_grid_nn16f<16, true> : k_grid_nn16f<16, false>);
     hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, S.st, (const double4 *)S.qrec, (double4 *)S.pslot, S.cell_start,

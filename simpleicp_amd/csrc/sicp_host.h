@@ -304,24 +304,24 @@ struct sicp_ctx {
     // positions (the kept rows themselves are stream-ordered memory of the call)
     DevBuf<uint32_t> sel_blk;
     DevBuf<int64_t> sel_pos;
-    // voxel selection (sicp_voxel.hip): the hash table of {key, winner} word pairs, every candidate's slot in it, the rows and the
-    // verdicts of a call on their way in and out, [0] the kept count [1] the error bits; grown, never shrunk, gone with the ctx
+    // the candidates of a whole-cloud operator call (take_candidates: voxel selection, the outlier filters): their rows, the verdict
+    // bytes on their way out, CAND_WORDS counter words; one call at a time uses them and has synchronised before it returns; grown,
+    // never shrunk, gone with the ctx
+    DevBuf<int64_t> cand_rows;
+    DevBuf<uint8_t> cand_keep;
+    DevBuf<unsigned long long> cand_small;
+    // voxel selection (sicp_voxel.hip): the hash table of {key, winner} word pairs, every candidate's slot in it (cand_small's first
+    // word as two 32-bit ones: the kept count, the error bits)
     DevBuf<unsigned long long> vx_tab;
     DevBuf<uint32_t> vx_slot;
-    DevBuf<int64_t> vx_rows;
-    DevBuf<uint8_t> vx_keep;
-    DevBuf<unsigned> vx_cnt;
     // sicp_evaluate (sicp_eval.hip): the workgroups' partial sums and the levels above them, their inlier counts, the record on its
     // way out; grown, never shrunk, gone with the ctx
     DevBuf<double> ev_part, ev_out;
     DevBuf<long long> ev_cnt;
-    // outlier filters (sicp_outlier.hip): d_i per position, the candidate rows, the staged verdicts and counts, the trees' partials,
-    // [0..2] mean / std / threshold [4] kept [5] candidates of a mask; grown, never shrunk, gone with the ctx
+    // outlier filters (sicp_outlier.hip): d_i per position, the staged counts, the trees' partials (cand_small: [0..2] mean / std /
+    // threshold [4] kept); grown, never shrunk, gone with the ctx
     DevBuf<double> ol_d, ol_part;
-    DevBuf<int64_t> ol_rows;
-    DevBuf<uint8_t> ol_keep;
     DevBuf<uint32_t> ol_cnt;
-    DevBuf<unsigned long long> ol_small;
     long outlier_chunk = 0;        // SICP_OUTLIER_CHUNK: candidates per search of the outlier filters (0: chosen per call; what a chunk holds is (chunk, k) distances)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
@@ -440,6 +440,28 @@ int reset_barrier_state(sicp_ctx *c);
 int barrier_timed_out(sicp_ctx *c);
 int check_slot(sicp_ctx *c, int slot, bool need_data);
 int check_rows(const int64_t *rows, int64_t m, int64_t n, const char *what);
+int check_candidate_rows(const int64_t *rows, int64_t m, int64_t n);
+int check_device_ptr(sicp_ctx *c, const void *p, const char *what);
+// operators whose answer needs every point on this rank refuse an exchange (`who` is not supported ... (`why`)); check_whole_cloud
+// also refuses a shard in `slot` and 2^31 points or more (check_below_2_31)
+int check_no_exchange(const sicp_ctx *c, const char *who, const char *why);
+int check_below_2_31(const sicp_ctx *c, int slot, const char *who);
+int check_whole_cloud(const sicp_ctx *c, int slot, const char *who, const char *why);
+// which of the three candidate forms a whole-cloud operator call takes: a row list, a device mask, or the whole slot
+struct Candidates {
+    const int64_t *d_rows = nullptr;   // device: the candidates' rows (null: rows 0, 1, ... of the slot)
+    const uint8_t *d_mask = nullptr;   // the masked form's mask, known to be memory of the ctx's device
+    long count = 0;                    // candidates
+    long positions = 0;                // entries of every output
+    bool by_position = false;          // results go to the candidate's ROW (masked form), not to its place in the list
+};
+constexpr int CAND_WORDS = 8;          // c->cand_small: cleared by take_candidates; [CAND_COUNT] belongs to it, the others to the operator
+constexpr int CAND_COUNT = 5;          // the set bytes of a mask
+constexpr int H_CAND = 208;            // c->h_small + H_CAND: the pinned mirror of c->cand_small
+// what a masked call does with its mask before anything else: enqueue the kernel that adds the number of set bytes to *d_count
+// (zero before) and say in *d_rows where it collected their rows (null: it only counted)
+typedef int (*MaskPass)(sicp_ctx *c, const uint8_t *mask, long n, unsigned long long *d_count, const int64_t **d_rows);
+int take_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, MaskPass by_mask, Candidates *K);
 double key_to_double(unsigned long long k);
 int subsample_build(sicp_ctx *c, int slot);
 int grid_coarse_level(sicp_ctx *c, int slot, GridLevel *lv, const GridLevel **out);

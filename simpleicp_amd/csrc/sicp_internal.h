@@ -20,6 +20,7 @@ constexpr int    NE_BLOCK  = 256;
 constexpr int    NE_MAX_GRID = 1024;
 constexpr long   STATS_MB_MIN_Q = 16384;  // above: mean / std over many workgroups (two launches) instead of one CU
 #define SICP_PAD_COORD 1.0e300
+inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }   // blocks of b that cover a (host side)
 
 constexpr int SOLVE_MAX_Q = 2048;   // single-launch tail (sicp_tail.hip): 8 staged Jacobian columns x 2048 x 8 B = 128 KiB of LDS
 void launch_fill_f32(hipStream_t s, float *dst, long n, float v);

@@ -1021,8 +1021,6 @@ __global__ void k_unpack_idx_postmatch(const double *__restrict__ gathered, long
 // ------------------------------------------------------------------------------------
 // launchers (host)
 // ------------------------------------------------------------------------------------
-static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
-
 // ---- the same winner by three all-reduces on 8-byte keys (cloud shards, many queries) ------------------------------
 // An all-gather hands every rank 40 bytes per query and RANK; a ring all-reduce moves ~2 x the vector whatever the rank count:
 //   1. min over the ranks of the squared distance's bit pattern (non-negative doubles order like their bits; ~0 = no match here);

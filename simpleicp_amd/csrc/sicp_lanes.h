@@ -81,6 +81,31 @@ __device__ __forceinline__ unsigned long long wsum_u64(unsigned long long v)
     return v;
 }
 
+__device__ __forceinline__ unsigned wsum_u32(unsigned v)
+{
+    v += lane_xor32<32>(v);
+    v += lane_xor32<16>(v);
+    v += lane_xor32<8>(v);
+    v += lane_xor32<4>(v);
+    v += lane_xor32<2>(v);
+    v += lane_xor32<1>(v);
+    return v;
+}
+
+// sum of v over a workgroup of WAVES waves (wave sums through LDS): thread 0 gets the total, the others their wave's sum.
+// Called by all threads.
+template <int WAVES>
+__device__ __forceinline__ unsigned block_sum_u32(unsigned v)
+{
+    __shared__ unsigned wtot[WAVES];
+    v = wsum_u32(v);
+    if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < WAVES; ++w) v += wtot[w];
+    __syncthreads();                                               // (wtot may be written again)
+    return v;
+}
 
 // ---- grid barrier for kernels whose blocks are all resident at once (at most one block per CU is launched) -------------------
 // What three measured versions taught (Q = 1 M, 256 blocks, a phase = one pass over 9 MB):

@@ -162,7 +162,7 @@ namespace sicph {
 
 namespace {
 
-unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
+const char *const NA_WHO = "rejection by the angle between normals", *const NA_WHY = "the matched point may live on another rank";
 
 // buffers of Q correspondences and the movable slot's cache, ready for an iteration's launches (before a run's first launch,
 // before an operator call).  Emptied cache: an upload or transform of the slot, another k.
@@ -171,9 +171,7 @@ int na_prepare(sicp_ctx *c, int k, bool need_cache)
     NormalAngle &N = c->na;
     Cloud &cl = c->cloud[SICP_MOV];
     const long Q = c->Q;
-    if (c->collective())
-        return fail(SICP_ERR_INVALID, "rejection by the angle between normals is not supported with an exchange (the matched point may "
-                                      "live on another rank)");
+    CHK(check_no_exchange(c, NA_WHO, NA_WHY));
     if (!N.cnt.p) {
         CHK(N.cnt.reserve(sicp::NA_WORDS));
         HIPCHK(hipMemsetAsync(N.cnt.p, 0, sicp::NA_WORDS * sizeof(unsigned), c->stream));
@@ -226,7 +224,7 @@ int na_enqueue(sicp_ctx *c, double cos_max, int k, uint8_t *flag, const IcpDev *
     A.cos_max = cos_max; A.par = N.par;
     A.use_H = H ? 1 : 0; A.st = st;
     if (H) A.H = *H;
-    hipLaunchKernelGGL(sicp::k_na_verdict, dim3(blocks256(Q)), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(sicp::k_na_verdict, dim3(cdiv(Q, 256)), dim3(256), 0, c->stream, A);
     const bool cached = !per_q && !A.col;
     if (cached) {
         // many correspondences (a first iteration misses everywhere): four list entries per wave, as launch_grid_knn_sweep chooses
@@ -234,7 +232,7 @@ int na_enqueue(sicp_ctx *c, double cos_max, int k, uint8_t *flag, const IcpDev *
         // (iota_n: how many leading words of `iota` hold 0, 1, 2, ... -- a setup with more correspondences than that, or a spill
         // list written over them, and they are written again before the sweep walks them)
         if (!four && N.iota_n < Q) {
-            hipLaunchKernelGGL(sicp::k_na_iota, dim3(blocks256(Q)), dim3(256), 0, c->stream, N.iota.p, Q);
+            hipLaunchKernelGGL(sicp::k_na_iota, dim3(cdiv(Q, 256)), dim3(256), 0, c->stream, N.iota.p, Q);
             N.iota_n = Q;
         }
         if (four) N.iota_n = 0;
@@ -243,7 +241,7 @@ int na_enqueue(sicp_ctx *c, double cos_max, int k, uint8_t *flag, const IcpDev *
                                    four ? N.iota.p : nullptr, four ? N.cnt.p + sicp::NA_SPILL + N.par : nullptr);
     }
     // (normals that were all there: nothing is listed, one block keeps the counters' books)
-    hipLaunchKernelGGL(sicp::k_na_finish, dim3(cached ? blocks256(Q) : 1u), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(sicp::k_na_finish, dim3(cached ? cdiv(Q, 256) : 1u), dim3(256), 0, c->stream, A);
     N.par ^= 1;
     HIPCHK(hipGetLastError());
     return SICP_OK;
@@ -289,7 +287,7 @@ SICP_EXPORT int sicp_cloud_set_normals(sicp_ctx *c, int slot, const int64_t *row
         HIPCHK(hipMemcpyAsync(d_rows.p, rows, (size_t)m * sizeof(int64_t), hipMemcpyDefault, c->stream));
         HIPCHK(hipMemcpyAsync(d_vals.p, normals, (size_t)3 * m * sizeof(float), hipMemcpyDefault, c->stream));
         launch_fill_f32(c->stream, cl.nv.p, 3 * n_global, std::numeric_limits<float>::quiet_NaN());
-        if (m > 0) hipLaunchKernelGGL(sicp::k_na_scatter3, dim3(blocks256(m)), dim3(256), 0, c->stream, cl.nv.p, d_rows.p, d_vals.p, (long)m);
+        if (m > 0) hipLaunchKernelGGL(sicp::k_na_scatter3, dim3(cdiv(m, 256)), dim3(256), 0, c->stream, cl.nv.p, d_rows.p, d_vals.p, (long)m);
         HIPCHK(hipGetLastError());
         return sync(c);
     };
@@ -306,9 +304,7 @@ SICP_EXPORT int sicp_normal_angle_set(sicp_ctx *c, double cos_max, int k)
     if (std::isnan(cos_max) || cos_max <= 0.0) { c->na.cos_max = 0.0; return SICP_OK; }
     if (cos_max > 1.0) return fail(SICP_ERR_INVALID, "cos_max must be <= 1");
     if (k < 2) return fail(SICP_ERR_INVALID, "neighbors must be >= 2");
-    if (c->collective())
-        return fail(SICP_ERR_INVALID, "rejection by the angle between normals is not supported with an exchange (the matched point may "
-                                      "live on another rank)");
+    CHK(check_no_exchange(c, NA_WHO, NA_WHY));
     c->na.cos_max = cos_max; c->na.k = k;
     return SICP_OK;
 }

@@ -2,119 +2,59 @@
 //
 // Statistical filter: the candidates go through the slot's k-NN search (knnk_device: the one-sweep kernel on the grid, in cell
 // order) a chunk at a time, k_ol_mean turns a chunk's ranked (chunk, k) squared distances into d_i at the candidate's POSITION;
-// two trees over all positions (k_ol_partials / k_ol_fold: contract (E)'s adjacent-pair tree of one term, cut at the wave, the
-// workgroup and the launch as sicp_eval.hip cuts its ten) give mean and std, k_ol_verdict writes the bytes and counts them.
+// two trees over all positions (k_ol_partials / k_ol_fold: contract (E)'s adjacent-pair tree of one term, sicp_pairtree.h) give mean
+// and std, k_ol_verdict writes the bytes and counts them.
 // Radius filter: k_ball_count walks the grid rows of a candidate's ball with OL_GS lanes, counts d2 < r^2 and leaves at
 // min_points + 1.  Integer atomics count; no floating-point atomic takes part.
 #include "sicp_host.h"
 #include "sicp_grid_dev.h"
+#include "sicp_pairtree.h"
 #include "../../include/simpleicp_hip_outlier.h"
 
 namespace sicp {
 namespace {
 
 constexpr int OL_BLOCK = 256;
-constexpr int OL_WAVES = OL_BLOCK / 64;
-constexpr int OL_TILES = 4;                        // tiles a workgroup of k_ol_partials takes (a power of two): 1024 positions a partial
-constexpr long OL_SPAN = (long)OL_BLOCK * OL_TILES;
-constexpr int OL_FOLD = 1024;                      // threads of k_ol_fold = nodes of one of its steps
-constexpr int OL_FOLD_WAVES = OL_FOLD / 64;
 constexpr int OL_GS = 16;                          // lanes per candidate of k_ball_count (k_grid_nn16's share of a wave; the group talks through ballots and ds_bpermute)
 constexpr int OL_MAX_BLOCKS = 4096;
 
-// ---- the tree of contract (E), one term ------------------------------------------------------------------------------------------
-// one level inside the wave: element e of this lane and its partner's are the halves (J each) of one pair; a pair whose upper half
-// starts at or beyond P is no addition of the contract
-template <int J>
-__device__ __forceinline__ double ol_level(double v, long e, long P)
-{
-    const bool add = (e & ~(long)(2 * J - 1)) + J < P;
-    const double o = lane_xor_f64<J>(v);
-    return add ? v + o : v;
-}
-__device__ __forceinline__ double ol_wave(double v, long e, long P)
-{
-    v = ol_level<1>(v, e, P);  v = ol_level<2>(v, e, P);   v = ol_level<4>(v, e, P);
-    v = ol_level<8>(v, e, P);  v = ol_level<16>(v, e, P);  v = ol_level<32>(v, e, P);
-    return v;
-}
-// the levels above the wave: N wave sums in LDS, node i covering the 64 elements from base + 64 i; thread 0 folds them in pair
-// order and returns the sum.  Called by all threads.
-template <int N>
-__device__ __forceinline__ double ol_nodes(const double *node, long base, long P)
-{
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        double a[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) a[i] = node[i];
-#pragma unroll
-        for (int s = 1; s < N; s *= 2)
-#pragma unroll
-            for (int i = 0; i < N; i += 2 * s)
-                a[i] = base + 64L * (i + s) < P ? a[i] + a[i + s] : a[i];
-        r = a[0];
-    }
-    __syncthreads();
-    return r;
-}
-
 // st: [0] mean [1] std [2] threshold.  SQ false: term = d (non-candidates hold +0.0 there); true: (d - mean)^2 of the candidates
 template <bool SQ>
-__global__ __launch_bounds__(OL_BLOCK) void k_ol_partials(const double *__restrict__ d, const uint8_t *__restrict__ mask, long n, long P,
+__global__ __launch_bounds__(PT_BLOCK) void k_ol_partials(const double *__restrict__ d, const uint8_t *__restrict__ mask, long n, long P,
                                                           const double *__restrict__ st, double *__restrict__ part)
 {
-    __shared__ double node[OL_TILES * OL_WAVES];
+    __shared__ double node[PT_TILES * PT_WAVES][1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long base = (long)blockIdx.x * OL_SPAN;
+    const long base = (long)blockIdx.x * PT_SPAN;
     const double mean = SQ ? st[0] : 0.0;
 #pragma unroll
-    for (int t = 0; t < OL_TILES; ++t) {
-        const long e = base + (long)t * OL_BLOCK + threadIdx.x;
-        double v = 0.0;
+    for (int t = 0; t < PT_TILES; ++t) {
+        const long e = base + (long)t * PT_BLOCK + threadIdx.x;
+        double v[1] = {0.0};
         if (e < n) {
             const double di = d[e];
             if (SQ) {
                 const double c = di - mean;
-                v = (!mask || mask[e] != 0) ? c * c : 0.0;
+                v[0] = (!mask || mask[e] != 0) ? c * c : 0.0;
             } else {
-                v = di;
+                v[0] = di;
             }
         }
-        v = ol_wave(v, e, P);
-        if (lane == 0) node[t * OL_WAVES + wave] = v;
+        pt_wave(v, e, P);
+        if (lane == 0) node[t * PT_WAVES + wave][0] = v[0];
     }
-    const double s = ol_nodes<OL_TILES * OL_WAVES>(node, base, P);
+    const double s = pt_nodes<PT_TILES * PT_WAVES>(node, base, P);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// One workgroup: the tree over the nb partials, 1024 nodes a step, level after level between the buffers a and b; then the
-// statistics.  SQ false: st[0] = sum / m; true: st[1] = sqrt(sum / (m - 1)) (m == 1: 0), st[2] = st[0] + ratio * st[1].
+// One workgroup: the tree over the nb partials (pt_fold, between the buffers a and b); then the statistics.
+// SQ false: st[0] = sum / m; true: st[1] = sqrt(sum / (m - 1)) (m == 1: 0), st[2] = st[0] + ratio * st[1].
 template <bool SQ>
-__global__ __launch_bounds__(OL_FOLD) void k_ol_fold(double *a, double *b, long nb, double m, double ratio, double *__restrict__ st)
+__global__ __launch_bounds__(PT_FOLD) void k_ol_fold(double *a, double *b, long nb, double m, double ratio, double *__restrict__ st)
 {
-    __shared__ double node[OL_FOLD_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long P = 1;
-    while (P < nb) P *= 2;
-    long cnt = nb;
-    while (P > 1) {
-        const long tiles = (cnt + OL_FOLD - 1) / OL_FOLD;
-        for (long t = 0; t < tiles; ++t) {
-            const long e = t * OL_FOLD + threadIdx.x;
-            double v = e < cnt ? a[e] : 0.0;
-            v = ol_wave(v, e, P);
-            if (lane == 0) node[wave] = v;
-            const double s = ol_nodes<OL_FOLD_WAVES>(node, t * OL_FOLD, P);
-            if (threadIdx.x == 0) b[t] = s;
-        }
-        __syncthreads();
-        cnt = tiles;
-        P = P > OL_FOLD ? P / OL_FOLD : 1;
-        double *p = a; a = b; b = p;
-    }
-    __syncthreads();
+    __shared__ double node[PT_FOLD_WAVES][1];
+    long sa = 0;                                                   // (one term: one row)
+    pt_fold(a, sa, b, 0, nb, node);
     if (threadIdx.x == 0) {
         const double sum = a[0];
         if (!SQ) {
@@ -147,14 +87,14 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ol_verdict(const double *__restric
 {
     const double thr = st[2];
     const long stride = (long)gridDim.x * OL_BLOCK;
-    unsigned long long mine = 0;
+    unsigned mine = 0;                                             // (n < 2^31)
     for (long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x; e < n; e += stride) {
         const bool k = (!mask || mask[e] != 0) && d[e] <= thr;
         keep[e] = k ? 1 : 0;
-        mine += k ? 1ull : 0ull;
+        mine += k ? 1u : 0u;
     }
-    mine = wsum_u64(mine);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(cnt, mine);
+    mine = wsum_u32(mine);                                         // block_sum_u32's wave step: one atomic per wave
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(cnt, (unsigned long long)mine);
 }
 
 // rows[0 .. *cnt) = the points whose mask byte is set (in no particular order: every result lands at the point's own position)
@@ -285,60 +225,26 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restric
 
 namespace {
 
-enum { OL_MEAN = 0, OL_STD = 1, OL_THR = 2, OL_KEPT = 4, OL_NCAND = 5, OL_WORDS = 8 };
+enum { OL_MEAN = 0, OL_STD = 1, OL_THR = 2, OL_KEPT = 4 };     // words of c->cand_small (CAND_COUNT is the intake's)
+static_assert(OL_KEPT != CAND_COUNT && OL_THR < CAND_COUNT && OL_KEPT < CAND_WORDS, "the filters' words and the intake's are apart");
 
-// which of the three candidate forms a call takes, and what both filters check alike
-struct Candidates {
-    const int64_t *d_rows = nullptr;   // device: the candidates' rows (null: rows lo, lo + 1, ...)
-    const uint8_t *d_mask = nullptr;   // the masked form's mask
-    long count = 0;                    // candidates
-    long positions = 0;                // entries of every output
-    bool by_position = false;          // results go to the candidate's ROW (masked form), not to its place in the list
-};
-
+// what both filters check alike
 int ol_common(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, const void *keep_out, const char *who)
 {
     CHK(check_slot(c, slot, true));
     if (!keep_out) return fail(SICP_ERR_INVALID, "keep_out is null");
     if (rows && mask) return fail(SICP_ERR_INVALID, "rows and mask are mutually exclusive");
-    if (c->collective())
-        return fail(SICP_ERR_INVALID, "%s is not supported with an exchange (a point's neighbours may live on another rank)", who);
-    const Cloud &cl = c->cloud[slot];
-    if (cl.idx_base != 0) return fail(SICP_ERR_INVALID, "%s is not supported on a shard (a point's neighbours may live on another rank)", who);
-    if (cl.n >= (1LL << 31)) return fail(SICP_ERR_INVALID, "%s takes clouds of fewer than 2^31 points", who);
-    if (rows && (m <= 0 || m >= (1LL << 31))) return fail(SICP_ERR_INVALID, "m must be in [1, 2^31)");
-    if (rows) CHK(check_rows(rows, m, cl.n, "rows"));
-    return SICP_OK;
+    CHK(check_whole_cloud(c, slot, who, "a point's neighbours may live on another rank"));
+    return check_candidate_rows(rows, m, c->cloud[slot].n);
 }
 
-// the candidates on the device: the list uploaded, or the mask's set bytes collected; c->ol_small cleared
-int ol_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, Candidates *K)
+// the masked form collects the rows of the set bytes: every result lands at the point's own position
+int ol_compact_mask(sicp_ctx *c, const uint8_t *mask, long n, unsigned long long *d_count, const int64_t **d_rows)
 {
-    const Cloud &cl = c->cloud[slot];
-    CHK(c->ol_small.reserve(OL_WORDS));
-    HIPCHK(hipMemsetAsync(c->ol_small.p, 0, OL_WORDS * sizeof(unsigned long long), c->stream));
-    if (rows) {
-        CHK(c->ol_rows.reserve((size_t)m));
-        HIPCHK(hipMemcpyAsync(c->ol_rows.p, rows, (size_t)m * sizeof(int64_t), hipMemcpyDefault, c->stream));
-        K->d_rows = c->ol_rows.p; K->count = (long)m; K->positions = (long)m;
-    } else if (mask) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, mask) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void)hipGetLastError();
-            return fail(SICP_ERR_INVALID, "mask is not device memory");
-        }
-        if (at.device != c->device) return fail(SICP_ERR_INVALID, "mask is memory of device %d, the ctx is on device %d", at.device, c->device);
-        CHK(c->ol_rows.reserve((size_t)cl.n));
-        const unsigned g = (unsigned)std::min<long>((cl.n + OL_BLOCK - 1) / OL_BLOCK, OL_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_ol_compact, dim3(g), dim3(OL_BLOCK), 0, c->stream, mask, (long)cl.n, c->ol_rows.p, c->ol_small.p + OL_NCAND);
-        HIPCHK(hipGetLastError());
-        unsigned long long *h = (unsigned long long *)(c->h_small + 208);
-        HIPCHK(hipMemcpyAsync(h, c->ol_small.p + OL_NCAND, sizeof *h, hipMemcpyDeviceToHost, c->stream));
-        CHK(sync(c));
-        K->d_rows = c->ol_rows.p; K->d_mask = mask; K->count = (long)*h; K->positions = (long)cl.n; K->by_position = true;
-    } else {
-        K->count = (long)cl.n; K->positions = (long)cl.n;
-    }
+    CHK(c->cand_rows.reserve((size_t)n));
+    const unsigned g = std::min(cdiv(n, OL_BLOCK), (unsigned)OL_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_ol_compact, dim3(g), dim3(OL_BLOCK), 0, c->stream, mask, n, c->cand_rows.p, d_count);
+    *d_rows = c->cand_rows.p;
     return SICP_OK;
 }
 
@@ -403,15 +309,15 @@ SICP_EXPORT int sicp_outlier_statistical(sicp_ctx *c, int slot, const int64_t *r
     HIPCHK(hipSetDevice(c->device));
     auto body = [&]() -> int {
         Candidates K;
-        CHK(ol_candidates(c, slot, rows, m, mask, &K));
+        CHK(take_candidates(c, slot, rows, m, mask, ol_compact_mask, &K));
         const long N = K.positions;
-        CHK(c->ol_keep.reserve((size_t)N));
+        CHK(c->cand_keep.reserve((size_t)N));
         CHK(c->ol_d.reserve((size_t)N));
         std::memset(out, 0, sizeof *out);
         if (K.count == 0) {                                        // an all-zero mask
-            HIPCHK(hipMemsetAsync(c->ol_keep.p, 0, (size_t)N, c->stream));
+            HIPCHK(hipMemsetAsync(c->cand_keep.p, 0, (size_t)N, c->stream));
             HIPCHK(hipMemsetAsync(c->ol_d.p, 0, (size_t)N * sizeof(double), c->stream));
-            CHK(ol_deliver(c, keep_out, c->ol_keep.p, (size_t)N));
+            CHK(ol_deliver(c, keep_out, c->cand_keep.p, (size_t)N));
             CHK(ol_deliver(c, mean_dist_out, c->ol_d.p, (size_t)N * sizeof(double)));
             return sync(c);
         }
@@ -425,27 +331,27 @@ SICP_EXPORT int sicp_outlier_statistical(sicp_ctx *c, int slot, const int64_t *r
             const long cnt = std::min(chunk, K.count - lo), qpad = round_up(cnt, QPAD);
             ol_gather(c, cl, K, lo, cnt, qpad);
             CHK(knnk_device(c, slot, c->kq.p, cnt, qpad, k, c->k_d2.p, c->k_idx.p));
-            hipLaunchKernelGGL(k_ol_mean, dim3((unsigned)((cnt + OL_BLOCK - 1) / OL_BLOCK)), dim3(OL_BLOCK), 0, c->stream, c->k_d2.p, cnt, k,
+            hipLaunchKernelGGL(k_ol_mean, dim3(cdiv(cnt, OL_BLOCK)), dim3(OL_BLOCK), 0, c->stream, c->k_d2.p, cnt, k,
                                K.by_position ? K.d_rows + lo : nullptr, K.by_position ? c->ol_d.p : c->ol_d.p + lo);
             HIPCHK(hipGetLastError());
         }
         // the two trees over all positions, then the verdicts
-        const long nb = (N + OL_SPAN - 1) / OL_SPAN, nb2 = (nb + OL_FOLD - 1) / OL_FOLD;
+        const long nb = cdiv(N, PT_SPAN), nb2 = cdiv(nb, PT_FOLD);
         long P = 1;
         while (P < N) P *= 2;
         CHK(c->ol_part.reserve((size_t)(nb + nb2)));
-        double *st = (double *)c->ol_small.p;
+        double *st = (double *)c->cand_small.p;
         const double md = (double)K.count;
-        hipLaunchKernelGGL(k_ol_partials<false>, dim3((unsigned)nb), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, P, st, c->ol_part.p);
-        hipLaunchKernelGGL(k_ol_fold<false>, dim3(1), dim3(OL_FOLD), 0, c->stream, c->ol_part.p, c->ol_part.p + nb, nb, md, std_ratio, st);
-        hipLaunchKernelGGL(k_ol_partials<true>, dim3((unsigned)nb), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, P, st, c->ol_part.p);
-        hipLaunchKernelGGL(k_ol_fold<true>, dim3(1), dim3(OL_FOLD), 0, c->stream, c->ol_part.p, c->ol_part.p + nb, nb, md, std_ratio, st);
-        const unsigned g = (unsigned)std::min<long>((N + OL_BLOCK - 1) / OL_BLOCK, OL_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_ol_verdict, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, st, c->ol_keep.p, c->ol_small.p + OL_KEPT);
+        hipLaunchKernelGGL(k_ol_partials<false>, dim3((unsigned)nb), dim3(PT_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, P, st, c->ol_part.p);
+        hipLaunchKernelGGL(k_ol_fold<false>, dim3(1), dim3(PT_FOLD), 0, c->stream, c->ol_part.p, c->ol_part.p + nb, nb, md, std_ratio, st);
+        hipLaunchKernelGGL(k_ol_partials<true>, dim3((unsigned)nb), dim3(PT_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, P, st, c->ol_part.p);
+        hipLaunchKernelGGL(k_ol_fold<true>, dim3(1), dim3(PT_FOLD), 0, c->stream, c->ol_part.p, c->ol_part.p + nb, nb, md, std_ratio, st);
+        const unsigned g = std::min(cdiv(N, OL_BLOCK), (unsigned)OL_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_ol_verdict, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, st, c->cand_keep.p, c->cand_small.p + OL_KEPT);
         HIPCHK(hipGetLastError());
-        unsigned long long *h = (unsigned long long *)(c->h_small + 208);
-        HIPCHK(hipMemcpyAsync(h, c->ol_small.p, OL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        CHK(ol_deliver(c, keep_out, c->ol_keep.p, (size_t)N));
+        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND);
+        HIPCHK(hipMemcpyAsync(h, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(ol_deliver(c, keep_out, c->cand_keep.p, (size_t)N));
         CHK(ol_deliver(c, mean_dist_out, c->ol_d.p, (size_t)N * sizeof(double)));
         CHK(sync(c));
         out->n_candidates = (int64_t)K.count;
@@ -465,7 +371,7 @@ SICP_EXPORT int sicp_outlier_radius_cells(sicp_ctx *c, int slot, double radius, 
     CHK(check_slot(c, slot, true));
     if (!out4) return fail(SICP_ERR_INVALID, "out4 is null");
     if (!std::isfinite(radius) || !(radius > 0.0)) return fail(SICP_ERR_INVALID, "radius must be finite and > 0");
-    if (c->cloud[slot].n >= (1LL << 31)) return fail(SICP_ERR_INVALID, "the radius filter takes clouds of fewer than 2^31 points");
+    CHK(check_below_2_31(c, slot, "the radius filter"));
     HIPCHK(hipSetDevice(c->device));
     GridLevel lv; long cells = 0;
     CHK(ol_level(c, slot, radius, &lv, out4, &cells));
@@ -490,12 +396,12 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
                         "smaller radius", radius, (long long)ext[0], (long long)ext[1], (long long)ext[2], (long long)cells, lv.g.h,
                         SICP_OUTLIER_MAX_BOX_CELLS);
         Candidates K;
-        CHK(ol_candidates(c, slot, rows, m, mask, &K));
+        CHK(take_candidates(c, slot, rows, m, mask, ol_compact_mask, &K));
         const long N = K.positions;
-        CHK(c->ol_keep.reserve((size_t)N));
+        CHK(c->cand_keep.reserve((size_t)N));
         CHK(c->ol_cnt.reserve((size_t)N));
         if (K.by_position) {
-            HIPCHK(hipMemsetAsync(c->ol_keep.p, 0, (size_t)N, c->stream));
+            HIPCHK(hipMemsetAsync(c->cand_keep.p, 0, (size_t)N, c->stream));
             HIPCHK(hipMemsetAsync(c->ol_cnt.p, 0, (size_t)N * sizeof(uint32_t), c->stream));
         }
         const double r2 = radius * radius;
@@ -510,17 +416,17 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
                 CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, 2.0 * lv.g.h, 1L << 22, c->k_order));
                 order = c->k_order.p;
             }
-            unsigned g = (unsigned)((cnt + (OL_BLOCK / OL_GS) - 1) / (OL_BLOCK / OL_GS));
+            unsigned g = cdiv(cnt, OL_BLOCK / OL_GS);
             if (order) g = (g + 7u) & ~7u;
             hipLaunchKernelGGL(k_ball_count, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, order,
                                K.by_position ? K.d_rows + lo : nullptr, lv.cell_start, (const double4 *)lv.rec, cnt, lv.g, radius, r2, cap,
-                               K.by_position ? c->ol_keep.p : c->ol_keep.p + lo, K.by_position ? c->ol_cnt.p : c->ol_cnt.p + lo,
-                               c->ol_small.p + OL_KEPT, c->count_work ? c->match_work.p : nullptr);
+                               K.by_position ? c->cand_keep.p : c->cand_keep.p + lo, K.by_position ? c->ol_cnt.p : c->ol_cnt.p + lo,
+                               c->cand_small.p + OL_KEPT, c->count_work ? c->match_work.p : nullptr);
             HIPCHK(hipGetLastError());
         }
-        unsigned long long *h = (unsigned long long *)(c->h_small + 208);
-        HIPCHK(hipMemcpyAsync(h, c->ol_small.p, OL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        CHK(ol_deliver(c, keep_out, c->ol_keep.p, (size_t)N));
+        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND);
+        HIPCHK(hipMemcpyAsync(h, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(ol_deliver(c, keep_out, c->cand_keep.p, (size_t)N));
         CHK(ol_deliver(c, count_out, c->ol_cnt.p, (size_t)N * sizeof(uint32_t)));
         CHK(sync(c));
         *kept_out = (int64_t)h[OL_KEPT];

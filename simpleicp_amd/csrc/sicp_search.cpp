@@ -411,8 +411,7 @@ SICP_EXPORT int sicp_evaluate(sicp_ctx *c, int query_slot, int search_slot, cons
     CHK(check_slot(c, search_slot, true));
     Cloud &qc = c->cloud[query_slot];
     if (qc.idx_base != 0) return fail(SICP_ERR_INVALID, "the query cloud (query_slot) must not be a shard");
-    if (c->collective())
-        return fail(SICP_ERR_INVALID, "sicp_evaluate is not supported with an exchange (the sums of one rank's queries are not the job's)");
+    CHK(check_no_exchange(c, "sicp_evaluate", "the sums of one rank's queries are not the job's"));
     if (!sel_idx) Q = qc.n;
     if (Q <= 0) return fail(SICP_ERR_INVALID, "Q must be > 0");
     HIPCHK(hipSetDevice(c->device));

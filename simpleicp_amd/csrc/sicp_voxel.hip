@@ -5,6 +5,7 @@
 // compare-and-swap, the winner by an atomic minimum -- so the table's final content is a function of the candidate SET, whatever
 // order the lanes arrive in.  k_voxel_verdict then writes keep = (winner of my slot == me).  Nothing here loops without a bound.
 #include "sicp_host.h"
+#include "sicp_lanes.h"
 #include "../../include/simpleicp_hip_voxel.h"
 
 namespace sicp {
@@ -82,7 +83,6 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel_verdict(const int64_t *__res
                                                             const uint32_t *__restrict__ slot_of, uint8_t *keep,
                                                             unsigned *__restrict__ cnt)
 {
-    __shared__ unsigned wsum[VX_BLOCK / 64];
     const long stride = (long)gridDim.x * VX_BLOCK;
     unsigned mine = 0;
     for (long i = (long)blockIdx.x * VX_BLOCK + threadIdx.x; i < m; i += stride) {
@@ -94,48 +94,25 @@ __global__ __launch_bounds__(VX_BLOCK) void k_voxel_verdict(const int64_t *__res
         keep[i] = k ? 1 : 0;
         mine += k ? 1u : 0u;
     }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-        for (int w = 0; w < VX_BLOCK / 64; ++w) t += wsum[w];
-        if (t) atomicAdd(cnt, t);
-    }
+    const unsigned t = block_sum_u32<VX_BLOCK / 64>(mine);
+    if (threadIdx.x == 0 && t) atomicAdd(cnt, t);
 }
 
 // cnt[0] += the non-zero bytes of mask: how many candidates a masked call has (its table is sized by them, not by the cloud)
-__global__ __launch_bounds__(VX_BLOCK) void k_voxel_count(const uint8_t *__restrict__ mask, long n, unsigned *__restrict__ cnt)
+__global__ __launch_bounds__(VX_BLOCK) void k_voxel_count(const uint8_t *__restrict__ mask, long n,
+                                                          unsigned long long *__restrict__ cnt)
 {
-    __shared__ unsigned wsum[VX_BLOCK / 64];
     const long stride = (long)gridDim.x * VX_BLOCK;
     unsigned mine = 0;
     for (long i = (long)blockIdx.x * VX_BLOCK + threadIdx.x; i < n; i += stride) mine += mask[i] != 0 ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-        for (int w = 0; w < VX_BLOCK / 64; ++w) t += wsum[w];
-        if (t) atomicAdd(cnt, t);
-    }
+    const unsigned t = block_sum_u32<VX_BLOCK / 64>(mine);
+    if (threadIdx.x == 0 && t) atomicAdd(cnt, (unsigned long long)t);
 }
 
 }  // namespace
 }  // namespace sicp
 
 namespace {
-
-int vx_device_ptr(sicp_ctx *c, const void *p, const char *what)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(SICP_ERR_INVALID, "%s is not device memory", what);
-    }
-    if (at.device != c->device) return fail(SICP_ERR_INVALID, "%s is memory of device %d, the ctx is on device %d", what, at.device, c->device);
-    return SICP_OK;
-}
 
 // the checks both entries share, and the lattice over the slot's bounding box
 int vx_lattice(sicp_ctx *c, int slot, double cell, const double *origin, VoxelLattice *L)
@@ -146,11 +123,8 @@ int vx_lattice(sicp_ctx *c, int slot, double cell, const double *origin, VoxelLa
         L->o[a] = origin ? origin[a] : 0.0;
         if (!std::isfinite(L->o[a])) return fail(SICP_ERR_INVALID, "origin must be finite");
     }
-    if (c->collective())
-        return fail(SICP_ERR_INVALID, "voxel selection is not supported with an exchange (the lowest index of a voxel may live on another rank)");
+    CHK(check_whole_cloud(c, slot, "voxel selection", "the lowest index of a voxel may live on another rank"));
     const Cloud &cl = c->cloud[slot];
-    if (cl.idx_base != 0) return fail(SICP_ERR_INVALID, "voxel selection is not supported on a shard (the lowest index of a voxel may live on another rank)");
-    if (cl.n >= (1LL << 31)) return fail(SICP_ERR_INVALID, "voxel selection takes clouds of fewer than 2^31 points");
     for (int a = 0; a < 3; ++a) {
         // the contract's formula on the box's corners: floor and the two operations are monotone, so every point's index lies between
         const double lo = std::floor((cl.bb_lo[a] - L->o[a]) / cell), hi = std::floor((cl.bb_hi[a] - L->o[a]) / cell);
@@ -163,27 +137,34 @@ int vx_lattice(sicp_ctx *c, int slot, double cell, const double *origin, VoxelLa
     return SICP_OK;
 }
 
-// both passes over m entries (rows / mask: device memory or null) of which ncand are candidates, verdicts into d_keep (device), the
-// count into *kept_out
-int vx_run(sicp_ctx *c, int slot, const int64_t *d_rows, const uint8_t *d_mask, long m, long ncand, const VoxelLattice &L,
-           uint8_t *d_keep, int64_t *kept_out)
+// the masked form only counts its candidates: the table (and what is cleared of it) follows the mask's set bytes, not the cloud's size
+int vx_count_mask(sicp_ctx *c, const uint8_t *mask, long n, unsigned long long *d_count, const int64_t **d_rows)
 {
+    const unsigned g = std::min(cdiv(n, VX_BLOCK), (unsigned)VX_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_voxel_count, dim3(g), dim3(VX_BLOCK), 0, c->stream, mask, n, d_count);
+    *d_rows = nullptr;
+    return SICP_OK;
+}
+
+// both passes over the candidates K, verdicts into d_keep (device), the count into *kept_out
+int vx_run(sicp_ctx *c, int slot, const Candidates &K, const VoxelLattice &L, uint8_t *d_keep, int64_t *kept_out)
+{
+    const long m = K.positions;
     const Cloud &cl = c->cloud[slot];
     size_t cap = 1024;
-    while (cap < 2 * (size_t)ncand) cap <<= 1;                      // load <= 0.5; ncand < 2^31, so at most 2^32 slots: their numbers fit 32 bits
+    while (cap < 2 * (size_t)K.count) cap <<= 1;                    // load <= 0.5; fewer than 2^31 candidates, so at most 2^32 slots: their numbers fit 32 bits
     CHK(c->vx_tab.reserve(2 * cap));
     CHK(c->vx_slot.reserve((size_t)m));
-    CHK(c->vx_cnt.reserve(2));
+    unsigned *cnt = (unsigned *)c->cand_small.p;                    // two 32-bit words of its own, written and read as such: [0] the kept [1] the error bits (cleared by take_candidates)
     HIPCHK(hipMemsetAsync(c->vx_tab.p, 0xff, 2 * cap * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->vx_cnt.p, 0, 2 * sizeof(unsigned), c->stream));
-    const unsigned g = (unsigned)std::min<long>((m + VX_BLOCK - 1) / VX_BLOCK, VX_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_voxel_insert, dim3(g), dim3(VX_BLOCK), 0, c->stream, cl.x(), cl.y(), cl.z(), d_rows, d_mask, m, L, c->vx_tab.p,
-                       (unsigned long long)(cap - 1), c->vx_slot.p, c->vx_cnt.p);
-    hipLaunchKernelGGL(k_voxel_verdict, dim3(g), dim3(VX_BLOCK), 0, c->stream, d_rows, d_mask, m, c->vx_tab.p, c->vx_slot.p, d_keep,
-                       c->vx_cnt.p);
+    const unsigned g = std::min(cdiv(m, VX_BLOCK), (unsigned)VX_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_voxel_insert, dim3(g), dim3(VX_BLOCK), 0, c->stream, cl.x(), cl.y(), cl.z(), K.d_rows, K.d_mask, m, L, c->vx_tab.p,
+                       (unsigned long long)(cap - 1), c->vx_slot.p, cnt);
+    hipLaunchKernelGGL(k_voxel_verdict, dim3(g), dim3(VX_BLOCK), 0, c->stream, K.d_rows, K.d_mask, m, c->vx_tab.p, c->vx_slot.p, d_keep,
+                       cnt);
     HIPCHK(hipGetLastError());
     unsigned h_cnt[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(h_cnt, c->vx_cnt.p, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
     CHK(sync(c));
     if (h_cnt[1] & 1u) return fail(SICP_ERR_INVALID, "a point lies outside the voxel lattice of the slot's bounding box (internal error)");
     if (h_cnt[1] & 2u) return fail(SICP_ERR_INVALID, "the voxel hash table is full (internal error)");
@@ -202,24 +183,23 @@ SICP_EXPORT int sicp_voxel_select(sicp_ctx *c, int slot, const int64_t *rows, in
     if (!keep_out || !kept_out) return fail(SICP_ERR_INVALID, "null argument");
     VoxelLattice L;
     CHK(vx_lattice(c, slot, cell, origin, &L));
-    const Cloud &cl = c->cloud[slot];
-    if (!rows) m = cl.n;
-    if (m <= 0 || m >= (1LL << 31)) return fail(SICP_ERR_INVALID, "m must be in [1, 2^31)");
+    CHK(check_candidate_rows(rows, m, c->cloud[slot].n));
     HIPCHK(hipSetDevice(c->device));
-    if (rows) {
-        CHK(check_rows(rows, m, cl.n, "rows"));
-        CHK(c->vx_rows.reserve((size_t)m));
-        HIPCHK(hipMemcpyAsync(c->vx_rows.p, rows, (size_t)m * sizeof(int64_t), hipMemcpyDefault, c->stream));
-    }
-    // verdicts for device memory of this device are written where the caller wants them; for the host they are staged
-    hipPointerAttribute_t at;
-    const bool direct = hipPointerGetAttributes(&at, keep_out) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
-    if (!direct) { (void)hipGetLastError(); CHK(c->vx_keep.reserve((size_t)m)); }
-    int rc = vx_run(c, slot, rows ? c->vx_rows.p : nullptr, nullptr, (long)m, (long)m, L, direct ? keep_out : c->vx_keep.p, kept_out);
-    if (rc != SICP_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (direct) return SICP_OK;
-    HIPCHK(hipMemcpyAsync(keep_out, c->vx_keep.p, (size_t)m, hipMemcpyDefault, c->stream));
-    return sync(c);
+    auto body = [&]() -> int {
+        Candidates K;
+        CHK(take_candidates(c, slot, rows, m, nullptr, nullptr, &K));
+        // verdicts for device memory of this device are written where the caller wants them; for the host they are staged
+        hipPointerAttribute_t at;
+        const bool direct = hipPointerGetAttributes(&at, keep_out) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+        if (!direct) { (void)hipGetLastError(); CHK(c->cand_keep.reserve((size_t)K.positions)); }
+        CHK(vx_run(c, slot, K, L, direct ? keep_out : c->cand_keep.p, kept_out));
+        if (direct) return SICP_OK;
+        HIPCHK(hipMemcpyAsync(keep_out, c->cand_keep.p, (size_t)K.positions, hipMemcpyDefault, c->stream));
+        return sync(c);
+    };
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
 }
 
 SICP_EXPORT int sicp_voxel_select_masked(sicp_ctx *c, int slot, const uint8_t *mask, int64_t n, double cell, const double *origin,
@@ -231,23 +211,18 @@ SICP_EXPORT int sicp_voxel_select_masked(sicp_ctx *c, int slot, const uint8_t *m
     CHK(vx_lattice(c, slot, cell, origin, &L));
     if (n != c->cloud[slot].n) return fail(SICP_ERR_INVALID, "n must be the slot's size (%lld points)", (long long)c->cloud[slot].n);
     HIPCHK(hipSetDevice(c->device));
-    CHK(vx_device_ptr(c, mask, "mask"));
-    CHK(vx_device_ptr(c, keep_out, "keep_out"));
-    // the candidates are counted first: the table (and what is cleared of it) follows the mask's set bytes, not the cloud's size
-    CHK(c->vx_cnt.reserve(2));
-    HIPCHK(hipMemsetAsync(c->vx_cnt.p, 0, 2 * sizeof(unsigned), c->stream));
-    const unsigned g = (unsigned)std::min<long>(((long)n + VX_BLOCK - 1) / VX_BLOCK, VX_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_voxel_count, dim3(g), dim3(VX_BLOCK), 0, c->stream, mask, (long)n, c->vx_cnt.p);
-    HIPCHK(hipGetLastError());
-    unsigned ncand = 0;
-    HIPCHK(hipMemcpyAsync(&ncand, c->vx_cnt.p, sizeof ncand, hipMemcpyDeviceToHost, c->stream));
-    CHK(sync(c));
-    if (ncand == 0) {
-        HIPCHK(hipMemsetAsync(keep_out, 0, (size_t)n, c->stream));
-        *kept_out = 0;
-        return sync(c);
-    }
-    int rc = vx_run(c, slot, nullptr, mask, (long)n, (long)ncand, L, keep_out, kept_out);
+    CHK(check_device_ptr(c, keep_out, "keep_out"));
+    auto body = [&]() -> int {
+        Candidates K;
+        CHK(take_candidates(c, slot, nullptr, 0, mask, vx_count_mask, &K));
+        if (K.count == 0) {
+            HIPCHK(hipMemsetAsync(keep_out, 0, (size_t)n, c->stream));
+            *kept_out = 0;
+            return sync(c);
+        }
+        return vx_run(c, slot, K, L, keep_out, kept_out);
+    };
+    const int rc = body();
     if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
     return rc;
 }

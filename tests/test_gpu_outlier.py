@@ -125,6 +125,16 @@ def test_candidate_counts_of_the_tree(ctx, seeded, m):
         assert ref["std"] == 0.0 and ref["keep"].all()
 
 
+def test_more_partials_than_one_step_of_the_second_stage(ctx, seeded):
+    """1024 positions a partial, 1024 partials a step of the one-workgroup second stage: from 2^20 positions on the one-term tree
+    runs two levels, as the ten-term one of test_gpu_eval.py does"""
+    X, d2 = seeded
+    m = 1024 * 1024 + 2049                                            # 1027 partials: an odd count, a last step of three
+    rows = np.random.default_rng(46).integers(0, len(X), m)
+    ref = check_stat(ctx, X, 8, 1.0, rows=rows, d2=d2)
+    assert ref["n_candidates"] == m and 0.5 * m < ref["n_kept"] < m
+
+
 def test_rows_in_random_order_with_repeats(ctx, seeded):
     X, d2 = seeded
     rows = np.random.default_rng(43).integers(0, len(X), 3001)
@@ -392,6 +402,41 @@ def test_two_calls_and_two_contexts_give_the_same_bytes(ctx, seeded):
         assert np.array_equal(x[0], a[0]) and np.array_equal(bits(x[1]), bits(a[1])) and x[2].as_dict() == a[2].as_dict()
     for x in (rb, rc):
         assert np.array_equal(x[0], ra[0]) and np.array_equal(x[1], ra[1]) and x[2] == ra[2]
+
+
+def test_voxel_selection_and_the_filters_share_their_candidate_buffers(seeded):
+    """a voxel selection by rows and a radius filter by mask take their candidates through the same buffers of the context: after
+    one another, in either order, each gives what it gives on a fresh context"""
+    from simpleicp_amd import _lib
+    X = seeded[0][:5000]
+    rng = np.random.default_rng(47)
+    rows = rng.integers(0, len(X), 3001)
+    mask = torch.tensor((rng.random(len(X)) < 0.4).astype(np.uint8), device=DEV)
+
+    def voxel(c):
+        return c.voxel_select(_lib.FIX, 0.7, rows=rows)
+
+    def radius(c):
+        keep = torch.full((len(X),), 7, dtype=torch.uint8, device=DEV)
+        cnt = torch.full((len(X),), 77, dtype=torch.int32, device=DEV)
+        kept = c.outlier_radius(_lib.FIX, 0.5, 6, mask_ptr=mask.data_ptr(), keep_ptr=keep.data_ptr(), count_ptr=cnt.data_ptr())
+        return keep.cpu().numpy(), cnt.cpu().numpy(), kept
+
+    want = {}
+    for name, op in (("voxel", voxel), ("radius", radius)):
+        with _lib.Context(0) as fresh:
+            fresh.upload(_lib.FIX, X)
+            want[name] = op(fresh)
+    assert 0 < want["voxel"].sum() < len(rows) and 0 < want["radius"][2] < int(mask.sum())
+    for order in ((voxel, radius), (radius, voxel)):
+        with _lib.Context(0) as c:
+            c.upload(_lib.FIX, X)
+            for op in order + order:                                   # ... and once more, behind the other one
+                got, ref = op(c), want["voxel" if op is voxel else "radius"]
+                if op is voxel:
+                    assert np.array_equal(got, ref)
+                else:
+                    assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and got[2] == ref[2]
 
 
 # ---- Python ----
