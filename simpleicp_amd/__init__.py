@@ -21,8 +21,9 @@ from .batch import BatchResult, run_batch                        # noqa: E402
 from .tensors import outlier_keep, run_tensors, voxel_keep                     # noqa: E402  (imports torch on its first call only)
 
 from .evaluation import Evaluation, evaluate_registration        # noqa: E402
+from .features import fpfh_features                              # noqa: E402
 from . import io                                                 # noqa: E402,F401
 
 __all__ = ["SimpleICP", "SimpleICPException", "PointCloud", "PointCloudException",
            "RigidBodyParameters", "Parameter", "run_batch", "BatchResult", "run_tensors", "voxel_keep", "outlier_keep", "Evaluation",
-           "evaluate_registration"]
+           "evaluate_registration", "fpfh_features"]

@@ -70,6 +70,12 @@ CHAIN_VERSION = 1
 OUTLIER_MAX_K = 128
 OUTLIER_MAX_BOX_CELLS = 4096
 
+# include/simpleicp_hip_fpfh.h: FPFH descriptors, the same kind of companion
+FPFH_EXPORTS = ["sicp_fpfh_version", "sicp_fpfh"]
+FPFH_VERSION = 1
+FPFH_MAX_K = 128
+FPFH_BINS = 33
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -93,6 +99,15 @@ class OutlierStats(C.Structure):
     def as_dict(self):
         return dict(n_candidates=int(self.n_candidates), n_kept=int(self.n_kept), mean=float(self.mean), std=float(self.std),
                     threshold=float(self.threshold))
+
+
+class FpfhStats(C.Structure):
+    """struct sicp_fpfh_stats (contract (F)): 32 bytes."""
+    _fields_ = [("n_points", C.c_int64), ("n_pairs", C.c_int64), ("n_void_pairs", C.c_int64), ("n_empty", C.c_int64)]
+
+    def as_dict(self):
+        return dict(n_points=int(self.n_points), n_pairs=int(self.n_pairs), n_void_pairs=int(self.n_void_pairs),
+                    n_empty=int(self.n_empty))
 
 
 class IterParams(C.Structure):
@@ -150,6 +165,8 @@ FEATURES = {
         "sicp_outlier_radius_cells": [_vp, _cint, _dbl, _vp]}),
     "chain": _Feature(CHAIN_EXPORTS, "simpleicp_hip_chain.h", "chain", CHAIN_VERSION, {
         "sicp_chain_info": [_vp, _vp]}),
+    "fpfh": _Feature(FPFH_EXPORTS, "simpleicp_hip_fpfh.h", "FPFH", FPFH_VERSION, {
+        "sicp_fpfh": [_vp, _cint, _vp, _cint, _dbl, _vp, _vp, _vp, C.POINTER(FpfhStats)]}),
 }
 
 _lib = None
@@ -291,6 +308,7 @@ normals_version = partial(_feature_version, "normals")
 voxel_version = partial(_feature_version, "voxel")
 eval_version = partial(_feature_version, "evaluation")
 outlier_version = partial(_feature_version, "outlier")
+fpfh_version = partial(_feature_version, "fpfh")
 
 
 def select_positions(m, Q):
@@ -663,6 +681,30 @@ class Context:
         out = np.zeros(4, np.int64)
         self._chk(self._L.sicp_outlier_radius_cells(self._h, slot, float(radius), _ptr(out)))
         return tuple(int(v) for v in out)
+
+    # -- FPFH descriptors (contract (F)) --
+    def fpfh(self, slot, normals, k, radius=np.inf, viewpoint=None, fpfh_ptr=None, counts_ptr=None, want_counts=False):
+        """sicp_fpfh: the 33-bin FPFH descriptor of every point of the slot from its k nearest points (the point itself
+        included in k) within radius (strict; inf = none).  normals: (n, 3) float32, a numpy array or a device tensor; viewpoint:
+        three floats, the normals are turned towards it first (None: used as they are).  Returns ((n, 33) float32, (n, 34) uint16
+        counts or None, FpfhStats); with fpfh_ptr (device memory, n * 33 floats) the descriptors are left there, the counts at
+        counts_ptr if given (n * 34 uint16), and the FpfhStats alone is returned."""
+        fpfh_version()
+        n = self.size(slot)
+        if isinstance(normals, np.ndarray) or not hasattr(normals, "data_ptr"):
+            normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if tuple(normals.shape) != (n, 3):
+            raise ValueError("normals must have shape (n, 3), one row per point of the slot")
+        vp = None if viewpoint is None else _f64(viewpoint).reshape(3)
+        st = FpfhStats()
+        if fpfh_ptr is not None:
+            self._chk(self._L.sicp_fpfh(self._h, slot, _ptr(normals), int(k), float(radius), _ptr(vp), C.c_void_p(int(fpfh_ptr)),
+                                        None if counts_ptr is None else C.c_void_p(int(counts_ptr)), C.byref(st)))
+            return st
+        out = np.empty((n, FPFH_BINS), np.float32)
+        cnt = np.empty((n, FPFH_BINS + 1), np.uint16) if want_counts else None
+        self._chk(self._L.sicp_fpfh(self._h, slot, _ptr(normals), int(k), float(radius), _ptr(vp), _ptr(out), _ptr(cnt), C.byref(st)))
+        return out, cnt, st
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):

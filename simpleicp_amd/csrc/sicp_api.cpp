@@ -256,6 +256,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FSCAN")) c->fscan_variant = !std::strcmp(e, "inline") ? 1 : 0;
     if (const char *e = std::getenv("SICP_FSCAN_CAP")) c->fscan_cap = std::atol(e);
     if (const char *e = std::getenv("SICP_OUTLIER_CHUNK")) c->outlier_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
     // SICP_SOLVE_TRACE: per-iteration traces on stderr -- any value: the tail's cycle counters; "host": the host's enqueue timings too;
     // "sel" / "eval": the fine splits of a -DSICP_SEL_FINE_TRACE / -DSICP_EVAL_FINE_TRACE build (build.build_variant)
     if (const char *e = std::getenv("SICP_SOLVE_TRACE")) {
@@ -304,6 +305,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->vx_tab.release(); c->vx_slot.release(); c->cand_rows.release(); c->cand_keep.release(); c->cand_small.release();
     c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
     c->ol_d.release(); c->ol_part.release(); c->ol_cnt.release();
+    c->fp_nrm.release(); c->fp_out.release(); c->fp_cnt.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

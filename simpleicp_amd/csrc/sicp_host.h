@@ -323,6 +323,11 @@ struct sicp_ctx {
     DevBuf<double> ol_d, ol_part;
     DevBuf<uint32_t> ol_cnt;
     long outlier_chunk = 0;        // SICP_OUTLIER_CHUNK: candidates per search of the outlier filters (0: chosen per call; what a chunk holds is (chunk, k) distances)
+    // FPFH descriptors (sicp_fpfh.hip): the normals as they are used (oriented), the counts of pass 1 ((n, 34) uint16), the staged
+    // descriptors of a call whose output is host memory; grown, never shrunk, gone with the ctx
+    DevBuf<float> fp_nrm, fp_out;
+    DevBuf<uint16_t> fp_cnt;
+    long fpfh_chunk = 0;           // SICP_FPFH_CHUNK: points per search of sicp_fpfh (0: chosen per call, as the outlier filters choose theirs)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

@@ -1,0 +1,144 @@
+"""FPFH descriptors: 33 floats per point, the local shape descriptor a global registration matches clouds by.
+
+Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
+a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is torch
+on tensors that are already on the device: ``torch.cdist(f_a, f_b).argmin(1)`` for the matches, a pose from three of them,
+``run_batch`` over the poses with ``evaluate_distance=`` to rank them.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _lib, backend, dist
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, (bool, float, str, bytes)) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer, not {v!r}")
+    if not lo <= int(v) <= hi:
+        raise ValueError(f"{name} must be >= {lo} and <= {hi}, not {v!r}")
+    return int(v)
+
+
+def fpfh_arguments(neighbors, radius, normal_neighbors, viewpoint):
+    """(k, radius as a float -- inf: none --, normal_neighbors, viewpoint as three floats or None), checked: TypeError / ValueError."""
+    k = _int_in("neighbors", neighbors, 2, _lib.FPFH_MAX_K)
+    kn = _int_in("normal_neighbors", normal_neighbors, 2, 2**31 - 1)
+    if radius is None:
+        r = math.inf
+    else:
+        if isinstance(radius, (bool, str, bytes)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+            raise TypeError(f"radius must be a number > 0 or None, not {radius!r}")
+        r = float(radius)
+        if math.isnan(r) or not r > 0.0:
+            raise ValueError(f"radius must be > 0 (None: no radius), not {radius!r}")
+    vp = None
+    if viewpoint is not None:
+        try:
+            vp = np.asarray(viewpoint, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError(f"viewpoint must be three numbers, not {viewpoint!r}") from None
+        if vp.shape != (3,) or not np.isfinite(vp).all():
+            raise ValueError(f"viewpoint must be three finite numbers, not {viewpoint!r}")
+    return k, r, kn, vp
+
+
+def _check_counts(n, k, kn, estimating):
+    if k > n:
+        raise ValueError(f"neighbors ({k}) exceeds the number of points ({n})")
+    if estimating and kn > n:
+        raise ValueError(f"normal_neighbors ({kn}) exceeds the number of points ({n})")
+
+
+def _need_backend(ctx):
+    if not hasattr(ctx, "fpfh"):
+        raise _lib.BackendError("this backend has no FPFH descriptors")
+
+
+def fpfh_features(X, normals=None, *, neighbors=32, radius=None, normal_neighbors=10, viewpoint=None, return_counts=False):
+    """The FPFH descriptors of X as an (n, 33) float32 array: bins 0..10 the angle of the Darboux frame's third feature, 11..21
+    and 22..32 the two cosines, each group summing to 200 (contract (F)).
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any
+    strides; ingest and stream rule are run_tensors').  A tensor gives a torch tensor on its device, anything else numpy.
+    ``neighbors``: k of the k-NN list of every point, the point itself included (2 .. 128); ``radius``: only neighbours strictly
+    closer count (None: all k - 1) -- Open3D's hybrid search (radius, max_nn).
+    ``normals``: (n, 3), one per point; None: a PointCloud's own nx / ny / nz columns if it has them, else the library's normals
+    from ``normal_neighbors`` points.  ``viewpoint``: three numbers; every normal is turned towards it first -- the library's own
+    normals carry no physical orientation, and the descriptor depends on the signs.
+    ``return_counts``: also the (n, 34) SPFH counts of pass 1 (33 bins and the number of pairs; uint16 in numpy, int16 in torch).
+    The library's fixed slot holds X afterwards."""
+    from .pointcloud import PointCloud
+    from .tensors import _is_device_tensor
+    k, r, kn, vp = fpfh_arguments(neighbors, radius, normal_neighbors, viewpoint)
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        return _on_device(X, normals, k, r, kn, vp, bool(return_counts))
+    own = None
+    if isinstance(X, PointCloud):
+        n = len(X)
+        if normals is None and all(c in X for c in ("nx", "ny", "nz")):
+            own = np.stack([np.asarray(X[c].to_numpy(), dtype=np.float32) for c in ("nx", "ny", "nz")], axis=1)
+    else:
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError("X must be a PointCloud, an (n, 3) array or a CUDA tensor")
+        n = X.shape[0]
+    if normals is not None:
+        own = np.ascontiguousarray(normals, dtype=np.float32)
+        if own.shape != (n, 3):
+            raise ValueError(f"normals must have shape ({n}, 3), not {own.shape}")
+    if n == 0:
+        out = np.empty((0, _lib.FPFH_BINS), np.float32)
+        return (out, np.empty((0, _lib.FPFH_BINS + 1), np.uint16)) if return_counts else out
+    _check_counts(n, k, kn, own is None)
+    if dist.is_distributed():
+        from .icp import SimpleICPException
+        raise SimpleICPException("fpfh_features does not run in a torch.distributed job: describe the clouds with one process first")
+    ctx = backend.get_context()
+    _need_backend(ctx)
+    ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this call)
+    dist.detach(ctx)
+    if isinstance(X, PointCloud):
+        X._upload(ctx, _lib.FIX)
+    else:
+        ctx.upload(_lib.FIX, X)
+    if own is None:                   # (host callers hold no device allocator: the normals make the round trip, 12 bytes per point)
+        own = ctx.estimate_normals(_lib.FIX, np.arange(n, dtype=np.int64), kn)[0]
+    out, cnt, _ = ctx.fpfh(_lib.FIX, own, k, r, vp, want_counts=bool(return_counts))
+    return (out, cnt) if return_counts else out
+
+
+def _on_device(X, normals, k, r, kn, vp, return_counts):
+    import torch
+    from .tensors import _keep_opening
+    if normals is not None and not isinstance(normals, (torch.Tensor, np.ndarray)):
+        raise TypeError("normals must be a torch.Tensor or a numpy array of shape (n, 3)")
+    if isinstance(X, torch.Tensor) and X.dim() == 2:
+        if normals is not None and tuple(normals.shape) != (X.shape[0], 3):
+            raise ValueError(f"normals must have shape ({X.shape[0]}, 3), not {tuple(normals.shape)}")
+        if X.shape[0] > 0:
+            _check_counts(X.shape[0], k, kn, normals is None)
+    ctx, n, _, _ = _keep_opening("fpfh_features", X, None, needs=("fpfh", "FPFH descriptors"))
+    dev = X.device
+    out = torch.empty((n, _lib.FPFH_BINS), dtype=torch.float32, device=dev)
+    cnt = torch.empty((n, _lib.FPFH_BINS + 1), dtype=torch.int16, device=dev) if return_counts else None
+    if ctx is None:
+        return (out, cnt) if return_counts else out
+    if normals is None:               # the library's normals of all points, left in device memory
+        sel = torch.arange(n, dtype=torch.int64, device=dev)
+        nv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        pl = torch.empty(n, dtype=torch.float32, device=dev)
+    elif isinstance(normals, torch.Tensor):
+        if normals.device != dev:
+            raise ValueError(f"normals is on {normals.device}, X on {dev}")
+        nv = normals.to(torch.float32).contiguous()
+    else:
+        nv = torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32)).to(dev)
+    # what torch queued for this call on its current stream (the index vector, the normals' copy) comes before the library reads it
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
+    if normals is None:
+        ctx.estimate_normals_into(_lib.FIX, sel.data_ptr(), n, kn, nv.data_ptr(), pl.data_ptr())
+    ctx.fpfh(_lib.FIX, nv, k, r, vp, fpfh_ptr=out.data_ptr(), counts_ptr=None if cnt is None else cnt.data_ptr())
+    return (out, cnt) if return_counts else out

@@ -324,6 +324,13 @@ class PointCloud(pd.DataFrame):
         keep, _, _ = ctx.outlier_radius(_lib.FIX, r, int(min_points), rows=None if len(cur) == self._num_points else cur)
         self._set_idx_selected(cur[keep])
 
+    def fpfh(self, neighbors: int = 32, radius=None) -> np.ndarray:
+        """The (n, 33) float32 FPFH descriptors of ALL points (contract (F)): ``fpfh_features(self,
+        neighbors=neighbors, radius=radius)`` -- the cloud's own nx / ny / nz columns where it has them (a point without a normal
+        has no pairs of its own: its row holds its neighbours' share alone), the library's normals otherwise.  Not in the reference."""
+        from .features import fpfh_features
+        return fpfh_features(self, neighbors=neighbors, radius=radius)
+
     # ---- attributes (pointcloud.py:173-203) ---------------------------------------------
     def estimate_normals(self, neighbors: int, _ctx=None, _uploaded=False, _sel=None) -> None:
         """Normal vector + planarity of every SELECTED point from its `neighbors` nearest
