@@ -76,6 +76,11 @@ FPFH_VERSION = 1
 FPFH_MAX_K = 128
 FPFH_BINS = 33
 
+# include/simpleicp_hip_global.h: descriptor matching and RANSAC poses, the same kind of companion
+GLOBAL_EXPORTS = ["sicp_global_version", "sicp_feature_match", "sicp_ransac_triplets"]
+GLOBAL_VERSION = 1
+MATCH_MAX_DIM = 64
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -108,6 +113,24 @@ class FpfhStats(C.Structure):
     def as_dict(self):
         return dict(n_points=int(self.n_points), n_pairs=int(self.n_pairs), n_void_pairs=int(self.n_void_pairs),
                     n_empty=int(self.n_empty))
+
+
+class MatchStats(C.Structure):
+    """struct sicp_match_stats (contract (M)): 24 bytes."""
+    _fields_ = [("n_query", C.c_int64), ("n_target", C.c_int64), ("n_unmatched", C.c_int64)]
+
+    def as_dict(self):
+        return dict(n_query=int(self.n_query), n_target=int(self.n_target), n_unmatched=int(self.n_unmatched))
+
+
+class RansacStats(C.Structure):
+    """struct sicp_ransac_stats (contract (R)): 40 bytes."""
+    _fields_ = [("n_hypotheses", C.c_int64), ("n_void", C.c_int64), ("n_pruned", C.c_int64), ("best", C.c_int64),
+                ("best_inliers", C.c_int64)]
+
+    def as_dict(self):
+        return dict(n_hypotheses=int(self.n_hypotheses), n_void=int(self.n_void), n_pruned=int(self.n_pruned), best=int(self.best),
+                    best_inliers=int(self.best_inliers))
 
 
 class IterParams(C.Structure):
@@ -167,6 +190,9 @@ FEATURES = {
         "sicp_chain_info": [_vp, _vp]}),
     "fpfh": _Feature(FPFH_EXPORTS, "simpleicp_hip_fpfh.h", "FPFH", FPFH_VERSION, {
         "sicp_fpfh": [_vp, _cint, _vp, _cint, _dbl, _vp, _vp, _vp, C.POINTER(FpfhStats)]}),
+    "global": _Feature(GLOBAL_EXPORTS, "simpleicp_hip_global.h", "global-registration", GLOBAL_VERSION, {
+        "sicp_feature_match": [_vp, _vp, _i64, _vp, _i64, _cint, _vp, _vp, C.POINTER(MatchStats)],
+        "sicp_ransac_triplets": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _dbl, _vp, _vp, C.POINTER(RansacStats)]}),
 }
 
 _lib = None
@@ -309,6 +335,7 @@ voxel_version = partial(_feature_version, "voxel")
 eval_version = partial(_feature_version, "evaluation")
 outlier_version = partial(_feature_version, "outlier")
 fpfh_version = partial(_feature_version, "fpfh")
+global_version = partial(_feature_version, "global")
 
 
 def select_positions(m, Q):
@@ -705,6 +732,54 @@ class Context:
         cnt = np.empty((n, FPFH_BINS + 1), np.uint16) if want_counts else None
         self._chk(self._L.sicp_fpfh(self._h, slot, _ptr(normals), int(k), float(radius), _ptr(vp), _ptr(out), _ptr(cnt), C.byref(st)))
         return out, cnt, st
+
+    # -- descriptor matching and RANSAC poses (contracts (M) and (R)) --
+    def feature_match(self, query, target, nq=None, nt=None, dim=None, idx_ptr=None, d2_ptr=None, want_d2=True):
+        """sicp_feature_match: for every row of query (nq, dim) the row of target (nt, dim) with the smallest (d2, row), d2 the
+        float32 sum of squared differences in column order; -1 / +inf where no row has a finite d2.  Host form: float32 arrays;
+        returns ((nq,) int32, (nq,) float32 or None, MatchStats).  Device form: query and target are device addresses (ints) of
+        contiguous float32 rows, nq, nt, dim given; the indices are left at idx_ptr (nq int32), the distances at d2_ptr if
+        given (nq float32), and the MatchStats alone is returned."""
+        global_version()
+        st = MatchStats()
+        if idx_ptr is not None:
+            self._chk(self._L.sicp_feature_match(self._h, C.c_void_p(int(query)), int(nq), C.c_void_p(int(target)), int(nt), int(dim),
+                                                 C.c_void_p(int(idx_ptr)), None if d2_ptr is None else C.c_void_p(int(d2_ptr)),
+                                                 C.byref(st)))
+            return st
+        q, t = np.ascontiguousarray(query, dtype=np.float32), np.ascontiguousarray(target, dtype=np.float32)
+        if q.ndim != 2 or t.ndim != 2 or q.shape[1] != t.shape[1]:
+            raise ValueError("query and target must be (nq, dim) and (nt, dim)")
+        idx = np.empty(q.shape[0], np.int32)
+        d2 = np.empty(q.shape[0], np.float32) if want_d2 else None
+        self._chk(self._L.sicp_feature_match(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], q.shape[1], _ptr(idx), _ptr(d2),
+                                             C.byref(st)))
+        return idx, d2, st
+
+    def ransac_triplets(self, src, dst, triples, max_distance, edge_ratio, m=None, h=None, poses_ptr=None, inliers_ptr=None,
+                        want_poses=True):
+        """sicp_ransac_triplets: one pose per triple of the matched rows src[c] <-> dst[c] (the minimal solver of contract (R),
+        pruned by the edge-length check first), scored by its inliers within max_distance.  Host form: (m, 3) float64 arrays and
+        (h, 3) int32 triples; returns ((h, 12) float64 poses -- R row-major, then t -- or None, (h,) int32 inliers: -1 void, -2
+        pruned, RansacStats).  Device form: src, dst and triples are device addresses (ints), m and h given; the inliers are left
+        at inliers_ptr (h int32), the poses at poses_ptr if given (h * 12 doubles), and the RansacStats alone is returned."""
+        global_version()
+        st = RansacStats()
+        if inliers_ptr is not None:
+            self._chk(self._L.sicp_ransac_triplets(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m), C.c_void_p(int(triples)),
+                                                   int(h), float(max_distance), float(edge_ratio),
+                                                   None if poses_ptr is None else C.c_void_p(int(poses_ptr)),
+                                                   C.c_void_p(int(inliers_ptr)), C.byref(st)))
+            return st
+        s, d = _f64(src), _f64(dst)
+        tri = np.ascontiguousarray(triples, dtype=np.int32)
+        if s.ndim != 2 or s.shape[1] != 3 or d.shape != s.shape or tri.ndim != 2 or tri.shape[1] != 3:
+            raise ValueError("src and dst must be (m, 3), triples (h, 3)")
+        poses = np.empty((tri.shape[0], 12), np.float64) if want_poses else None
+        inl = np.empty(tri.shape[0], np.int32)
+        self._chk(self._L.sicp_ransac_triplets(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(tri), tri.shape[0], float(max_distance),
+                                               float(edge_ratio), _ptr(poses), _ptr(inl), C.byref(st)))
+        return poses, inl, st
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):

@@ -257,6 +257,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FSCAN_CAP")) c->fscan_cap = std::atol(e);
     if (const char *e = std::getenv("SICP_OUTLIER_CHUNK")) c->outlier_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
     // SICP_SOLVE_TRACE: per-iteration traces on stderr -- any value: the tail's cycle counters; "host": the host's enqueue timings too;
     // "sel" / "eval": the fine splits of a -DSICP_SEL_FINE_TRACE / -DSICP_EVAL_FINE_TRACE build (build.build_variant)
     if (const char *e = std::getenv("SICP_SOLVE_TRACE")) {
@@ -306,6 +307,8 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
     c->ol_d.release(); c->ol_part.release(); c->ol_cnt.release();
     c->fp_nrm.release(); c->fp_out.release(); c->fp_cnt.release();
+    c->gl_key.release(); c->gl_q.release(); c->gl_t.release(); c->gl_d2.release(); c->gl_idx.release(); c->gl_tri.release();
+    c->gl_src.release(); c->gl_dst.release(); c->gl_pose.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

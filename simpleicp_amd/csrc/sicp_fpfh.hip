@@ -164,15 +164,6 @@ long fp_chunk(const sicp_ctx *c, int k)
     return std::max<long>(65536, (1L << 24) / std::max(k, 1));
 }
 
-// is p memory of the ctx's device?  (a kernel may write it then; anything else leaves through a staging buffer)
-bool fp_on_device(const sicp_ctx *c, const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device) return true;
-    (void)hipGetLastError();
-    return false;
-}
-
 // rows [lo, lo + cnt) of the cloud as query columns (c->kq), searched: their ranked lists in c->k_d2 / c->k_idx
 int fp_search(sicp_ctx *c, int slot, long lo, long cnt, int k)
 {
@@ -204,7 +195,7 @@ SICP_EXPORT int sicp_fpfh(sicp_ctx *c, int slot, const float *normals, int k, do
     HIPCHK(hipSetDevice(c->device));
     auto body = [&]() -> int {
         const long n = (long)cl.n;
-        const bool direct = fp_on_device(c, fpfh_out);
+        const bool direct = ptr_on_device(c, fpfh_out);
         CHK(c->fp_nrm.reserve((size_t)3 * n));
         CHK(c->fp_cnt.reserve((size_t)FP_ROW * n));
         if (!direct) CHK(c->fp_out.reserve((size_t)SICP_FPFH_BINS * n));

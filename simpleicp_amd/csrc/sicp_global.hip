@@ -1,0 +1,362 @@
+// sicp_global.hip -- descriptor matching and RANSAC poses (include/simpleicp_hip_global.h; contracts (M) and (R)).
+//
+// Matching (k_match): one query row per lane, held in registers; a tile of target rows in LDS, every lane reading the same row at a
+// time (broadcast reads).  The grid's second dimension splits the target into chunks so that a few thousand queries still fill the
+// machine; a chunk's winner joins the query's 64-bit key (bits(d2) << 32) | j through an integer atomicMin -- for d2 >= +0 the bit
+// pattern orders like the value, so the key's order IS the contract's (d2, j).  The row width is a template parameter (4, 16, 36,
+// 64): the columns past dim hold 0 on both sides and add +0.0 to a sum that is >= +0, which changes no bit.
+// RANSAC (k_ransac): one wave per hypothesis, every lane forming the same pose, then the lanes striding over the m rows; counts by
+// ballot and popcount; k_ransac_best picks the lowest index among the best.  Integer atomics only.
+#include "sicp_host.h"
+#include "sicp_grid_dev.h"
+#include "../../include/simpleicp_hip_global.h"
+
+namespace sicp {
+namespace {
+
+constexpr int MT_BLOCK = 256;                      // queries per workgroup
+constexpr int MT_TILE = 128;                       // target rows in LDS at a time (64 columns: 32 KiB)
+constexpr int MT_MAX_QBLOCKS = 8192, MT_MAX_CHUNKS = 1024;   // grid limits: the blocks stride from there on
+constexpr int MT_FILL = 2048;                      // workgroups the chunking aims at
+constexpr unsigned long long MT_NONE = ~0ull;      // a key no row has joined
+constexpr int RS_BLOCK = 256, RS_WAVES = RS_BLOCK / 64;
+constexpr int RS_MAX_BLOCKS = 16384;
+
+template <int DP>
+__global__ __launch_bounds__(MT_BLOCK) void k_match(const float *__restrict__ query, const float *__restrict__ target,
+                                                    unsigned long long *__restrict__ key, long nq, long nt, int dim, long chunk,
+                                                    long nchunks)
+{
+    __shared__ __attribute__((aligned(16))) float tile[MT_TILE * DP];
+    const long nqb = (nq + MT_BLOCK - 1) / MT_BLOCK;
+    for (long qb = blockIdx.x; qb < nqb; qb += gridDim.x) {
+        const long i = qb * MT_BLOCK + threadIdx.x;
+        float q[DP];
+#pragma unroll
+        for (int b = 0; b < DP; ++b) q[b] = (i < nq && b < dim) ? query[i * dim + b] : 0.0f;
+        for (long ch = blockIdx.y; ch < nchunks; ch += gridDim.y) {
+            const long lo = ch * chunk, hi = lo + chunk < nt ? lo + chunk : nt;
+            float best = __builtin_inff();
+            long bj = -1;
+            for (long t0 = lo; t0 < hi; t0 += MT_TILE) {
+                const int rows = hi - t0 < MT_TILE ? (int)(hi - t0) : MT_TILE;
+                __syncthreads();                                   // (the last tile has been read by everyone)
+                for (int e = threadIdx.x; e < rows * DP; e += MT_BLOCK) {
+                    const int r = e / DP, b = e - r * DP;
+                    tile[e] = b < dim ? target[(t0 + r) * dim + b] : 0.0f;
+                }
+                __syncthreads();
+#pragma unroll 2
+                for (int r = 0; r < rows; ++r) {
+                    const float *g = tile + r * DP;
+                    const float t = q[0] - g[0];
+                    float d2 = t * t;
+#pragma unroll
+                    for (int b = 1; b < DP; ++b) {
+                        const float u = q[b] - g[b];
+                        d2 = d2 + u * u;
+                    }
+                    if (d2 < best) { best = d2; bj = t0 + r; }     // (ascending j: a tie keeps the lower index; NaN and +inf never win)
+                }
+            }
+            if (i < nq && bj >= 0) atomicMin(key + i, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)bj);
+        }
+    }
+}
+
+// keys -> idx_out / d2_out (nullable); st[0] += queries no row has joined
+__global__ __launch_bounds__(MT_BLOCK) void k_match_finish(const unsigned long long *__restrict__ key, long nq, int32_t *__restrict__ idx,
+                                                           float *__restrict__ d2, unsigned long long *__restrict__ st)
+{
+    const long stride = (long)gridDim.x * MT_BLOCK;
+    unsigned long long none = 0;
+    for (long base = (long)blockIdx.x * MT_BLOCK; base < nq; base += stride) {
+        const long i = base + threadIdx.x;
+        const unsigned long long k = i < nq ? key[i] : 0ull;
+        const bool un = k == MT_NONE;
+        if (i < nq) {
+            idx[i] = un ? -1 : (int32_t)(k & 0xffffffffull);
+            if (d2) d2[i] = un ? __builtin_inff() : __uint_as_float((unsigned)(k >> 32));
+        }
+        none += (unsigned long long)__popcll((long long)__ballot(un));
+    }
+    if ((threadIdx.x & 63) == 0 && none) atomicAdd(st, none);
+}
+
+__device__ __forceinline__ bool rs_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+struct V3 { double x, y, z; };
+__device__ __forceinline__ V3 rs_load(const double *__restrict__ a, long i) { return V3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}; }
+__device__ __forceinline__ V3 rs_sub(const V3 &a, const V3 &b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double rs_dot(const V3 &a, const V3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 rs_div(const V3 &a, double s) { return V3{a.x / s, a.y / s, a.z / s}; }
+__device__ __forceinline__ V3 rs_cross(const V3 &a, const V3 &b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double rs_len2(const V3 &a, const V3 &b) { const V3 d = rs_sub(a, b); return rs_dot(d, d); }
+// one pair of the edge check: does it prune?  (a NaN compares false: it prunes nothing)
+__device__ __forceinline__ bool rs_prunes(double ls2, double lt2, double r2) { return ls2 < r2 * lt2 || lt2 < r2 * ls2; }
+
+// the frame and the centroid of a triangle (contract (R), step 3)
+__device__ __forceinline__ void rs_frame(const V3 &a0, const V3 &a1, const V3 &a2, V3 &e1, V3 &e2, V3 &e3, V3 &c)
+{
+    const V3 u = rs_sub(a1, a0);
+    e1 = rs_div(u, sqrt(rs_dot(u, u)));
+    const V3 v = rs_sub(a2, a0);
+    const double s = rs_dot(e1, v);
+    const V3 w = V3{v.x - s * e1.x, v.y - s * e1.y, v.z - s * e1.z};
+    e2 = rs_div(w, sqrt(rs_dot(w, w)));
+    e3 = rs_cross(e1, e2);
+    c = V3{((a0.x + a1.x) + a2.x) / 3.0, ((a0.y + a1.y) + a2.y) / 3.0, ((a0.z + a1.z) + a2.z) / 3.0};
+}
+
+// One wave per hypothesis.  poses (nullable): (h, 12); inl: (h).
+// st: [RS_VOID] += void, [RS_PRUNED] += pruned, [RS_BEST1] = max over the hypotheses of inliers + 1.
+enum { RS_VOID = 0, RS_PRUNED = 1, RS_BEST1 = 2, RS_BEST = 3 };
+__global__ __launch_bounds__(RS_BLOCK) void k_ransac(const double *__restrict__ src, const double *__restrict__ dst,
+                                                     const int32_t *__restrict__ tri, double *__restrict__ poses,
+                                                     int32_t *__restrict__ inl, unsigned long long *__restrict__ st, long m, long h,
+                                                     double md2, double r2)
+{
+    const int lane = threadIdx.x & 63;
+    const long nw = (long)gridDim.x * RS_WAVES;
+    unsigned long long n_void = 0, n_pruned = 0, best1 = 0;        // (the same in every lane of the wave)
+    for (long k = (long)blockIdx.x * RS_WAVES + (threadIdx.x >> 6); k < h; k += nw) {
+        const long i0 = tri[3 * k], i1 = tri[3 * k + 1], i2 = tri[3 * k + 2];
+        Xf H;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) H.m[j] = 0.0;
+        int verdict = -1;
+        if (i0 >= 0 && i0 < m && i1 >= 0 && i1 < m && i2 >= 0 && i2 < m && i0 != i1 && i0 != i2 && i1 != i2) {
+            const V3 p0 = rs_load(src, i0), p1 = rs_load(src, i1), p2 = rs_load(src, i2);
+            const V3 q0 = rs_load(dst, i0), q1 = rs_load(dst, i1), q2 = rs_load(dst, i2);
+            if (rs_prunes(rs_len2(p0, p1), rs_len2(q0, q1), r2) || rs_prunes(rs_len2(p0, p2), rs_len2(q0, q2), r2) ||
+                rs_prunes(rs_len2(p1, p2), rs_len2(q1, q2), r2)) {
+                verdict = -2;
+            } else {
+                V3 a1, a2, a3, cp, b1, b2, b3, cq;
+                rs_frame(p0, p1, p2, a1, a2, a3, cp);
+                rs_frame(q0, q1, q2, b1, b2, b3, cq);
+                const double A1[3] = {a1.x, a1.y, a1.z}, A2[3] = {a2.x, a2.y, a2.z}, A3[3] = {a3.x, a3.y, a3.z};
+                const double B1[3] = {b1.x, b1.y, b1.z}, B2[3] = {b2.x, b2.y, b2.z}, B3[3] = {b3.x, b3.y, b3.z};
+                const double CQ[3] = {cq.x, cq.y, cq.z};
+                bool ok = true;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) H.m[4 * r + j] = (B1[r] * A1[j] + B2[r] * A2[j]) + B3[r] * A3[j];
+                    H.m[4 * r + 3] = CQ[r] - ((H.m[4 * r] * cp.x + H.m[4 * r + 1] * cp.y) + H.m[4 * r + 2] * cp.z);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ok = ok && rs_finite(H.m[4 * r + j]);
+                }
+                if (ok) verdict = 0;
+                else {
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) H.m[j] = 0.0;
+                }
+            }
+        }
+        int cnt = 0;
+        if (verdict == 0) {
+            for (long c0 = 0; c0 < m; c0 += 64) {
+                const long c = c0 + lane;
+                bool in = false;
+                if (c < m) {
+                    double X, Y, Z;
+                    xf(H, src[3 * c], src[3 * c + 1], src[3 * c + 2], X, Y, Z);
+                    const double dx = X - dst[3 * c], dy = Y - dst[3 * c + 1], dz = Z - dst[3 * c + 2];
+                    in = fma(dz, dz, fma(dy, dy, dx * dx)) < md2;
+                }
+                cnt += __popcll((long long)__ballot(in));
+            }
+            best1 = best1 > (unsigned long long)cnt + 1 ? best1 : (unsigned long long)cnt + 1;
+        }
+        n_void += verdict == -1 ? 1 : 0;
+        n_pruned += verdict == -2 ? 1 : 0;
+        if (lane == 0) {
+            inl[k] = verdict == 0 ? cnt : verdict;
+            if (poses) {
+                double *o = poses + 12 * k;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    o[3 * r] = H.m[4 * r]; o[3 * r + 1] = H.m[4 * r + 1]; o[3 * r + 2] = H.m[4 * r + 2];
+                    o[9 + r] = H.m[4 * r + 3];
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (n_void) atomicAdd(st + RS_VOID, n_void);
+        if (n_pruned) atomicAdd(st + RS_PRUNED, n_pruned);
+        if (best1) atomicMax(st + RS_BEST1, best1);
+    }
+}
+
+// st[RS_BEST] (all ones before) = the lowest index whose inliers + 1 == st[RS_BEST1]
+__global__ __launch_bounds__(RS_BLOCK) void k_ransac_best(const int32_t *__restrict__ inl, long h, unsigned long long *__restrict__ st)
+{
+    const unsigned long long best1 = st[RS_BEST1];
+    if (best1 == 0) return;
+    const int lane = threadIdx.x & 63;
+    const long stride = (long)gridDim.x * RS_BLOCK;
+    for (long base = (long)blockIdx.x * RS_BLOCK; base < h; base += stride) {
+        const long k = base + threadIdx.x;
+        const bool is = k < h && inl[k] >= 0 && (unsigned long long)inl[k] + 1 == best1;
+        const unsigned long long who = (unsigned long long)__ballot(is);
+        if (who && lane == __ffsll((long long)who) - 1) atomicMin(st + RS_BEST, (unsigned long long)k);      // (the wave's lowest)
+    }
+}
+
+}  // namespace
+}  // namespace sicp
+
+namespace {
+
+static_assert(RS_BEST < CAND_WORDS, "the record's counters fit the ctx's counter words");
+
+// `count` elements at p as the kernels read them: p itself if it is memory of the ctx's device, else a copy in `buf`
+template <class T>
+int gl_input(sicp_ctx *c, const T *p, size_t count, DevBuf<T> &buf, const T **dev)
+{
+    if (ptr_on_device(c, p)) { *dev = p; return SICP_OK; }
+    CHK(buf.reserve(count));
+    HIPCHK(hipMemcpyAsync(buf.p, p, count * sizeof(T), hipMemcpyDefault, c->stream));
+    *dev = buf.p;
+    return SICP_OK;
+}
+
+// where the kernels write `count` elements meant for p (null: nowhere): p itself or `buf`; gl_leave copies the staged ones out
+template <class T>
+int gl_output(sicp_ctx *c, T *p, size_t count, DevBuf<T> &buf, T **dev)
+{
+    if (!p || ptr_on_device(c, p)) { *dev = p; return SICP_OK; }
+    CHK(buf.reserve(count));
+    *dev = buf.p;
+    return SICP_OK;
+}
+template <class T>
+int gl_leave(sicp_ctx *c, T *p, size_t count, const T *dev)
+{
+    if (p && dev != p) HIPCHK(hipMemcpyAsync(p, dev, count * sizeof(T), hipMemcpyDefault, c->stream));
+    return SICP_OK;
+}
+
+int gl_check_ctx(sicp_ctx *c, const char *who)
+{
+    if (!c) return fail(SICP_ERR_INVALID, "null ctx");
+    return check_no_exchange(c, who, "the rows of one rank are not the job's");
+}
+
+template <int DP>
+void launch_match(sicp_ctx *c, dim3 grid, const float *q, const float *t, long nq, long nt, int dim, long chunk, long nchunks)
+{
+    hipLaunchKernelGGL(k_match<DP>, grid, dim3(MT_BLOCK), 0, c->stream, q, t, c->gl_key.p, nq, nt, dim, chunk, nchunks);
+}
+
+}  // namespace
+
+SICP_EXPORT int sicp_global_version(void) { return SICP_GLOBAL_VERSION; }
+
+SICP_EXPORT int sicp_feature_match(sicp_ctx *c, const float *query, int64_t nq, const float *target, int64_t nt, int dim,
+                                   int32_t *idx_out, float *d2_out, sicp_match_stats *out)
+{
+    CHK(gl_check_ctx(c, "sicp_feature_match"));
+    if (!query) return fail(SICP_ERR_INVALID, "query is null");
+    if (!target) return fail(SICP_ERR_INVALID, "target is null");
+    if (!idx_out) return fail(SICP_ERR_INVALID, "idx_out is null");
+    if (!out) return fail(SICP_ERR_INVALID, "out is null");
+    if (nq < 1) return fail(SICP_ERR_INVALID, "nq must be >= 1 (%lld given)", (long long)nq);
+    if (nt < 1) return fail(SICP_ERR_INVALID, "nt must be >= 1 (%lld given)", (long long)nt);
+    if (nt >= (1LL << 31)) return fail(SICP_ERR_INVALID, "nt must be < 2^31 (%lld given)", (long long)nt);
+    if (dim < 1 || dim > SICP_MATCH_MAX_DIM) return fail(SICP_ERR_INVALID, "dim must be >= 1 and <= %d (%d given)", SICP_MATCH_MAX_DIM, dim);
+    HIPCHK(hipSetDevice(c->device));
+    auto body = [&]() -> int {
+        const float *q, *t;
+        int32_t *idx;
+        float *d2;
+        CHK(gl_input(c, query, (size_t)nq * dim, c->gl_q, &q));
+        CHK(gl_input(c, target, (size_t)nt * dim, c->gl_t, &t));
+        CHK(gl_output(c, idx_out, (size_t)nq, c->gl_idx, &idx));
+        CHK(gl_output(c, d2_out, (size_t)nq, c->gl_d2, &d2));
+        CHK(c->gl_key.reserve((size_t)nq));
+        CHK(c->cand_small.reserve(CAND_WORDS));
+        HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+        HIPCHK(hipMemsetAsync(c->gl_key.p, 0xff, (size_t)nq * sizeof(unsigned long long), c->stream));
+        // target rows per chunk: the ctx's switch, else whole tiles, as many chunks as bring the grid to MT_FILL workgroups
+        const long nqb = (nq + MT_BLOCK - 1) / MT_BLOCK;
+        const long want = std::max<long>(1, MT_FILL / nqb);
+        const long chunk = c->match_chunk > 0 ? c->match_chunk : round_up(std::max<long>(1, (nt + want - 1) / want), MT_TILE);
+        const long nchunks = (nt + chunk - 1) / chunk;
+        const dim3 grid((unsigned)std::min<long>(nqb, MT_MAX_QBLOCKS), (unsigned)std::min<long>(nchunks, MT_MAX_CHUNKS));
+        if (dim <= 4) launch_match<4>(c, grid, q, t, nq, nt, dim, chunk, nchunks);
+        else if (dim <= 16) launch_match<16>(c, grid, q, t, nq, nt, dim, chunk, nchunks);
+        else if (dim <= 36) launch_match<36>(c, grid, q, t, nq, nt, dim, chunk, nchunks);
+        else launch_match<64>(c, grid, q, t, nq, nt, dim, chunk, nchunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_match_finish, dim3((unsigned)std::min<long>(nqb, MT_MAX_QBLOCKS)), dim3(MT_BLOCK), 0, c->stream, c->gl_key.p,
+                           (long)nq, idx, d2, c->cand_small.p);
+        HIPCHK(hipGetLastError());
+        unsigned long long *hs = (unsigned long long *)(c->h_small + H_CAND);
+        HIPCHK(hipMemcpyAsync(hs, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(gl_leave(c, idx_out, (size_t)nq, idx));
+        CHK(gl_leave(c, d2_out, (size_t)nq, d2));
+        CHK(sync(c));
+        out->n_query = nq;
+        out->n_target = nt;
+        out->n_unmatched = (int64_t)hs[0];
+        return SICP_OK;
+    };
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+SICP_EXPORT int sicp_ransac_triplets(sicp_ctx *c, const double *src, const double *dst, int64_t m, const int32_t *triples, int64_t h,
+                                     double max_distance, double edge_ratio, double *poses_out, int32_t *inliers_out,
+                                     sicp_ransac_stats *out)
+{
+    CHK(gl_check_ctx(c, "sicp_ransac_triplets"));
+    if (!src) return fail(SICP_ERR_INVALID, "src is null");
+    if (!dst) return fail(SICP_ERR_INVALID, "dst is null");
+    if (!triples) return fail(SICP_ERR_INVALID, "triples is null");
+    if (!inliers_out) return fail(SICP_ERR_INVALID, "inliers_out is null");
+    if (!out) return fail(SICP_ERR_INVALID, "out is null");
+    if (m < 3) return fail(SICP_ERR_INVALID, "m must be >= 3 (%lld given)", (long long)m);
+    if (m >= (1LL << 31)) return fail(SICP_ERR_INVALID, "m must be < 2^31 (%lld given)", (long long)m);
+    if (h < 1) return fail(SICP_ERR_INVALID, "h must be >= 1 (%lld given)", (long long)h);
+    if (!std::isfinite(max_distance) || !(max_distance > 0.0)) return fail(SICP_ERR_INVALID, "max_distance must be finite and > 0");
+    if (!(edge_ratio >= 0.0 && edge_ratio <= 1.0)) return fail(SICP_ERR_INVALID, "edge_ratio must be >= 0 and <= 1");
+    HIPCHK(hipSetDevice(c->device));
+    auto body = [&]() -> int {
+        const double *s, *d;
+        const int32_t *tri;
+        double *poses;
+        int32_t *inl;
+        CHK(gl_input(c, src, (size_t)3 * m, c->gl_src, &s));
+        CHK(gl_input(c, dst, (size_t)3 * m, c->gl_dst, &d));
+        CHK(gl_input(c, triples, (size_t)3 * h, c->gl_tri, &tri));
+        CHK(gl_output(c, poses_out, (size_t)12 * h, c->gl_pose, &poses));
+        CHK(gl_output(c, inliers_out, (size_t)h, c->gl_idx, &inl));
+        CHK(c->cand_small.reserve(CAND_WORDS));
+        HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+        HIPCHK(hipMemsetAsync(c->cand_small.p + RS_BEST, 0xff, sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_ransac, dim3((unsigned)std::min<long>((h + RS_WAVES - 1) / RS_WAVES, RS_MAX_BLOCKS)), dim3(RS_BLOCK), 0, c->stream,
+                           s, d, tri, poses, inl, c->cand_small.p, (long)m, (long)h, max_distance * max_distance, edge_ratio * edge_ratio);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ransac_best, dim3((unsigned)std::min<long>((h + RS_BLOCK - 1) / RS_BLOCK, RS_MAX_BLOCKS)), dim3(RS_BLOCK), 0,
+                           c->stream, inl, (long)h, c->cand_small.p);
+        HIPCHK(hipGetLastError());
+        unsigned long long *hs = (unsigned long long *)(c->h_small + H_CAND);
+        HIPCHK(hipMemcpyAsync(hs, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(gl_leave(c, poses_out, (size_t)12 * h, poses));
+        CHK(gl_leave(c, inliers_out, (size_t)h, inl));
+        CHK(sync(c));
+        out->n_hypotheses = h;
+        out->n_void = (int64_t)hs[RS_VOID];
+        out->n_pruned = (int64_t)hs[RS_PRUNED];
+        out->best = hs[RS_BEST1] ? (int64_t)hs[RS_BEST] : -1;
+        out->best_inliers = (int64_t)hs[RS_BEST1] - 1;
+        return SICP_OK;
+    };
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}

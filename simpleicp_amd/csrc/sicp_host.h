@@ -328,6 +328,14 @@ struct sicp_ctx {
     DevBuf<float> fp_nrm, fp_out;
     DevBuf<uint16_t> fp_cnt;
     long fpfh_chunk = 0;           // SICP_FPFH_CHUNK: points per search of sicp_fpfh (0: chosen per call, as the outlier filters choose theirs)
+    // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row), the staged copies of the
+    // arrays a call hands over in host memory -- query and target rows, indices / inlier counts, distances; matched points, triples,
+    // poses; grown, never shrunk, gone with the ctx
+    DevBuf<unsigned long long> gl_key;
+    DevBuf<float> gl_q, gl_t, gl_d2;
+    DevBuf<int32_t> gl_idx, gl_tri;
+    DevBuf<double> gl_src, gl_dst, gl_pose;
+    long match_chunk = 0;          // SICP_MATCH_CHUNK: target rows per chunk of sicp_feature_match (0: chosen per call)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;
@@ -447,6 +455,14 @@ int check_slot(sicp_ctx *c, int slot, bool need_data);
 int check_rows(const int64_t *rows, int64_t m, int64_t n, const char *what);
 int check_candidate_rows(const int64_t *rows, int64_t m, int64_t n);
 int check_device_ptr(sicp_ctx *c, const void *p, const char *what);
+// is p memory of the ctx's device?  (a kernel may read and write it then; anything else goes through a staging buffer)
+inline bool ptr_on_device(const sicp_ctx *c, const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device) return true;
+    (void)hipGetLastError();
+    return false;
+}
 // operators whose answer needs every point on this rank refuse an exchange (`who` is not supported ... (`why`)); check_whole_cloud
 // also refuses a shard in `slot` and 2^31 points or more (check_below_2_31)
 int check_no_exchange(const sicp_ctx *c, const char *who, const char *why);

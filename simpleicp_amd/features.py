@@ -1,8 +1,8 @@
 """FPFH descriptors: 33 floats per point, the local shape descriptor a global registration matches clouds by.
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
-a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is torch
-on tensors that are already on the device: ``torch.cdist(f_a, f_b).argmin(1)`` for the matches, a pose from three of them,
+a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
+``simpleicp_amd/registration.py``: ``match_features`` for the matches, ``ransac_pose`` for poses from triples of them,
 ``run_batch`` over the poses with ``evaluate_distance=`` to rank them.
 """
 from __future__ import annotations

@@ -1,0 +1,281 @@
+"""Global registration: descriptors matched across two clouds, poses from triples of matches scored by their inliers.
+
+Contracts (M) and (R), DESIGN.md section 18 (include/simpleicp_hip_global.h).  ``fpfh_features`` describes the clouds,
+``match_features`` finds every row's nearest descriptor, ``ransac_pose`` turns triples of matches into poses and counts their
+inliers -- all on the GPU, reproducible bit for bit; the random triples are drawn on the host from a seed.  ``register_global`` is
+the three in a row.  What comes back is a coarse pose and its runners-up: ``run_batch`` over ``candidates`` with
+``evaluate_distance=`` refines and ranks them.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _lib, backend, dist
+from .features import _int_in, fpfh_features
+from .tensors import _is_device_tensor
+
+
+class GlobalResult:
+    """What ``ransac_pose`` and ``register_global`` return.  ``H``: the best pose as a 4x4 float64 array (None: no hypothesis was
+    valid); ``inliers`` and ``index``: its inlier count and the row of its triple (-1: none); ``stats``: the call's record
+    (n_hypotheses, n_void, n_pruned, best, best_inliers); ``candidates``: the ``top`` best as ``(H, inliers, index)``, ordered by
+    ``(-inliers, index)``; ``n_matches``: the matches the poses were drawn from (``register_global`` only)."""
+
+    def __init__(self, candidates, stats, n_matches=None):
+        self.candidates = list(candidates)
+        self.stats = dict(stats)
+        self.n_matches = n_matches
+        self.H, self.inliers, self.index = self.candidates[0] if self.candidates else (None, -1, -1)
+
+    def __repr__(self):
+        return f"GlobalResult(inliers={self.inliers}, index={self.index}, n_matches={self.n_matches}, stats={self.stats})"
+
+
+def _refuse_distributed(who):
+    if dist.is_distributed():
+        from .icp import SimpleICPException
+        raise SimpleICPException(f"{who} does not run in a torch.distributed job: register the clouds with one process first")
+
+
+def _context(entry):
+    ctx = backend.get_context()
+    if not hasattr(ctx, entry):
+        raise _lib.BackendError("this backend has no global registration")
+    dist.detach(ctx)
+    return ctx
+
+
+def _is_torch(a):
+    return _is_device_tensor(a) or type(a).__module__.startswith("torch")
+
+
+def _check_tensor(name, t, width):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a CUDA torch.Tensor like its partner, not {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} is on {t.device}: tensors must be on the GPU; rows in host memory go in as numpy arrays")
+    device = backend.default_device()
+    if t.device.index != device:
+        raise ValueError(f"{name} is on {t.device}, the library's context on cuda:{device}")
+    if t.dim() != 2 or (width is not None and t.shape[1] != width):
+        raise ValueError(f"{name} must have shape (n, {'dim' if width is None else width}), not {tuple(t.shape)}")
+
+
+def _wait_for_torch(ctx, dev):
+    """The stream rule of run_tensors: the library's stream waits for torch's current stream before it reads anything."""
+    import torch
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
+
+
+# ---- matching ----
+def _match_shapes(nq, nt, wq, wt):
+    if wq != wt:
+        raise ValueError(f"query and target must have the same width, not {wq} and {wt}")
+    if not 1 <= wq <= _lib.MATCH_MAX_DIM:
+        raise ValueError(f"the descriptors' width must be >= 1 and <= {_lib.MATCH_MAX_DIM}, not {wq}")
+    if nt >= 2**31:
+        raise ValueError("target must have fewer than 2^31 rows")
+
+
+def _match_host(ctx, q, t):
+    """(idx int64, d2 float32) of one call; an empty side needs no backend: nobody is matched."""
+    if q.shape[0] == 0 or t.shape[0] == 0:
+        return np.full(q.shape[0], -1, np.int64), np.full(q.shape[0], np.inf, np.float32)
+    idx, d2, _ = ctx().feature_match(q, t)
+    return idx.astype(np.int64), d2
+
+
+def _match_device(ctx, q, t):
+    import torch
+    nq, nt = q.shape[0], t.shape[0]
+    if nq == 0 or nt == 0:
+        return (torch.full((nq,), -1, dtype=torch.int64, device=q.device),
+                torch.full((nq,), math.inf, dtype=torch.float32, device=q.device))
+    c = ctx()
+    idx = torch.empty(nq, dtype=torch.int32, device=q.device)
+    d2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+    _wait_for_torch(c, q.device)
+    c.feature_match(q.data_ptr(), t.data_ptr(), nq, nt, q.shape[1], idx_ptr=idx.data_ptr(), d2_ptr=d2.data_ptr())
+    return idx.to(torch.int64), d2
+
+
+def match_features(query, target, *, mutual=False, return_distance=False):
+    """For every row of ``query`` the row of ``target`` with the nearest descriptor (contract (M)): float32
+    squared differences summed in column order, ties to the lowest row, a row at a NaN or infinite distance never chosen.
+
+    ``query`` (nq, dim), ``target`` (nt, dim): float32, both numpy arrays or both CUDA torch tensors (the stream rule is
+    run_tensors'), dim at most 64.  Returns ``idx``: (nq,) int64 -- a tensor for tensors, an array for arrays --, -1 for a row
+    without a match.  ``mutual=True``: a second call with the roles swapped, and ``idx[i] = -1`` unless ``back[idx[i]] == i``.
+    ``return_distance=True``: also the (nq,) float32 squared distance to the nearest row (+inf where there is none), whatever the
+    mutual test says."""
+    on_device = _is_torch(query) or _is_torch(target)
+    if on_device:
+        import torch
+        _check_tensor("query", query, None)
+        _check_tensor("target", target, None)
+        for name, a in (("query", query), ("target", target)):
+            if a.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32, not {a.dtype}")
+    else:
+        for name, a in (("query", query), ("target", target)):
+            if not isinstance(a, np.ndarray):
+                raise TypeError(f"{name} must be a numpy array or a CUDA torch.Tensor, not {type(a).__name__}")
+            if a.dtype != np.float32:
+                raise TypeError(f"{name} must be float32, not {a.dtype}")
+            if a.ndim != 2:
+                raise ValueError(f"{name} must have shape (n, dim), not {a.shape}")
+    _match_shapes(query.shape[0], target.shape[0], query.shape[1], target.shape[1])
+    _refuse_distributed("match_features")
+    held = []
+
+    def ctx():
+        if not held:
+            held.append(_context("feature_match"))
+        return held[0]
+
+    if on_device:
+        q, t = query.contiguous(), target.contiguous()
+        one = _match_device
+    else:
+        q, t = np.ascontiguousarray(query), np.ascontiguousarray(target)
+        one = _match_host
+    idx, d2 = one(ctx, q, t)
+    if mutual and q.shape[0] and t.shape[0]:                          # (an empty side matches nobody: nothing to confirm)
+        back, _ = one(ctx, t, q)
+        found = idx >= 0
+        safe = idx.clamp(min=0) if on_device else np.maximum(idx, 0)
+        agree = found & (back[safe] == (torch.arange(len(idx), device=idx.device) if on_device else np.arange(len(idx))))
+        idx = torch.where(agree, idx, torch.full_like(idx, -1)) if on_device else np.where(agree, idx, -1)
+    return (idx, d2) if return_distance else idx
+
+
+# ---- poses ----
+def _number(name, v):
+    if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name} must be a number, not {v!r}")
+    return float(v)
+
+
+def ransac_arguments(max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1):
+    """(max_distance, hypotheses, edge_ratio, seed, triples as (h, 3) int32 or None, top), checked: TypeError / ValueError."""
+    d = _number("max_distance", max_distance)
+    if not math.isfinite(d) or not d > 0.0:
+        raise ValueError(f"max_distance must be finite and > 0, not {max_distance!r}")
+    h = _int_in("hypotheses", hypotheses, 1, 2**31 - 1)
+    r = _number("edge_ratio", edge_ratio)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f"edge_ratio must be >= 0 and <= 1, not {edge_ratio!r}")
+    s = _int_in("seed", seed, 0, 2**63 - 1)
+    k = _int_in("top", top, 1, 2**31 - 1)
+    tri = None
+    if triples is not None:
+        tri = np.asarray(triples)
+        if tri.dtype.kind not in "iu":
+            raise TypeError(f"triples must be integers, not {tri.dtype}")
+        if tri.ndim != 2 or tri.shape[1] != 3 or tri.shape[0] < 1:
+            raise ValueError(f"triples must have shape (h, 3), h >= 1, not {tri.shape}")
+        if tri.size and (tri.min() < -2**31 or tri.max() > 2**31 - 1):
+            raise ValueError("triples must fit 32-bit integers")
+        tri = np.ascontiguousarray(tri, dtype=np.int32)
+    return d, h, r, s, tri, k
+
+
+def _as_H(pose):
+    H = np.eye(4)
+    H[:3, :3] = np.asarray(pose[:9], dtype=np.float64).reshape(3, 3)
+    H[:3, 3] = pose[9:12]
+    return H
+
+
+def _best(inliers, top):
+    """The rows of the `top` best hypotheses, ordered by (-inliers, index); void and pruned ones never."""
+    valid = np.flatnonzero(inliers >= 0)
+    order = valid[np.lexsort((valid, -inliers[valid].astype(np.int64)))]
+    return order[:top]
+
+
+def ransac_pose(src, dst, *, max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1):
+    """The pose R, t that brings ``src[c]`` onto ``dst[c]`` for the most rows c (contract (R)): every triple
+    of matches gives one pose -- the minimal solver, exact for congruent triangles; triples whose edge lengths differ by more
+    than ``edge_ratio`` are pruned first (Open3D's edge-length checker) -- and a pose's score is the number of rows within
+    ``max_distance`` (strict).  A coarse pose: ICP refines it.
+
+    ``src``, ``dst``: (m, 3) matched points, both numpy arrays or both CUDA torch tensors; float32 is widened exactly.
+    ``triples``: (h, 3) integers; None: ``np.random.default_rng(seed).integers(0, m, (hypotheses, 3), dtype=np.int32)``, drawn on
+    the host (a repeated index is simply a void hypothesis).  Returns a ``GlobalResult``; its ``candidates`` are the ``top`` best."""
+    d, h, r, s, tri, top = ransac_arguments(max_distance, hypotheses, edge_ratio, seed, triples, top)
+    on_device = _is_torch(src) or _is_torch(dst)
+    if on_device:
+        import torch
+        _check_tensor("src", src, 3)
+        _check_tensor("dst", dst, 3)
+        for name, a in (("src", src), ("dst", dst)):
+            if a.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"{name} must be float32 or float64, not {a.dtype}")
+    else:
+        src, dst = np.ascontiguousarray(src, dtype=np.float64), np.ascontiguousarray(dst, dtype=np.float64)
+        for name, a in (("src", src), ("dst", dst)):
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name} must have shape (m, 3), not {a.shape}")
+    m = src.shape[0]
+    if dst.shape[0] != m:
+        raise ValueError(f"src and dst must have the same number of rows, not {m} and {dst.shape[0]}")
+    if m < 3:
+        raise ValueError(f"a pose needs at least 3 matches, not {m}")
+    if m >= 2**31:
+        raise ValueError("src must have fewer than 2^31 rows")
+    _refuse_distributed("ransac_pose")
+    if tri is None:
+        tri = np.random.default_rng(s).integers(0, m, (h, 3), dtype=np.int32)
+    ctx = _context("ransac_triplets")
+    if on_device:
+        S, D = src.to(torch.float64).contiguous(), dst.to(torch.float64).contiguous()
+        poses_d = torch.empty((len(tri), 12), dtype=torch.float64, device=S.device)
+        inl_d = torch.empty(len(tri), dtype=torch.int32, device=S.device)
+        _wait_for_torch(ctx, S.device)
+        st = ctx.ransac_triplets(S.data_ptr(), D.data_ptr(), tri.ctypes.data, d, r, m=m, h=len(tri), poses_ptr=poses_d.data_ptr(),
+                                 inliers_ptr=inl_d.data_ptr())
+        inl = inl_d.cpu().numpy()
+        rows = _best(inl, top)
+        poses = poses_d[torch.as_tensor(rows, device=S.device)].cpu().numpy() if len(rows) else np.empty((0, 12))
+    else:
+        allp, inl, st = ctx.ransac_triplets(src, dst, tri, d, r)
+        rows = _best(inl, top)
+        poses = allp[rows]
+    stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
+    return GlobalResult([(_as_H(p), int(inl[k]), int(k)) for p, k in zip(poses, rows)], stats)
+
+
+def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighbors=10, viewpoint_fixed=None, viewpoint_movable=None,
+                    mutual=True, **ransac_kwargs):
+    """A coarse pose of ``movable`` onto ``fixed`` without an initial guess -- in the direction of ``run()``'s H --: the FPFH
+    descriptors of both clouds (``fpfh_features``: ``neighbors``, ``normal_neighbors``, a viewpoint per cloud), every movable
+    point's nearest fixed descriptor (``match_features``, ``mutual``), poses from triples of those matches (``ransac_pose``:
+    ``max_distance`` and its other keywords).  Both clouds (n, 3) numpy arrays or both CUDA torch tensors.
+
+    Returns ``ransac_pose``'s GlobalResult with ``n_matches`` set; fewer than three matches give a result without a pose.
+    Refinement stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
+    unknown = set(ransac_kwargs) - {"hypotheses", "edge_ratio", "seed", "triples", "top"}
+    if unknown:
+        raise TypeError(f"register_global() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    ransac_arguments(max_distance, **ransac_kwargs)
+    if not isinstance(mutual, (bool, np.bool_)):
+        raise TypeError(f"mutual must be True or False, not {mutual!r}")
+    if _is_torch(fixed) != _is_torch(movable):
+        raise TypeError("fixed and movable must both be numpy arrays or both be CUDA torch tensors")
+    _refuse_distributed("register_global")
+    f_fix = fpfh_features(fixed, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_fixed)
+    f_mov = fpfh_features(movable, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_movable)
+    idx = match_features(f_mov, f_fix, mutual=bool(mutual))
+    keep = idx >= 0
+    n_matches = int(keep.sum())
+    if n_matches < 3:
+        return GlobalResult([], dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1), n_matches)
+    if not _is_torch(movable):
+        fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
+    res = ransac_pose(movable[keep], fixed[idx[keep]], max_distance=max_distance, **ransac_kwargs)
+    res.n_matches = n_matches
+    return res
