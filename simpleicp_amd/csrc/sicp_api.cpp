@@ -144,14 +144,13 @@ int check_whole_cloud(const sicp_ctx *c, int slot, const char *who, const char *
     return check_below_2_31(c, slot, who);
 }
 
-// the candidates on the device: the list uploaded, or the mask checked and handed to by_mask, or the whole slot; c->cand_small
-// cleared.  The masked form synchronises (its count sizes what follows); K->d_rows is good until the next reserve of c->cand_rows.
+// the candidates on the device: the list uploaded, or the mask checked and handed to by_mask, or the whole slot; the counter
+// words cleared.  The masked form synchronises (its count sizes what follows); K->d_rows is good until the next reserve of c->cand_rows.
 int take_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, MaskPass by_mask, Candidates *K)
 {
     const long n = (long)c->cloud[slot].n;
     *K = Candidates();
-    CHK(c->cand_small.reserve(CAND_WORDS));
-    HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+    CHK(counters_clear(c));
     if (rows) {
         CHK(c->cand_rows.reserve((size_t)m));
         HIPCHK(hipMemcpyAsync(c->cand_rows.p, rows, (size_t)m * sizeof(int64_t), hipMemcpyDefault, c->stream));
@@ -160,7 +159,7 @@ int take_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const
         CHK(check_device_ptr(c, mask, "mask"));
         CHK(by_mask(c, mask, n, c->cand_small.p + CAND_COUNT, &K->d_rows));
         HIPCHK(hipGetLastError());
-        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND) + CAND_COUNT;
+        unsigned long long *h = counters_host(c) + CAND_COUNT;       // (its own word alone: the operator's are fetched at the call's end)
         HIPCHK(hipMemcpyAsync(h, c->cand_small.p + CAND_COUNT, sizeof *h, hipMemcpyDeviceToHost, c->stream));
         CHK(sync(c));
         K->d_mask = mask; K->count = (long)*h; K->positions = n; K->by_position = true;
@@ -215,7 +214,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
         return fail(SICP_ERR_NO_DEVICE, "device %d is %s; this library carries gfx950 code only", device, arch.c_str());
     }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(SICP_ERR_HIP, "hipStreamCreate failed"); }
-    if (hipHostMalloc((void **)&c->h_small, 256 * sizeof(double), hipHostMallocMapped) != hipSuccess) { delete c; return fail(SICP_ERR_HIP, "hipHostMalloc failed"); }
+    if (hipHostMalloc((void **)&c->h_small, H_SMALL_WORDS * sizeof(double), hipHostMallocMapped) != hipSuccess) { delete c; return fail(SICP_ERR_HIP, "hipHostMalloc failed"); }
     int rc = c->small.reserve(128);
     if (rc == SICP_OK) rc = c->ne_partial.reserve((size_t)NE_MAX_GRID * 64);
     if (rc == SICP_OK) rc = c->ticket.reserve(4);

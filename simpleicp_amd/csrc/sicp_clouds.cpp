@@ -594,7 +594,7 @@ SICP_EXPORT int sicp_cloud_set_planarity(sicp_ctx *c, int slot, const int64_t *r
         return sync(c);
     };
     if (rc == SICP_OK) rc = body();
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);                // (always, not op_run: the local buffers are released next)
     d_rows.release(); d_vals.release();
     if (rc == SICP_OK) cl.pl_n = n_global;
     return rc;

@@ -447,7 +447,7 @@ SICP_EXPORT int sicp_lexmin_gathered(sicp_ctx *c, const double *gathered, int wo
         return sync(c);
     };
     if (rc == SICP_OK) rc = body();
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);                // (always, not op_run: the local buffers are released next)
     g.release(); d2.release(); xyz.release(); idx.release();
     return rc;
 }

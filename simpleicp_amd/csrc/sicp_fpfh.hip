@@ -18,8 +18,6 @@ constexpr int FP_WAVES = FP_BLOCK / 64;
 constexpr int FP_MAX_BLOCKS = 4096;                // the waves stride over the chunk's points from there on
 constexpr int FP_ROW = SICP_FPFH_BINS + 1;         // a point's counts: 33 bins and m_i
 
-__device__ __forceinline__ bool fp_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
 // min(10, max(0, floor(11 * ((f + 1) * 0.5)))), clamped in float64 before the conversion; a NaN gives 0
 __device__ __forceinline__ int fp_bin11(double f)
 {
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(FP_BLOCK) void k_fpfh_spfh(const double *__restrict
         const long i = lo + q;
         const double px = X[i], py = Y[i], pz = Z[i];
         const double pnx = (double)nrm[3 * i], pny = (double)nrm[3 * i + 1], pnz = (double)nrm[3 * i + 2];
-        const bool p_ok = fp_finite(pnx) && fp_finite(pny) && fp_finite(pnz);
+        const bool p_ok = finite_f64(pnx) && finite_f64(pny) && finite_f64(pnz);
         unsigned cnt = 0, m = 0, inside = 0;
         for (int r0 = 1; r0 < k; r0 += 64) {
             const int r = r0 + lane;
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(FP_BLOCK) void k_fpfh_spfh(const double *__restrict
             const double f2 = (vx * n2x + vy * n2y) + vz * n2z;
             const double a = (wx * n2x + wy * n2y) + wz * n2z;
             const double b = (n1x * n2x + n1y * n2y) + n1z * n2z;
-            const bool ok = in && d2 != 0.0 && vn != 0.0 && p_ok && fp_finite(qnx) && fp_finite(qny) && fp_finite(qnz);
+            const bool ok = in && d2 != 0.0 && vn != 0.0 && p_ok && finite_f64(qnx) && finite_f64(qny) && finite_f64(qnz);
             const int b1 = ok ? fp_sector(a, b) : -1, b2 = ok ? fp_bin11(f2) : -1, b3 = ok ? fp_bin11(f3) : -1;
 #pragma unroll
             for (int t = 0; t < 11; ++t) {
@@ -154,24 +152,8 @@ __global__ __launch_bounds__(FP_BLOCK) void k_fpfh_final(const double *__restric
 
 namespace {
 
-enum { FP_PAIRS = 0, FP_VOID = 1, FP_EMPTY = 2 };              // words of c->cand_small
+enum { FP_PAIRS = 0, FP_VOID = 1, FP_EMPTY = 2 };              // counter words
 static_assert(FP_EMPTY < CAND_WORDS, "the record's counters fit the ctx's counter words");
-
-// points per search: the ctx's switch, else as many as keep a chunk's (chunk, k) distances and indices at 256 MiB
-long fp_chunk(const sicp_ctx *c, int k)
-{
-    if (c->fpfh_chunk > 0) return c->fpfh_chunk;
-    return std::max<long>(65536, (1L << 24) / std::max(k, 1));
-}
-
-// rows [lo, lo + cnt) of the cloud as query columns (c->kq), searched: their ranked lists in c->k_d2 / c->k_idx
-int fp_search(sicp_ctx *c, int slot, long lo, long cnt, int k)
-{
-    Cloud &cl = c->cloud[slot];
-    const long qpad = round_up(cnt, QPAD);
-    launch_gather_queries(c->stream, cl.x() + lo, cl.y() + lo, cl.z() + lo, nullptr, cnt, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
-    return knnk_device(c, slot, c->kq.p, cnt, qpad, k, c->k_d2.p, c->k_idx.p);
-}
 
 }  // namespace
 
@@ -193,31 +175,28 @@ SICP_EXPORT int sicp_fpfh(sicp_ctx *c, int slot, const float *normals, int k, do
         return fail(SICP_ERR_INVALID, "viewpoint must be finite");
     CHK(check_whole_cloud(c, slot, "sicp_fpfh", "a point's neighbours may live on another rank"));
     HIPCHK(hipSetDevice(c->device));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         const long n = (long)cl.n;
-        const bool direct = ptr_on_device(c, fpfh_out);
+        float *dst;
         CHK(c->fp_nrm.reserve((size_t)3 * n));
         CHK(c->fp_cnt.reserve((size_t)FP_ROW * n));
-        if (!direct) CHK(c->fp_out.reserve((size_t)SICP_FPFH_BINS * n));
-        CHK(c->cand_small.reserve(CAND_WORDS));
-        HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+        CHK(stage_out(c, fpfh_out, (size_t)SICP_FPFH_BINS * n, c->fp_out, &dst));
+        CHK(counters_clear(c));
+        // the normals are always copied (no stage_in): k_fpfh_orient writes them
         HIPCHK(hipMemcpyAsync(c->fp_nrm.p, normals, (size_t)3 * n * sizeof(float), hipMemcpyDefault, c->stream));
         if (viewpoint) {
             hipLaunchKernelGGL(k_fpfh_orient, dim3(std::min(cdiv(n, FP_BLOCK), (unsigned)FP_MAX_BLOCKS)), dim3(FP_BLOCK), 0, c->stream,
                                cl.x(), cl.y(), cl.z(), c->fp_nrm.p, n, viewpoint[0], viewpoint[1], viewpoint[2]);
             HIPCHK(hipGetLastError());
         }
-        const long chunk = fp_chunk(c, k), most = std::min(chunk, n);
-        CHK(c->kq.reserve((size_t)3 * round_up(most, QPAD)));
-        CHK(c->k_d2.reserve((size_t)most * k));
-        CHK(c->k_idx.reserve((size_t)most * k));
+        const long chunk = knn_chunk(c->fpfh_chunk, k);
+        CHK(knn_chunk_reserve(c, std::min(chunk, n), k));
         const bool no_radius = std::isinf(radius);
         const double r2 = radius * radius;
-        float *dst = direct ? fpfh_out : c->fp_out.p;
         for (int pass = 1; pass <= 2; ++pass)
             for (long lo = 0; lo < n; lo += chunk) {
                 const long cnt = std::min(chunk, n - lo);
-                CHK(fp_search(c, slot, lo, cnt, k));
+                CHK(rows_knn(c, slot, nullptr, lo, cnt, k));
                 const unsigned g = std::min(cdiv(cnt, FP_WAVES), (unsigned)FP_MAX_BLOCKS);
                 if (pass == 1)
                     hipLaunchKernelGGL(k_fpfh_spfh, dim3(g), dim3(FP_BLOCK), 0, c->stream, cl.x(), cl.y(), cl.z(), c->fp_nrm.p, c->k_d2.p,
@@ -227,19 +206,16 @@ SICP_EXPORT int sicp_fpfh(sicp_ctx *c, int slot, const float *normals, int k, do
                                        no_radius ? 1 : 0, c->fp_cnt.p, dst);
                 HIPCHK(hipGetLastError());
             }
-        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND);
-        HIPCHK(hipMemcpyAsync(h, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if (!direct) HIPCHK(hipMemcpyAsync(fpfh_out, c->fp_out.p, (size_t)SICP_FPFH_BINS * n * sizeof(float), hipMemcpyDefault, c->stream));
+        CHK(counters_fetch(c));
+        CHK(stage_leave(c, fpfh_out, (size_t)SICP_FPFH_BINS * n, dst));
         if (spfh_counts_out)
             HIPCHK(hipMemcpyAsync(spfh_counts_out, c->fp_cnt.p, (size_t)FP_ROW * n * sizeof(uint16_t), hipMemcpyDefault, c->stream));
         CHK(sync(c));
+        const unsigned long long *h = counters_host(c);
         out->n_points = (int64_t)n;
         out->n_pairs = (int64_t)h[FP_PAIRS];
         out->n_void_pairs = (int64_t)h[FP_VOID];
         out->n_empty = (int64_t)h[FP_EMPTY];
         return SICP_OK;
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }

@@ -83,8 +83,6 @@ __global__ __launch_bounds__(MT_BLOCK) void k_match_finish(const unsigned long l
     if ((threadIdx.x & 63) == 0 && none) atomicAdd(st, none);
 }
 
-__device__ __forceinline__ bool rs_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
 struct V3 { double x, y, z; };
 __device__ __forceinline__ V3 rs_load(const double *__restrict__ a, long i) { return V3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}; }
 __device__ __forceinline__ V3 rs_sub(const V3 &a, const V3 &b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_ransac(const double *__restrict__ 
                     for (int j = 0; j < 3; ++j) H.m[4 * r + j] = (B1[r] * A1[j] + B2[r] * A2[j]) + B3[r] * A3[j];
                     H.m[4 * r + 3] = CQ[r] - ((H.m[4 * r] * cp.x + H.m[4 * r + 1] * cp.y) + H.m[4 * r + 2] * cp.z);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) ok = ok && rs_finite(H.m[4 * r + j]);
+                    for (int j = 0; j < 4; ++j) ok = ok && finite_f64(H.m[4 * r + j]);
                 }
                 if (ok) verdict = 0;
                 else {
@@ -212,33 +210,6 @@ namespace {
 
 static_assert(RS_BEST < CAND_WORDS, "the record's counters fit the ctx's counter words");
 
-// `count` elements at p as the kernels read them: p itself if it is memory of the ctx's device, else a copy in `buf`
-template <class T>
-int gl_input(sicp_ctx *c, const T *p, size_t count, DevBuf<T> &buf, const T **dev)
-{
-    if (ptr_on_device(c, p)) { *dev = p; return SICP_OK; }
-    CHK(buf.reserve(count));
-    HIPCHK(hipMemcpyAsync(buf.p, p, count * sizeof(T), hipMemcpyDefault, c->stream));
-    *dev = buf.p;
-    return SICP_OK;
-}
-
-// where the kernels write `count` elements meant for p (null: nowhere): p itself or `buf`; gl_leave copies the staged ones out
-template <class T>
-int gl_output(sicp_ctx *c, T *p, size_t count, DevBuf<T> &buf, T **dev)
-{
-    if (!p || ptr_on_device(c, p)) { *dev = p; return SICP_OK; }
-    CHK(buf.reserve(count));
-    *dev = buf.p;
-    return SICP_OK;
-}
-template <class T>
-int gl_leave(sicp_ctx *c, T *p, size_t count, const T *dev)
-{
-    if (p && dev != p) HIPCHK(hipMemcpyAsync(p, dev, count * sizeof(T), hipMemcpyDefault, c->stream));
-    return SICP_OK;
-}
-
 int gl_check_ctx(sicp_ctx *c, const char *who)
 {
     if (!c) return fail(SICP_ERR_INVALID, "null ctx");
@@ -268,17 +239,16 @@ SICP_EXPORT int sicp_feature_match(sicp_ctx *c, const float *query, int64_t nq, 
     if (nt >= (1LL << 31)) return fail(SICP_ERR_INVALID, "nt must be < 2^31 (%lld given)", (long long)nt);
     if (dim < 1 || dim > SICP_MATCH_MAX_DIM) return fail(SICP_ERR_INVALID, "dim must be >= 1 and <= %d (%d given)", SICP_MATCH_MAX_DIM, dim);
     HIPCHK(hipSetDevice(c->device));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         const float *q, *t;
         int32_t *idx;
         float *d2;
-        CHK(gl_input(c, query, (size_t)nq * dim, c->gl_q, &q));
-        CHK(gl_input(c, target, (size_t)nt * dim, c->gl_t, &t));
-        CHK(gl_output(c, idx_out, (size_t)nq, c->gl_idx, &idx));
-        CHK(gl_output(c, d2_out, (size_t)nq, c->gl_d2, &d2));
+        CHK(stage_in(c, query, (size_t)nq * dim, c->gl_q, &q));
+        CHK(stage_in(c, target, (size_t)nt * dim, c->gl_t, &t));
+        CHK(stage_out(c, idx_out, (size_t)nq, c->gl_idx, &idx));
+        CHK(stage_out(c, d2_out, (size_t)nq, c->gl_d2, &d2));
         CHK(c->gl_key.reserve((size_t)nq));
-        CHK(c->cand_small.reserve(CAND_WORDS));
-        HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+        CHK(counters_clear(c));
         HIPCHK(hipMemsetAsync(c->gl_key.p, 0xff, (size_t)nq * sizeof(unsigned long long), c->stream));
         // target rows per chunk: the ctx's switch, else whole tiles, as many chunks as bring the grid to MT_FILL workgroups
         const long nqb = (nq + MT_BLOCK - 1) / MT_BLOCK;
@@ -294,19 +264,15 @@ SICP_EXPORT int sicp_feature_match(sicp_ctx *c, const float *query, int64_t nq, 
         hipLaunchKernelGGL(k_match_finish, dim3((unsigned)std::min<long>(nqb, MT_MAX_QBLOCKS)), dim3(MT_BLOCK), 0, c->stream, c->gl_key.p,
                            (long)nq, idx, d2, c->cand_small.p);
         HIPCHK(hipGetLastError());
-        unsigned long long *hs = (unsigned long long *)(c->h_small + H_CAND);
-        HIPCHK(hipMemcpyAsync(hs, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        CHK(gl_leave(c, idx_out, (size_t)nq, idx));
-        CHK(gl_leave(c, d2_out, (size_t)nq, d2));
+        CHK(counters_fetch(c));
+        CHK(stage_leave(c, idx_out, (size_t)nq, idx));
+        CHK(stage_leave(c, d2_out, (size_t)nq, d2));
         CHK(sync(c));
         out->n_query = nq;
         out->n_target = nt;
-        out->n_unmatched = (int64_t)hs[0];
+        out->n_unmatched = (int64_t)counters_host(c)[0];
         return SICP_OK;
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }
 
 SICP_EXPORT int sicp_ransac_triplets(sicp_ctx *c, const double *src, const double *dst, int64_t m, const int32_t *triples, int64_t h,
@@ -325,18 +291,17 @@ SICP_EXPORT int sicp_ransac_triplets(sicp_ctx *c, const double *src, const doubl
     if (!std::isfinite(max_distance) || !(max_distance > 0.0)) return fail(SICP_ERR_INVALID, "max_distance must be finite and > 0");
     if (!(edge_ratio >= 0.0 && edge_ratio <= 1.0)) return fail(SICP_ERR_INVALID, "edge_ratio must be >= 0 and <= 1");
     HIPCHK(hipSetDevice(c->device));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         const double *s, *d;
         const int32_t *tri;
         double *poses;
         int32_t *inl;
-        CHK(gl_input(c, src, (size_t)3 * m, c->gl_src, &s));
-        CHK(gl_input(c, dst, (size_t)3 * m, c->gl_dst, &d));
-        CHK(gl_input(c, triples, (size_t)3 * h, c->gl_tri, &tri));
-        CHK(gl_output(c, poses_out, (size_t)12 * h, c->gl_pose, &poses));
-        CHK(gl_output(c, inliers_out, (size_t)h, c->gl_idx, &inl));
-        CHK(c->cand_small.reserve(CAND_WORDS));
-        HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+        CHK(stage_in(c, src, (size_t)3 * m, c->gl_src, &s));
+        CHK(stage_in(c, dst, (size_t)3 * m, c->gl_dst, &d));
+        CHK(stage_in(c, triples, (size_t)3 * h, c->gl_tri, &tri));
+        CHK(stage_out(c, poses_out, (size_t)12 * h, c->gl_pose, &poses));
+        CHK(stage_out(c, inliers_out, (size_t)h, c->gl_idx, &inl));
+        CHK(counters_clear(c));
         HIPCHK(hipMemsetAsync(c->cand_small.p + RS_BEST, 0xff, sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(k_ransac, dim3((unsigned)std::min<long>((h + RS_WAVES - 1) / RS_WAVES, RS_MAX_BLOCKS)), dim3(RS_BLOCK), 0, c->stream,
                            s, d, tri, poses, inl, c->cand_small.p, (long)m, (long)h, max_distance * max_distance, edge_ratio * edge_ratio);
@@ -344,19 +309,16 @@ SICP_EXPORT int sicp_ransac_triplets(sicp_ctx *c, const double *src, const doubl
         hipLaunchKernelGGL(k_ransac_best, dim3((unsigned)std::min<long>((h + RS_BLOCK - 1) / RS_BLOCK, RS_MAX_BLOCKS)), dim3(RS_BLOCK), 0,
                            c->stream, inl, (long)h, c->cand_small.p);
         HIPCHK(hipGetLastError());
-        unsigned long long *hs = (unsigned long long *)(c->h_small + H_CAND);
-        HIPCHK(hipMemcpyAsync(hs, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        CHK(gl_leave(c, poses_out, (size_t)12 * h, poses));
-        CHK(gl_leave(c, inliers_out, (size_t)h, inl));
+        CHK(counters_fetch(c));
+        CHK(stage_leave(c, poses_out, (size_t)12 * h, poses));
+        CHK(stage_leave(c, inliers_out, (size_t)h, inl));
         CHK(sync(c));
+        const unsigned long long *hs = counters_host(c);
         out->n_hypotheses = h;
         out->n_void = (int64_t)hs[RS_VOID];
         out->n_pruned = (int64_t)hs[RS_PRUNED];
         out->best = hs[RS_BEST1] ? (int64_t)hs[RS_BEST] : -1;
         out->best_inliers = (int64_t)hs[RS_BEST1] - 1;
         return SICP_OK;
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }

@@ -304,13 +304,12 @@ struct sicp_ctx {
     // positions (the kept rows themselves are stream-ordered memory of the call)
     DevBuf<uint32_t> sel_blk;
     DevBuf<int64_t> sel_pos;
-    // the candidates of a whole-cloud operator call (take_candidates: voxel selection, the outlier filters): their rows, the verdict
-    // bytes on their way out, CAND_WORDS counter words; one call at a time uses them and has synchronised before it returns; grown,
-    // never shrunk, gone with the ctx
+    // a whole-cloud operator call's candidates (take_candidates): their rows, the verdict bytes on their way out; and the counter
+    // words of every stand-alone operator (counters_clear / counters_fetch / counters_host below)
     DevBuf<int64_t> cand_rows;
     DevBuf<uint8_t> cand_keep;
     DevBuf<unsigned long long> cand_small;
-    // voxel selection (sicp_voxel.hip): the hash table of {key, winner} word pairs, every candidate's slot in it (cand_small's first
+    // voxel selection (sicp_voxel.hip): the hash table of {key, winner} word pairs, every candidate's slot in it (the first counter
     // word as two 32-bit ones: the kept count, the error bits)
     DevBuf<unsigned long long> vx_tab;
     DevBuf<uint32_t> vx_slot;
@@ -318,19 +317,17 @@ struct sicp_ctx {
     // way out; grown, never shrunk, gone with the ctx
     DevBuf<double> ev_part, ev_out;
     DevBuf<long long> ev_cnt;
-    // outlier filters (sicp_outlier.hip): d_i per position, the staged counts, the trees' partials (cand_small: [0..2] mean / std /
-    // threshold [4] kept); grown, never shrunk, gone with the ctx
+    // outlier filters (sicp_outlier.hip): d_i per position, the staged counts, the trees' partials (counter words: OL_*)
     DevBuf<double> ol_d, ol_part;
     DevBuf<uint32_t> ol_cnt;
     long outlier_chunk = 0;        // SICP_OUTLIER_CHUNK: candidates per search of the outlier filters (0: chosen per call; what a chunk holds is (chunk, k) distances)
-    // FPFH descriptors (sicp_fpfh.hip): the normals as they are used (oriented), the counts of pass 1 ((n, 34) uint16), the staged
-    // descriptors of a call whose output is host memory; grown, never shrunk, gone with the ctx
+    // FPFH descriptors (sicp_fpfh.hip): the normals as they are used (oriented), the counts of pass 1 ((n, 34) uint16), the staging
+    // buffer of the descriptors
     DevBuf<float> fp_nrm, fp_out;
     DevBuf<uint16_t> fp_cnt;
-    long fpfh_chunk = 0;           // SICP_FPFH_CHUNK: points per search of sicp_fpfh (0: chosen per call, as the outlier filters choose theirs)
-    // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row), the staged copies of the
-    // arrays a call hands over in host memory -- query and target rows, indices / inlier counts, distances; matched points, triples,
-    // poses; grown, never shrunk, gone with the ctx
+    long fpfh_chunk = 0;           // SICP_FPFH_CHUNK: points per search of sicp_fpfh (0: chosen per call)
+    // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
+    // the call's arrays
     DevBuf<unsigned long long> gl_key;
     DevBuf<float> gl_q, gl_t, gl_d2;
     DevBuf<int32_t> gl_idx, gl_tri;
@@ -463,6 +460,7 @@ inline bool ptr_on_device(const sicp_ctx *c, const void *p)
     (void)hipGetLastError();
     return false;
 }
+
 // operators whose answer needs every point on this rank refuse an exchange (`who` is not supported ... (`why`)); check_whole_cloud
 // also refuses a shard in `slot` and 2^31 points or more (check_below_2_31)
 int check_no_exchange(const sicp_ctx *c, const char *who, const char *why);
@@ -476,13 +474,77 @@ struct Candidates {
     long positions = 0;                // entries of every output
     bool by_position = false;          // results go to the candidate's ROW (masked form), not to its place in the list
 };
-constexpr int CAND_WORDS = 8;          // c->cand_small: cleared by take_candidates; [CAND_COUNT] belongs to it, the others to the operator
+constexpr int CAND_WORDS = 8;          // c->cand_small, the counter words: [CAND_COUNT] belongs to take_candidates, the others to the operator
 constexpr int CAND_COUNT = 5;          // the set bytes of a mask
-constexpr int H_CAND = 208;            // c->h_small + H_CAND: the pinned mirror of c->cand_small
+// c->h_small, H_SMALL_WORDS pinned doubles.  The run's words lie below H_LOOP_END (sicp_icp.cpp: 8..37 normal equations, 128..159
+// their polled copy, 160..175 statistics; sicp_clouds.cpp / sicp_device.hip: 40..46 cloud statistics, 54..55 grid build;
+// sicp_search.cpp: 62 the filtered scan's overflow word); the stand-alone operators' follow
+constexpr int H_SMALL_WORDS = 256, H_LOOP_END = 176;
+constexpr int H_EVAL = 192, H_EVAL_WORDS = 12;   // sicp_evaluate's record
+constexpr int H_CAND = 208;                      // the mirror of the counter words (counters_host)
+static_assert(H_LOOP_END <= H_EVAL && H_EVAL + H_EVAL_WORDS <= H_CAND && H_CAND + CAND_WORDS <= H_SMALL_WORDS, "h_small's regions are apart");
 // what a masked call does with its mask before anything else: enqueue the kernel that adds the number of set bytes to *d_count
 // (zero before) and say in *d_rows where it collected their rows (null: it only counted)
 typedef int (*MaskPass)(sicp_ctx *c, const uint8_t *mask, long n, unsigned long long *d_count, const int64_t **d_rows);
 int take_candidates(sicp_ctx *c, int slot, const int64_t *rows, int64_t m, const uint8_t *mask, MaskPass by_mask, Candidates *K);
+
+// ---- an operator call's frame ("An operator call's frame") ------------------------------------------------------------
+// body(), and on failure the stream drained: whatever the call enqueued is over before its caller sees the error
+template <class Body>
+int op_run(sicp_ctx *c, Body &&body)
+{
+    const int rc = body();
+    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+// the counter words: zeroed on the stream; copied to their pinned mirror on the stream; the mirror, good after sync(c)
+inline int counters_clear(sicp_ctx *c)
+{
+    CHK(c->cand_small.reserve(CAND_WORDS));
+    HIPCHK(hipMemsetAsync(c->cand_small.p, 0, CAND_WORDS * sizeof(unsigned long long), c->stream));
+    return SICP_OK;
+}
+inline unsigned long long *counters_host(const sicp_ctx *c) { return (unsigned long long *)(c->h_small + H_CAND); }
+inline int counters_fetch(sicp_ctx *c)
+{
+    HIPCHK(hipMemcpyAsync(counters_host(c), c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    return SICP_OK;
+}
+// `count` elements at p as the kernels read them: p itself if it is memory of the ctx's device, else a copy in `buf`
+template <class T>
+int stage_in(sicp_ctx *c, const T *p, size_t count, DevBuf<T> &buf, const T **dev)
+{
+    if (ptr_on_device(c, p)) { *dev = p; return SICP_OK; }
+    CHK(buf.reserve(count));
+    HIPCHK(hipMemcpyAsync(buf.p, p, count * sizeof(T), hipMemcpyDefault, c->stream));
+    *dev = buf.p;
+    return SICP_OK;
+}
+// where the kernels write `count` elements meant for p (null: nowhere): p itself or `buf`; stage_leave copies the staged ones out
+template <class T>
+int stage_out(sicp_ctx *c, T *p, size_t count, DevBuf<T> &buf, T **dev)
+{
+    if (!p || ptr_on_device(c, p)) { *dev = p; return SICP_OK; }
+    CHK(buf.reserve(count));
+    *dev = buf.p;
+    return SICP_OK;
+}
+template <class T>
+int stage_leave(sicp_ctx *c, T *p, size_t count, const T *dev)
+{
+    if (p && dev != p) HIPCHK(hipMemcpyAsync(p, dev, count * sizeof(T), hipMemcpyDefault, c->stream));
+    return SICP_OK;
+}
+// a chunked k-NN over rows of a slot (sicp_search.cpp): rows per search -- the ctx's switch, else as many as keep a chunk's
+// (chunk, k) distances and indices at 256 MiB; c->kq / k_d2 / k_idx for chunks of up to `most` rows; rows d_rows[lo, lo + cnt)
+// (null: rows lo, lo + 1, ...) as query columns in c->kq (stride round_up(cnt, QPAD)); ... searched: (cnt, k) in c->k_d2 / c->k_idx
+long knn_chunk(long forced, int k);
+int knn_chunk_reserve(sicp_ctx *c, long most, int k);
+void rows_gather(sicp_ctx *c, int slot, const int64_t *d_rows, long lo, long cnt);
+int rows_knn(sicp_ctx *c, int slot, const int64_t *d_rows, long lo, long cnt, int k);
+// the rows sel_idx[0, Q) of a cloud (host or device memory, staged in `sel`; null: rows 0 .. Q - 1) as query columns in c->kq;
+// *qpad_out: their stride
+int selected_queries(sicp_ctx *c, const Cloud &cl, const int64_t *sel_idx, long Q, DevBuf<int64_t> &sel, long *qpad_out);
 double key_to_double(unsigned long long k);
 int subsample_build(sicp_ctx *c, int slot);
 int grid_coarse_level(sicp_ctx *c, int slot, GridLevel *lv, const GridLevel **out);

@@ -45,6 +45,9 @@ __device__ __forceinline__ double lane_xor_f64(double v)
     return __longlong_as_double((long long)lane_xor64<J>((unsigned long long)__double_as_longlong(v)));
 }
 
+// neither NaN nor an infinity
+__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
 // wave-wide sum by a butterfly: every lane ends up with the total, in a fixed order
 __device__ __forceinline__ double wsum(double v)
 {

@@ -292,7 +292,7 @@ SICP_EXPORT int sicp_cloud_set_normals(sicp_ctx *c, int slot, const int64_t *row
         return sync(c);
     };
     if (rc == SICP_OK) rc = body();
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);                // (always, not op_run: the local buffers are released next)
     d_rows.release(); d_vals.release();
     if (rc == SICP_OK) cl.nv_n = n_global;
     return rc;

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restric
 
 namespace {
 
-enum { OL_MEAN = 0, OL_STD = 1, OL_THR = 2, OL_KEPT = 4 };     // words of c->cand_small (CAND_COUNT is the intake's)
+enum { OL_MEAN = 0, OL_STD = 1, OL_THR = 2, OL_KEPT = 4 };     // counter words (CAND_COUNT is the intake's)
 static_assert(OL_KEPT != CAND_COUNT && OL_THR < CAND_COUNT && OL_KEPT < CAND_WORDS, "the filters' words and the intake's are apart");
 
 // what both filters check alike
@@ -248,21 +248,7 @@ int ol_compact_mask(sicp_ctx *c, const uint8_t *mask, long n, unsigned long long
     return SICP_OK;
 }
 
-// candidates per search: the ctx's switch, else as many as keep a chunk's (chunk, k) distances and indices at 256 MiB
-long ol_chunk(const sicp_ctx *c, int k)
-{
-    if (c->outlier_chunk > 0) return c->outlier_chunk;
-    return std::max<long>(65536, (1L << 24) / std::max(k, 1));
-}
-
-// a chunk's candidates as query columns (c->kq): rows [lo, lo + cnt) of the list, or of the cloud itself
-void ol_gather(sicp_ctx *c, const Cloud &cl, const Candidates &K, long lo, long cnt, long qpad)
-{
-    if (K.d_rows) launch_gather_queries(c->stream, cl.x(), cl.y(), cl.z(), K.d_rows + lo, cnt, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
-    else launch_gather_queries(c->stream, cl.x() + lo, cl.y() + lo, cl.z() + lo, nullptr, cnt, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
-}
-
-// the outputs leave through staging buffers: host or device memory alike, and keep_out may alias the mask
+// the outputs always leave through staging buffers, host or device memory alike (no stage_out): keep_out may alias the mask
 int ol_deliver(sicp_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, c->stream));
@@ -307,7 +293,7 @@ SICP_EXPORT int sicp_outlier_statistical(sicp_ctx *c, int slot, const int64_t *r
     if (k > cl.n) return fail(SICP_ERR_INVALID, "k (%d) exceeds the number of points (%lld)", k, (long long)cl.n);
     if (!std::isfinite(std_ratio)) return fail(SICP_ERR_INVALID, "std_ratio must be finite");
     HIPCHK(hipSetDevice(c->device));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         Candidates K;
         CHK(take_candidates(c, slot, rows, m, mask, ol_compact_mask, &K));
         const long N = K.positions;
@@ -322,15 +308,11 @@ SICP_EXPORT int sicp_outlier_statistical(sicp_ctx *c, int slot, const int64_t *r
             return sync(c);
         }
         if (K.by_position) HIPCHK(hipMemsetAsync(c->ol_d.p, 0, (size_t)N * sizeof(double), c->stream));   // +0.0 where no candidate is
-        const long chunk = ol_chunk(c, k);
-        const long qpad_max = round_up(std::min(chunk, K.count), QPAD);
-        CHK(c->kq.reserve((size_t)3 * qpad_max));
-        CHK(c->k_d2.reserve((size_t)std::min(chunk, K.count) * k));
-        CHK(c->k_idx.reserve((size_t)std::min(chunk, K.count) * k));
+        const long chunk = knn_chunk(c->outlier_chunk, k);
+        CHK(knn_chunk_reserve(c, std::min(chunk, K.count), k));
         for (long lo = 0; lo < K.count; lo += chunk) {
-            const long cnt = std::min(chunk, K.count - lo), qpad = round_up(cnt, QPAD);
-            ol_gather(c, cl, K, lo, cnt, qpad);
-            CHK(knnk_device(c, slot, c->kq.p, cnt, qpad, k, c->k_d2.p, c->k_idx.p));
+            const long cnt = std::min(chunk, K.count - lo);
+            CHK(rows_knn(c, slot, K.d_rows, lo, cnt, k));
             hipLaunchKernelGGL(k_ol_mean, dim3(cdiv(cnt, OL_BLOCK)), dim3(OL_BLOCK), 0, c->stream, c->k_d2.p, cnt, k,
                                K.by_position ? K.d_rows + lo : nullptr, K.by_position ? c->ol_d.p : c->ol_d.p + lo);
             HIPCHK(hipGetLastError());
@@ -349,21 +331,18 @@ SICP_EXPORT int sicp_outlier_statistical(sicp_ctx *c, int slot, const int64_t *r
         const unsigned g = std::min(cdiv(N, OL_BLOCK), (unsigned)OL_MAX_BLOCKS);
         hipLaunchKernelGGL(k_ol_verdict, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->ol_d.p, K.d_mask, N, st, c->cand_keep.p, c->cand_small.p + OL_KEPT);
         HIPCHK(hipGetLastError());
-        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND);
-        HIPCHK(hipMemcpyAsync(h, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(counters_fetch(c));
         CHK(ol_deliver(c, keep_out, c->cand_keep.p, (size_t)N));
         CHK(ol_deliver(c, mean_dist_out, c->ol_d.p, (size_t)N * sizeof(double)));
         CHK(sync(c));
+        const unsigned long long *h = counters_host(c);
         out->n_candidates = (int64_t)K.count;
         out->n_kept = (int64_t)h[OL_KEPT];
         std::memcpy(&out->mean, h + OL_MEAN, sizeof(double));
         std::memcpy(&out->std, h + OL_STD, sizeof(double));
         std::memcpy(&out->threshold, h + OL_THR, sizeof(double));
         return SICP_OK;
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }
 
 SICP_EXPORT int sicp_outlier_radius_cells(sicp_ctx *c, int slot, double radius, int64_t out4[4])
@@ -386,9 +365,8 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
     if (!kept_out) return fail(SICP_ERR_INVALID, "kept_out is null");
     if (!std::isfinite(radius) || !(radius > 0.0)) return fail(SICP_ERR_INVALID, "radius must be finite and > 0");
     if (min_points < 0) return fail(SICP_ERR_INVALID, "min_points must be >= 0");
-    Cloud &cl = c->cloud[slot];
     HIPCHK(hipSetDevice(c->device));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         GridLevel lv; int64_t ext[3]; long cells = 0;
         CHK(ol_level(c, slot, radius, &lv, ext, &cells));
         if (cells > SICP_OUTLIER_MAX_BOX_CELLS)
@@ -410,7 +388,7 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
         CHK(c->kq.reserve((size_t)3 * round_up(std::min(chunk, std::max<long>(K.count, 1)), QPAD)));
         for (long lo = 0; lo < K.count; lo += chunk) {
             const long cnt = std::min(chunk, K.count - lo), qpad = round_up(cnt, QPAD);
-            ol_gather(c, cl, K, lo, cnt, qpad);
+            rows_gather(c, slot, K.d_rows, lo, cnt);
             const uint32_t *order = nullptr;
             if (c->order_min_q > 0 && cnt >= c->order_min_q) {
                 CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, 2.0 * lv.g.h, 1L << 22, c->k_order));
@@ -424,15 +402,11 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
                                c->cand_small.p + OL_KEPT, c->count_work ? c->match_work.p : nullptr);
             HIPCHK(hipGetLastError());
         }
-        unsigned long long *h = (unsigned long long *)(c->h_small + H_CAND);
-        HIPCHK(hipMemcpyAsync(h, c->cand_small.p, CAND_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        CHK(counters_fetch(c));
         CHK(ol_deliver(c, keep_out, c->cand_keep.p, (size_t)N));
         CHK(ol_deliver(c, count_out, c->ol_cnt.p, (size_t)N * sizeof(uint32_t)));
         CHK(sync(c));
-        *kept_out = (int64_t)h[OL_KEPT];
+        *kept_out = (int64_t)counters_host(c)[OL_KEPT];
         return SICP_OK;
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }

@@ -321,6 +321,42 @@ int knnk_device(sicp_ctx *c, int slot, const double *qsoa, long Q, long qpad, in
     return SICP_OK;
 }
 
+long knn_chunk(long forced, int k) { return forced > 0 ? forced : std::max<long>(65536, (1L << 24) / std::max(k, 1)); }
+
+int knn_chunk_reserve(sicp_ctx *c, long most, int k)
+{
+    CHK(c->kq.reserve((size_t)3 * round_up(most, QPAD)));
+    CHK(c->k_d2.reserve((size_t)most * k));
+    return c->k_idx.reserve((size_t)most * k);
+}
+
+void rows_gather(sicp_ctx *c, int slot, const int64_t *d_rows, long lo, long cnt)
+{
+    const Cloud &cl = c->cloud[slot];
+    const long qpad = round_up(cnt, QPAD), at = d_rows ? 0 : lo;
+    launch_gather_queries(c->stream, cl.x() + at, cl.y() + at, cl.z() + at, d_rows ? d_rows + lo : nullptr, cnt, qpad, c->kq.p,
+                          c->kq.p + qpad, c->kq.p + 2 * qpad);
+}
+
+int rows_knn(sicp_ctx *c, int slot, const int64_t *d_rows, long lo, long cnt, int k)
+{
+    rows_gather(c, slot, d_rows, lo, cnt);
+    return knnk_device(c, slot, c->kq.p, cnt, round_up(cnt, QPAD), k, c->k_d2.p, c->k_idx.p);
+}
+
+int selected_queries(sicp_ctx *c, const Cloud &cl, const int64_t *sel_idx, long Q, DevBuf<int64_t> &sel, long *qpad_out)
+{
+    const long qpad = round_up(Q, QPAD);
+    CHK(c->kq.reserve((size_t)3 * qpad));
+    if (sel_idx) {
+        CHK(sel.reserve((size_t)Q));
+        HIPCHK(hipMemcpyAsync(sel.p, sel_idx, (size_t)Q * sizeof(int64_t), hipMemcpyDefault, c->stream));
+    }
+    launch_gather_queries(c->stream, cl.x(), cl.y(), cl.z(), sel_idx ? sel.p : nullptr, Q, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
+    *qpad_out = qpad;
+    return SICP_OK;
+}
+
 }  // namespace sicph
 
 // ------------------------------------------------------------------------------------------
@@ -368,20 +404,14 @@ SICP_EXPORT int sicp_select_in_range(sicp_ctx *c, int query_slot, int search_slo
     if (Q <= 0) return fail(SICP_ERR_INVALID, "Q must be > 0");
     if (qc.idx_base != 0) return fail(SICP_ERR_INVALID, "the query cloud must not be a shard");
     HIPCHK(hipSetDevice(c->device));
-    const long qpad = round_up(Q, QPAD);
-    CHK(c->kq.reserve((size_t)3 * qpad));
     CHK(c->k_d2.reserve((size_t)Q));
     CHK(c->k_idx.reserve((size_t)Q));
     DevBuf<int64_t> sel; DevBuf<uint8_t> mask;
     int rc = mask.reserve(Q);
-    if (rc == SICP_OK && sel_idx) rc = sel.reserve(Q);
     auto body = [&]() -> int {
-        if (sel_idx) {
-            CHK(check_rows(sel_idx, Q, qc.n, "sel_idx"));
-            HIPCHK(hipMemcpyAsync(sel.p, sel_idx, (size_t)Q * sizeof(int64_t), hipMemcpyDefault, c->stream));
-        }
-        launch_gather_queries(c->stream, qc.x(), qc.y(), qc.z(), sel_idx ? sel.p : nullptr, Q, qpad, c->kq.p, c->kq.p + qpad,
-                              c->kq.p + 2 * qpad);
+        if (sel_idx) CHK(check_rows(sel_idx, Q, qc.n, "sel_idx"));
+        long qpad;
+        CHK(selected_queries(c, qc, sel_idx, Q, sel, &qpad));
         Xf X;
         if (H) H16_to_Xf(H, &X);
         CHK(knn1_device(c, search_slot, c->kq.p, Q, qpad, H ? &X : nullptr, max_range, nullptr, c->k_d2.p, c->k_idx.p, nullptr));
@@ -392,7 +422,7 @@ SICP_EXPORT int sicp_select_in_range(sicp_ctx *c, int query_slot, int search_slo
         return sync(c);
     };
     if (rc == SICP_OK) rc = body();
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);                // (always, not op_run: the local buffers are released next)
     sel.release(); mask.release();
     return rc;
 }
@@ -416,36 +446,29 @@ SICP_EXPORT int sicp_evaluate(sicp_ctx *c, int query_slot, int search_slot, cons
     if (Q <= 0) return fail(SICP_ERR_INVALID, "Q must be > 0");
     HIPCHK(hipSetDevice(c->device));
     if (sel_idx) CHK(check_rows(sel_idx, Q, qc.n, "sel_idx"));
-    static_assert(sizeof(sicp_eval) == 12 * sizeof(double), "the record is twelve 8-byte words");
-    const long qpad = round_up(Q, QPAD);
+    static_assert(sizeof(sicp_eval) == H_EVAL_WORDS * sizeof(double), "the record is twelve 8-byte words");
     const long nb = eval_partials_count(Q);
-    CHK(c->kq.reserve((size_t)3 * qpad));
     CHK(c->k_d2.reserve((size_t)Q));
     CHK(c->k_idx.reserve((size_t)Q));
-    // (scratch kept with the ctx, as sicp_estimate_normals keeps its own: at small Q a hipMalloc costs more than both kernels)
-    if (sel_idx) CHK(c->k_sel.reserve((size_t)Q));
+    // (scratch kept with the ctx, c->k_sel as sicp_estimate_normals keeps its own: at small Q a hipMalloc costs more than both kernels)
     CHK(c->ev_part.reserve((size_t)10 * (nb + (nb + 255) / 256)));
     CHK(c->ev_cnt.reserve((size_t)nb));
     CHK(c->ev_out.reserve(12));
-    auto body = [&]() -> int {
-        if (sel_idx) HIPCHK(hipMemcpyAsync(c->k_sel.p, sel_idx, (size_t)Q * sizeof(int64_t), hipMemcpyDefault, c->stream));
-        launch_gather_queries(c->stream, qc.x(), qc.y(), qc.z(), sel_idx ? c->k_sel.p : nullptr, Q, qpad, c->kq.p, c->kq.p + qpad,
-                              c->kq.p + 2 * qpad);
+    return op_run(c, [&]() -> int {
+        long qpad;
+        CHK(selected_queries(c, qc, sel_idx, Q, c->k_sel, &qpad));
         Xf X;
         if (H) H16_to_Xf(H, &X);
         CHK(knn1_device(c, search_slot, c->kq.p, Q, qpad, H ? &X : nullptr, max_distance, nullptr, c->k_d2.p, c->k_idx.p, nullptr));
         launch_eval(c->stream, c->k_idx.p, c->k_d2.p, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, Q, c->ev_part.p, c->ev_cnt.p,
                     c->ev_out.p);
         HIPCHK(hipGetLastError());
-        double *h_rec = c->h_small + 192;                 // pinned: the record's twelve words
-        HIPCHK(hipMemcpyAsync(h_rec, c->ev_out.p, 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        double *h_rec = c->h_small + H_EVAL;              // pinned: the record's twelve words
+        HIPCHK(hipMemcpyAsync(h_rec, c->ev_out.p, H_EVAL_WORDS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         CHK(sync(c));
         std::memcpy(out, h_rec, sizeof *out);
         return SICP_OK;
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }
 
 SICP_EXPORT int sicp_estimate_normals(sicp_ctx *c, int slot, const int64_t *sel_idx, int64_t Q, int k, float *normals_out,
@@ -459,20 +482,17 @@ SICP_EXPORT int sicp_estimate_normals(sicp_ctx *c, int slot, const int64_t *sel_
     if (k > cl.n) return fail(SICP_ERR_INVALID, "neighbors (%d) exceeds the number of points (%lld)", k, (long long)cl.n);
     CHK(check_rows(sel_idx, Q, cl.n, "sel_idx"));
     HIPCHK(hipSetDevice(c->device));
-    const long qpad = round_up(Q, QPAD);
-    CHK(c->kq.reserve((size_t)3 * qpad));
     // the one-sweep kernel keeps the neighbours on chip: the (Q, k) index / distance arrays exist only when the caller wants them
     const bool sweep = c->knn_sweep && knnk_uses_grid(c, cl, Q) && grid_knn_sweep_handles(k);
     const bool want_lists = !sweep || nn_idx_out;
     if (want_lists) { CHK(c->k_d2.reserve((size_t)Q * k)); CHK(c->k_idx.reserve((size_t)Q * k)); }
     // (scratch kept with the ctx: a hipMalloc / hipFree pair per call costs more than the kernels at Q = 1000)
-    DevBuf<int64_t> &sel = c->k_sel; DevBuf<float> &nv = c->k_nv, &pl = c->k_pl;
-    int rc = sel.reserve(Q);
-    if (rc == SICP_OK) rc = nv.reserve((size_t)3 * Q);
-    if (rc == SICP_OK) rc = pl.reserve(Q);
-    auto body = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(sel.p, sel_idx, (size_t)Q * sizeof(int64_t), hipMemcpyDefault, c->stream));
-        launch_gather_queries(c->stream, cl.x(), cl.y(), cl.z(), sel.p, Q, qpad, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad);
+    DevBuf<float> &nv = c->k_nv, &pl = c->k_pl;
+    return op_run(c, [&]() -> int {
+        long qpad;
+        CHK(selected_queries(c, cl, sel_idx, Q, c->k_sel, &qpad));
+        CHK(nv.reserve((size_t)3 * Q));
+        CHK(pl.reserve(Q));
         bool fused = false;
         CHK(knnk_device(c, slot, c->kq.p, Q, qpad, k, want_lists ? c->k_d2.p : nullptr, want_lists ? c->k_idx.p : nullptr, nv.p, pl.p,
                         &fused));
@@ -482,9 +502,6 @@ SICP_EXPORT int sicp_estimate_normals(sicp_ctx *c, int slot, const int64_t *sel_
         HIPCHK(hipMemcpyAsync(planarity_out, pl.p, (size_t)Q * sizeof(float), hipMemcpyDefault, c->stream));
         if (nn_idx_out) HIPCHK(hipMemcpyAsync(nn_idx_out, c->k_idx.p, (size_t)Q * k * sizeof(int64_t), hipMemcpyDefault, c->stream));
         return sync(c);
-    };
-    if (rc == SICP_OK) rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }
 

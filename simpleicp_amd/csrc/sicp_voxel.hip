@@ -155,7 +155,7 @@ int vx_run(sicp_ctx *c, int slot, const Candidates &K, const VoxelLattice &L, ui
     while (cap < 2 * (size_t)K.count) cap <<= 1;                    // load <= 0.5; fewer than 2^31 candidates, so at most 2^32 slots: their numbers fit 32 bits
     CHK(c->vx_tab.reserve(2 * cap));
     CHK(c->vx_slot.reserve((size_t)m));
-    unsigned *cnt = (unsigned *)c->cand_small.p;                    // two 32-bit words of its own, written and read as such: [0] the kept [1] the error bits (cleared by take_candidates)
+    unsigned *cnt = (unsigned *)c->cand_small.p;                    // the first counter word as two 32-bit ones, written and read as such: [0] the kept [1] the error bits (cleared by take_candidates)
     HIPCHK(hipMemsetAsync(c->vx_tab.p, 0xff, 2 * cap * sizeof(unsigned long long), c->stream));
     const unsigned g = std::min(cdiv(m, VX_BLOCK), (unsigned)VX_MAX_BLOCKS);
     hipLaunchKernelGGL(k_voxel_insert, dim3(g), dim3(VX_BLOCK), 0, c->stream, cl.x(), cl.y(), cl.z(), K.d_rows, K.d_mask, m, L, c->vx_tab.p,
@@ -163,9 +163,10 @@ int vx_run(sicp_ctx *c, int slot, const Candidates &K, const VoxelLattice &L, ui
     hipLaunchKernelGGL(k_voxel_verdict, dim3(g), dim3(VX_BLOCK), 0, c->stream, K.d_rows, K.d_mask, m, c->vx_tab.p, c->vx_slot.p, d_keep,
                        cnt);
     HIPCHK(hipGetLastError());
-    unsigned h_cnt[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+    CHK(counters_fetch(c));
     CHK(sync(c));
+    unsigned h_cnt[2];
+    std::memcpy(h_cnt, counters_host(c), sizeof h_cnt);
     if (h_cnt[1] & 1u) return fail(SICP_ERR_INVALID, "a point lies outside the voxel lattice of the slot's bounding box (internal error)");
     if (h_cnt[1] & 2u) return fail(SICP_ERR_INVALID, "the voxel hash table is full (internal error)");
     *kept_out = (int64_t)h_cnt[0];
@@ -185,21 +186,16 @@ SICP_EXPORT int sicp_voxel_select(sicp_ctx *c, int slot, const int64_t *rows, in
     CHK(vx_lattice(c, slot, cell, origin, &L));
     CHK(check_candidate_rows(rows, m, c->cloud[slot].n));
     HIPCHK(hipSetDevice(c->device));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         Candidates K;
         CHK(take_candidates(c, slot, rows, m, nullptr, nullptr, &K));
-        // verdicts for device memory of this device are written where the caller wants them; for the host they are staged
-        hipPointerAttribute_t at;
-        const bool direct = hipPointerGetAttributes(&at, keep_out) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
-        if (!direct) { (void)hipGetLastError(); CHK(c->cand_keep.reserve((size_t)K.positions)); }
-        CHK(vx_run(c, slot, K, L, direct ? keep_out : c->cand_keep.p, kept_out));
-        if (direct) return SICP_OK;
-        HIPCHK(hipMemcpyAsync(keep_out, c->cand_keep.p, (size_t)K.positions, hipMemcpyDefault, c->stream));
+        uint8_t *d_keep;
+        CHK(stage_out(c, keep_out, (size_t)K.positions, c->cand_keep, &d_keep));
+        CHK(vx_run(c, slot, K, L, d_keep, kept_out));
+        if (d_keep == keep_out) return SICP_OK;
+        CHK(stage_leave(c, keep_out, (size_t)K.positions, d_keep));
         return sync(c);
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }
 
 SICP_EXPORT int sicp_voxel_select_masked(sicp_ctx *c, int slot, const uint8_t *mask, int64_t n, double cell, const double *origin,
@@ -212,7 +208,7 @@ SICP_EXPORT int sicp_voxel_select_masked(sicp_ctx *c, int slot, const uint8_t *m
     if (n != c->cloud[slot].n) return fail(SICP_ERR_INVALID, "n must be the slot's size (%lld points)", (long long)c->cloud[slot].n);
     HIPCHK(hipSetDevice(c->device));
     CHK(check_device_ptr(c, keep_out, "keep_out"));
-    auto body = [&]() -> int {
+    return op_run(c, [&]() -> int {
         Candidates K;
         CHK(take_candidates(c, slot, nullptr, 0, mask, vx_count_mask, &K));
         if (K.count == 0) {
@@ -221,8 +217,5 @@ SICP_EXPORT int sicp_voxel_select_masked(sicp_ctx *c, int slot, const uint8_t *m
             return sync(c);
         }
         return vx_run(c, slot, K, L, keep_out, kept_out);
-    };
-    const int rc = body();
-    if (rc != SICP_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    });
 }
