@@ -81,6 +81,12 @@ GLOBAL_EXPORTS = ["sicp_global_version", "sicp_feature_match", "sicp_ransac_trip
 GLOBAL_VERSION = 1
 MATCH_MAX_DIM = 64
 
+# include/simpleicp_hip_posefit.h: least-squares poses of matched rows, the same kind of companion
+POSEFIT_EXPORTS = ["sicp_posefit_version", "sicp_pose_refit"]
+POSEFIT_VERSION = 1
+POSEFIT_MAX_ROUNDS = 64
+POSEFIT_SWEEPS = 6
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -130,6 +136,16 @@ class RansacStats(C.Structure):
 
     def as_dict(self):
         return dict(n_hypotheses=int(self.n_hypotheses), n_void=int(self.n_void), n_pruned=int(self.n_pruned), best=int(self.best),
+                    best_inliers=int(self.best_inliers))
+
+
+class PosefitStats(C.Structure):
+    """struct sicp_posefit_stats (contract (L)): 40 bytes."""
+    _fields_ = [("n_poses", C.c_int64), ("n_void", C.c_int64), ("n_improved", C.c_int64), ("best", C.c_int64),
+                ("best_inliers", C.c_int64)]
+
+    def as_dict(self):
+        return dict(n_poses=int(self.n_poses), n_void=int(self.n_void), n_improved=int(self.n_improved), best=int(self.best),
                     best_inliers=int(self.best_inliers))
 
 
@@ -193,6 +209,8 @@ FEATURES = {
     "global": _Feature(GLOBAL_EXPORTS, "simpleicp_hip_global.h", "global-registration", GLOBAL_VERSION, {
         "sicp_feature_match": [_vp, _vp, _i64, _vp, _i64, _cint, _vp, _vp, C.POINTER(MatchStats)],
         "sicp_ransac_triplets": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _dbl, _vp, _vp, C.POINTER(RansacStats)]}),
+    "posefit": _Feature(POSEFIT_EXPORTS, "simpleicp_hip_posefit.h", "pose-refit", POSEFIT_VERSION, {
+        "sicp_pose_refit": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _cint, _vp, _vp, C.POINTER(PosefitStats)]}),
 }
 
 _lib = None
@@ -336,6 +354,7 @@ eval_version = partial(_feature_version, "evaluation")
 outlier_version = partial(_feature_version, "outlier")
 fpfh_version = partial(_feature_version, "fpfh")
 global_version = partial(_feature_version, "global")
+posefit_version = partial(_feature_version, "posefit")
 
 
 def select_positions(m, Q):
@@ -780,6 +799,31 @@ class Context:
         self._chk(self._L.sicp_ransac_triplets(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(tri), tri.shape[0], float(max_distance),
                                                float(edge_ratio), _ptr(poses), _ptr(inl), C.byref(st)))
         return poses, inl, st
+
+    # -- least-squares poses of matched rows (contract (L)) --
+    def pose_refit(self, src, dst, poses, max_distance, rounds, m=None, b=None, poses_ptr=None, inliers_ptr=None):
+        """sicp_pose_refit: every pose refitted on its own inliers among the matched rows src[c] <-> dst[c] in `rounds` rounds
+        (contract (L)); what leaves is the pose with the most inliers among the one given and every round's.  poses None: the
+        plain least-squares fit of all finite rows (b = 1).  Host form: (m, 3) float64 arrays and (b, 12) float64 poses -- R
+        row-major, then t --; returns ((b, 12) float64 poses, (b,) int32 inliers: -1 void, PosefitStats).  Pointer form: src, dst
+        and poses (or None) are addresses (ints) of host or device memory, m and b given; the poses are left at poses_ptr
+        (b * 12 doubles), the inliers at inliers_ptr (b int32), and the PosefitStats alone is returned."""
+        posefit_version()
+        st = PosefitStats()
+        if inliers_ptr is not None:
+            self._chk(self._L.sicp_pose_refit(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m),
+                                              None if poses is None else C.c_void_p(int(poses)), int(b), float(max_distance), int(rounds),
+                                              C.c_void_p(int(poses_ptr)), C.c_void_p(int(inliers_ptr)), C.byref(st)))
+            return st
+        s, d = _f64(src), _f64(dst)
+        p = None if poses is None else _f64(poses)
+        if s.ndim != 2 or s.shape[1] != 3 or d.shape != s.shape or (p is not None and (p.ndim != 2 or p.shape[1] != 12)):
+            raise ValueError("src and dst must be (m, 3), poses (b, 12) or None")
+        n = 1 if p is None else p.shape[0]
+        out, inl = np.empty((n, 12), np.float64), np.empty(n, np.int32)
+        self._chk(self._L.sicp_pose_refit(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds), _ptr(out),
+                                          _ptr(inl), C.byref(st)))
+        return out, inl, st
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):

@@ -308,6 +308,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->fp_nrm.release(); c->fp_out.release(); c->fp_cnt.release();
     c->gl_key.release(); c->gl_q.release(); c->gl_t.release(); c->gl_d2.release(); c->gl_idx.release(); c->gl_tri.release();
     c->gl_src.release(); c->gl_dst.release(); c->gl_pose.release();
+    c->pf_in.release(); c->pf_state.release(); c->pf_part.release(); c->pf_part2.release(); c->pf_cnt.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

@@ -333,6 +333,10 @@ struct sicp_ctx {
     DevBuf<int32_t> gl_idx, gl_tri;
     DevBuf<double> gl_src, gl_dst, gl_pose;
     long match_chunk = 0;          // SICP_MATCH_CHUNK: target rows per chunk of sicp_feature_match (0: chosen per call)
+    // least-squares poses (sicp_posefit.hip): the staged input poses, the poses' states between the launches, the spans' partial
+    // sums and the level above them, the spans' inlier counts (src, dst and the outputs are staged in the gl_ buffers)
+    DevBuf<double> pf_in, pf_state, pf_part, pf_part2;
+    DevBuf<uint32_t> pf_cnt;
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

@@ -5,6 +5,10 @@ Contracts (M) and (R), DESIGN.md section 18 (include/simpleicp_hip_global.h).  `
 inliers -- all on the GPU, reproducible bit for bit; the random triples are drawn on the host from a seed.  ``register_global`` is
 the three in a row.  What comes back is a coarse pose and its runners-up: ``run_batch`` over ``candidates`` with
 ``evaluate_distance=`` refines and ranks them.
+
+Contract (L), DESIGN.md section 19 (include/simpleicp_hip_posefit.h): ``fit_pose`` is the least-squares rigid fit of matched
+rows, ``refine_pose`` refits poses on their own inliers, and ``register_global(..., refine=r)`` sends its ``top`` candidates
+through that refit before it ranks them.
 """
 from __future__ import annotations
 
@@ -21,12 +25,15 @@ class GlobalResult:
     """What ``ransac_pose`` and ``register_global`` return.  ``H``: the best pose as a 4x4 float64 array (None: no hypothesis was
     valid); ``inliers`` and ``index``: its inlier count and the row of its triple (-1: none); ``stats``: the call's record
     (n_hypotheses, n_void, n_pruned, best, best_inliers); ``candidates``: the ``top`` best as ``(H, inliers, index)``, ordered by
-    ``(-inliers, index)``; ``n_matches``: the matches the poses were drawn from (``register_global`` only)."""
+    ``(-inliers, index)``; ``n_matches``: the matches the poses were drawn from (``register_global`` only); ``refined``: the
+    record of the refit the candidates went through (n_poses, n_void, n_improved, best, best_inliers -- ``best`` a position among
+    the unrefined candidates), None without one."""
 
-    def __init__(self, candidates, stats, n_matches=None):
+    def __init__(self, candidates, stats, n_matches=None, refined=None):
         self.candidates = list(candidates)
         self.stats = dict(stats)
         self.n_matches = n_matches
+        self.refined = None if refined is None else dict(refined)
         self.H, self.inliers, self.index = self.candidates[0] if self.candidates else (None, -1, -1)
 
     def __repr__(self):
@@ -197,16 +204,8 @@ def _best(inliers, top):
     return order[:top]
 
 
-def ransac_pose(src, dst, *, max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1):
-    """The pose R, t that brings ``src[c]`` onto ``dst[c]`` for the most rows c (contract (R), DESIGN.md section 18): every triple
-    of matches gives one pose -- the minimal solver, exact for congruent triangles; triples whose edge lengths differ by more
-    than ``edge_ratio`` are pruned first (Open3D's edge-length checker) -- and a pose's score is the number of rows within
-    ``max_distance`` (strict).  A coarse pose: ICP refines it.
-
-    ``src``, ``dst``: (m, 3) matched points, both numpy arrays or both CUDA torch tensors; float32 is widened exactly.
-    ``triples``: (h, 3) integers; None: ``np.random.default_rng(seed).integers(0, m, (hypotheses, 3), dtype=np.int32)``, drawn on
-    the host (a repeated index is simply a void hypothesis).  Returns a ``GlobalResult``; its ``candidates`` are the ``top`` best."""
-    d, h, r, s, tri, top = ransac_arguments(max_distance, hypotheses, edge_ratio, seed, triples, top)
+def _matched_rows(src, dst):
+    """(on_device, src, dst, m) of two sets of matched rows, checked: both numpy (made float64) or both CUDA tensors."""
     on_device = _is_torch(src) or _is_torch(dst)
     if on_device:
         import torch
@@ -227,26 +226,134 @@ def ransac_pose(src, dst, *, max_distance, hypotheses=4096, edge_ratio=0.9, seed
         raise ValueError(f"a pose needs at least 3 matches, not {m}")
     if m >= 2**31:
         raise ValueError("src must have fewer than 2^31 rows")
+    return on_device, src, dst, m
+
+
+def _on_device_f64(ctx, src, dst):
+    """The tensors as the kernels read them (float32 widened exactly), the library's stream behind torch's."""
+    import torch
+    S, D = src.to(torch.float64).contiguous(), dst.to(torch.float64).contiguous()
+    _wait_for_torch(ctx, S.device)
+    return S, D
+
+
+def _refit(ctx, on_device, S, D, m, poses, max_distance, rounds):
+    """sicp_pose_refit on rows that are where they are: (poses (b, 12), inliers (b,) int32, the record as a dict).  The poses
+    (None: the plain fit) and the results are a few hundred bytes of host memory on either road."""
+    if not on_device:
+        out, inl, st = ctx.pose_refit(S, D, poses, max_distance, rounds)
+    else:
+        b = 1 if poses is None else len(poses)
+        out, inl = np.empty((b, 12), np.float64), np.empty(b, np.int32)
+        st = ctx.pose_refit(S.data_ptr(), D.data_ptr(), None if poses is None else poses.ctypes.data, max_distance, rounds, m=m, b=b,
+                            poses_ptr=out.ctypes.data, inliers_ptr=inl.ctypes.data)
+    return out, inl, st.as_dict() if hasattr(st, "as_dict") else dict(st)
+
+
+def _ransac_pose(src, dst, max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1, refine=0):
+    """ransac_pose, and with refine >= 1 the refit of its candidates."""
+    d, h, r, s, tri, top = ransac_arguments(max_distance, hypotheses, edge_ratio, seed, triples, top)
+    refine = _int_in("refine", refine, 0, _lib.POSEFIT_MAX_ROUNDS)
+    on_device, src, dst, m = _matched_rows(src, dst)
     _refuse_distributed("ransac_pose")
     if tri is None:
         tri = np.random.default_rng(s).integers(0, m, (h, 3), dtype=np.int32)
     ctx = _context("ransac_triplets")
+    if refine and not hasattr(ctx, "pose_refit"):
+        raise _lib.BackendError("this backend has no pose refit")
     if on_device:
-        S, D = src.to(torch.float64).contiguous(), dst.to(torch.float64).contiguous()
+        import torch
+        S, D = _on_device_f64(ctx, src, dst)
         poses_d = torch.empty((len(tri), 12), dtype=torch.float64, device=S.device)
         inl_d = torch.empty(len(tri), dtype=torch.int32, device=S.device)
-        _wait_for_torch(ctx, S.device)
         st = ctx.ransac_triplets(S.data_ptr(), D.data_ptr(), tri.ctypes.data, d, r, m=m, h=len(tri), poses_ptr=poses_d.data_ptr(),
                                  inliers_ptr=inl_d.data_ptr())
         inl = inl_d.cpu().numpy()
         rows = _best(inl, top)
         poses = poses_d[torch.as_tensor(rows, device=S.device)].cpu().numpy() if len(rows) else np.empty((0, 12))
     else:
+        S, D = src, dst
         allp, inl, st = ctx.ransac_triplets(src, dst, tri, d, r)
         rows = _best(inl, top)
         poses = allp[rows]
     stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
-    return GlobalResult([(_as_H(p), int(inl[k]), int(k)) for p, k in zip(poses, rows)], stats)
+    counts, refined = inl[rows], None
+    if refine and len(rows):
+        # the `top` candidates refitted on their own inliers (contract (L)) while the rows are where they are, then ranked again
+        poses, counts, refined = _refit(ctx, on_device, S, D, m, np.ascontiguousarray(poses, dtype=np.float64), d, refine)
+        again = np.lexsort((rows, -counts.astype(np.int64)))
+        poses, counts, rows = poses[again], counts[again], rows[again]
+    return GlobalResult([(_as_H(p), int(n), int(k)) for p, n, k in zip(poses, counts, rows)], stats, refined=refined)
+
+
+def ransac_pose(src, dst, *, max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1):
+    """The pose R, t that brings ``src[c]`` onto ``dst[c]`` for the most rows c (contract (R), DESIGN.md section 18): every triple
+    of matches gives one pose -- the minimal solver, exact for congruent triangles; triples whose edge lengths differ by more
+    than ``edge_ratio`` are pruned first (Open3D's edge-length checker) -- and a pose's score is the number of rows within
+    ``max_distance`` (strict).  A coarse pose: ``refine_pose`` refits it on its inliers, ICP refines it.
+
+    ``src``, ``dst``: (m, 3) matched points, both numpy arrays or both CUDA torch tensors; float32 is widened exactly.
+    ``triples``: (h, 3) integers; None: ``np.random.default_rng(seed).integers(0, m, (hypotheses, 3), dtype=np.int32)``, drawn on
+    the host (a repeated index is simply a void hypothesis).  Returns a ``GlobalResult``; its ``candidates`` are the ``top`` best."""
+    return _ransac_pose(src, dst, max_distance, hypotheses, edge_ratio, seed, triples, top)
+
+
+# ---- least-squares poses (contract (L)) ----
+def _refit_distance(max_distance):
+    d = _number("max_distance", max_distance)
+    if math.isnan(d) or not d > 0.0:
+        raise ValueError(f"max_distance must be > 0 (math.inf: every row counts), not {max_distance!r}")
+    return d
+
+
+def _refit_context():
+    ctx = backend.get_context()
+    if not hasattr(ctx, "pose_refit"):
+        raise _lib.BackendError("this backend has no pose refit")
+    dist.detach(ctx)
+    return ctx
+
+
+def fit_pose(src, dst):
+    """The rigid pose that brings ``src[c]`` closest to ``dst[c]`` in the least-squares sense over all rows whose six coordinates
+    are finite (Kabsch / Horn; contract (L)): centroids and centred cross sums by the fixed pair tree, the
+    rotation from the top eigenvector of Horn's 4x4 matrix by a fixed number of Jacobi sweeps -- the same bits on every run.
+
+    ``src``, ``dst``: (m, 3) matched points, m >= 3, both numpy arrays or both CUDA torch tensors; float32 is widened exactly.
+    Returns the 4x4 float64 ``H``; None when fewer than three rows are finite or the fit is not."""
+    on_device, src, dst, m = _matched_rows(src, dst)
+    _refuse_distributed("fit_pose")
+    ctx = _refit_context()
+    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+    poses, inl, _ = _refit(ctx, on_device, S, D, m, None, math.inf, 1)
+    return _as_H(poses[0]) if inl[0] >= 0 else None
+
+
+def refine_pose(src, dst, H, *, max_distance, rounds=3):
+    """Poses refitted on their own inliers (contract (L)): per round the least-squares fit (``fit_pose``'s)
+    of the rows within ``max_distance`` (strict; ``math.inf``: every row at a finite distance) of their partner under the
+    current pose; the next round starts from that fit.  What comes back is the pose with the most inliers among the one given
+    and every round's -- the earliest on a tie, so never a pose with fewer inliers than the one that went in.
+
+    ``src``, ``dst`` as for ``fit_pose``; ``H``: one 4x4 pose or a stack (b, 4, 4).  Returns ``(H, inliers)`` in the same shape:
+    float64 poses and their inlier counts (an int, or a (b,) int64 array); a pose with a non-finite entry comes back as zeros
+    with -1."""
+    d = _refit_distance(max_distance)
+    r = _int_in("rounds", rounds, 1, _lib.POSEFIT_MAX_ROUNDS)
+    if _is_torch(H):
+        H = H.detach().cpu().numpy()
+    H = np.asarray(H, dtype=np.float64)
+    if H.shape[-2:] != (4, 4) or H.ndim not in (2, 3) or H.shape[0] < 1:
+        raise ValueError(f"H must have shape (4, 4) or (b, 4, 4), b >= 1, not {H.shape}")
+    on_device, src, dst, m = _matched_rows(src, dst)
+    _refuse_distributed("refine_pose")
+    stack = H.reshape(-1, 4, 4)
+    poses = np.ascontiguousarray(np.concatenate([stack[:, :3, :3].reshape(-1, 9), stack[:, :3, 3]], axis=1))
+    ctx = _refit_context()
+    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+    out, inl, _ = _refit(ctx, on_device, S, D, m, poses, d, r)
+    Hs = np.stack([_as_H(p) if n >= 0 else np.zeros((4, 4)) for p, n in zip(out, inl)])
+    return (Hs[0], int(inl[0])) if H.ndim == 2 else (Hs, inl.astype(np.int64))
 
 
 def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighbors=10, viewpoint_fixed=None, viewpoint_movable=None,
@@ -256,11 +363,16 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     point's nearest fixed descriptor (``match_features``, ``mutual``), poses from triples of those matches (``ransac_pose``:
     ``max_distance`` and its other keywords).  Both clouds (n, 3) numpy arrays or both CUDA torch tensors.
 
+    ``refine=r`` (0 .. 64, default 0: nothing) refits the ``top`` candidates on their own inliers in r rounds (``refine_pose``
+    with the same ``max_distance``) and ranks them again by ``(-inliers, index)``; ``index`` stays the row of the triple, ``stats``
+    the record of the hypotheses, ``refined`` the refit's.
+
     Returns ``ransac_pose``'s GlobalResult with ``n_matches`` set; fewer than three matches give a result without a pose.
-    Refinement stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
-    unknown = set(ransac_kwargs) - {"hypotheses", "edge_ratio", "seed", "triples", "top"}
+    ICP stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
+    unknown = set(ransac_kwargs) - {"hypotheses", "edge_ratio", "seed", "triples", "top", "refine"}
     if unknown:
         raise TypeError(f"register_global() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    refine = _int_in("refine", ransac_kwargs.pop("refine", 0), 0, _lib.POSEFIT_MAX_ROUNDS)
     ransac_arguments(max_distance, **ransac_kwargs)
     if not isinstance(mutual, (bool, np.bool_)):
         raise TypeError(f"mutual must be True or False, not {mutual!r}")
@@ -276,6 +388,6 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
         return GlobalResult([], dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1), n_matches)
     if not _is_torch(movable):
         fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
-    res = ransac_pose(movable[keep], fixed[idx[keep]], max_distance=max_distance, **ransac_kwargs)
+    res = _ransac_pose(movable[keep], fixed[idx[keep]], max_distance, refine=refine, **ransac_kwargs)
     res.n_matches = n_matches
     return res
