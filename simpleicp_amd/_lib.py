@@ -87,6 +87,11 @@ POSEFIT_VERSION = 1
 POSEFIT_MAX_ROUNDS = 64
 POSEFIT_SWEEPS = 6
 
+# include/simpleicp_hip_robust.h: robust poses of matched rows (graduated Geman-McClure weights), the same kind of companion
+ROBUST_EXPORTS = ["sicp_robust_version", "sicp_pose_robust"]
+ROBUST_VERSION = 1
+ROBUST_MAX_ROUNDS = 256
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -147,6 +152,14 @@ class PosefitStats(C.Structure):
     def as_dict(self):
         return dict(n_poses=int(self.n_poses), n_void=int(self.n_void), n_improved=int(self.n_improved), best=int(self.best),
                     best_inliers=int(self.best_inliers))
+
+
+class RobustStats(C.Structure):
+    """struct sicp_robust_stats (contract (G)): 32 bytes."""
+    _fields_ = [("n_poses", C.c_int64), ("n_void", C.c_int64), ("best", C.c_int64), ("best_inliers", C.c_int64)]
+
+    def as_dict(self):
+        return dict(n_poses=int(self.n_poses), n_void=int(self.n_void), best=int(self.best), best_inliers=int(self.best_inliers))
 
 
 class IterParams(C.Structure):
@@ -211,6 +224,8 @@ FEATURES = {
         "sicp_ransac_triplets": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _dbl, _vp, _vp, C.POINTER(RansacStats)]}),
     "posefit": _Feature(POSEFIT_EXPORTS, "simpleicp_hip_posefit.h", "pose-refit", POSEFIT_VERSION, {
         "sicp_pose_refit": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _cint, _vp, _vp, C.POINTER(PosefitStats)]}),
+    "robust": _Feature(ROBUST_EXPORTS, "simpleicp_hip_robust.h", "robust-pose", ROBUST_VERSION, {
+        "sicp_pose_robust": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _cint, _dbl, _dbl, _vp, _vp, _vp, C.POINTER(RobustStats)]}),
 }
 
 _lib = None
@@ -355,6 +370,7 @@ outlier_version = partial(_feature_version, "outlier")
 fpfh_version = partial(_feature_version, "fpfh")
 global_version = partial(_feature_version, "global")
 posefit_version = partial(_feature_version, "posefit")
+robust_version = partial(_feature_version, "robust")
 
 
 def select_positions(m, Q):
@@ -824,6 +840,35 @@ class Context:
         self._chk(self._L.sicp_pose_refit(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds), _ptr(out),
                                           _ptr(inl), C.byref(st)))
         return out, inl, st
+
+    # -- robust poses of matched rows (contract (G)) --
+    def pose_robust(self, src, dst, poses, max_distance, rounds, divisor, start_scale=0.0, m=None, b=None, poses_ptr=None,
+                    inliers_ptr=None, scales_ptr=None):
+        """sicp_pose_robust: every pose refitted over all matched rows src[c] <-> dst[c] under Geman-McClure weights whose scale
+        starts at start_scale (0: twice the largest squared residual under the start) and is divided by `divisor` after each of
+        the `rounds` rounds, never below max_distance^2 (contract (G)); what leaves is the latest pose.  poses None: the start is
+        the identity (b = 1).  Host form: (m, 3) float64 arrays and (b, 12) float64 poses -- R row-major, then t --; returns
+        ((b, 12) float64 poses, (b,) int32 inliers: -1 void, (b,) float64 final scales, RobustStats).  Pointer form: src, dst and
+        poses (or None) are addresses (ints) of host or device memory, m and b given; the poses are left at poses_ptr (b * 12
+        doubles), the inliers at inliers_ptr (b int32), the scales at scales_ptr (b doubles), and the RobustStats alone is
+        returned."""
+        robust_version()
+        st = RobustStats()
+        if inliers_ptr is not None:
+            self._chk(self._L.sicp_pose_robust(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m),
+                                               None if poses is None else C.c_void_p(int(poses)), int(b), float(max_distance), int(rounds),
+                                               float(divisor), float(start_scale), C.c_void_p(int(poses_ptr)), C.c_void_p(int(inliers_ptr)),
+                                               C.c_void_p(int(scales_ptr)), C.byref(st)))
+            return st
+        s, d = _f64(src), _f64(dst)
+        p = None if poses is None else _f64(poses)
+        if s.ndim != 2 or s.shape[1] != 3 or d.shape != s.shape or (p is not None and (p.ndim != 2 or p.shape[1] != 12)):
+            raise ValueError("src and dst must be (m, 3), poses (b, 12) or None")
+        n = 1 if p is None else p.shape[0]
+        out, inl, scales = np.empty((n, 12), np.float64), np.empty(n, np.int32), np.empty(n, np.float64)
+        self._chk(self._L.sicp_pose_robust(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds),
+                                           float(divisor), float(start_scale), _ptr(out), _ptr(inl), _ptr(scales), C.byref(st)))
+        return out, inl, scales, st
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):

@@ -337,6 +337,10 @@ struct sicp_ctx {
     // sums and the level above them, the spans' inlier counts (src, dst and the outputs are staged in the gl_ buffers)
     DevBuf<double> pf_in, pf_state, pf_part, pf_part2;
     DevBuf<uint32_t> pf_cnt;
+    // robust poses (sicp_robust.hip): the poses' states between the launches of the sweeps path, the staged scales (the partial
+    // sums lie in pf_part / pf_part2, the other arrays are staged where sicp_posefit.hip stages them)
+    DevBuf<double> rb_state, rb_scale;
+    int robust_path = 0;           // SICP_ROBUST: 1 "sweeps", 2 "one" -- the path of sicp_pose_robust where both apply (0: chosen per call)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

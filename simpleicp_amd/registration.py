@@ -9,6 +9,10 @@ the three in a row.  What comes back is a coarse pose and its runners-up: ``run_
 Contract (L), DESIGN.md section 19 (include/simpleicp_hip_posefit.h): ``fit_pose`` is the least-squares rigid fit of matched
 rows, ``refine_pose`` refits poses on their own inliers, and ``register_global(..., refine=r)`` sends its ``top`` candidates
 through that refit before it ranks them.
+
+Contract (G), DESIGN.md section 20 (include/simpleicp_hip_robust.h): ``robust_pose`` fits a pose to all matches at once under
+Geman-McClure weights whose scale is tightened round by round, and ``register_global(..., method="robust")`` ends the chain with
+it instead of the random triples.
 """
 from __future__ import annotations
 
@@ -356,6 +360,76 @@ def refine_pose(src, dst, H, *, max_distance, rounds=3):
     return (Hs[0], int(inl[0])) if H.ndim == 2 else (Hs, inl.astype(np.int64))
 
 
+# ---- robust poses (contract (G)) ----
+def robust_arguments(max_distance, rounds=64, divisor=1.4, start_scale=None):
+    """(max_distance, rounds, divisor, start_scale: 0.0 for None), checked: TypeError / ValueError."""
+    d = _number("max_distance", max_distance)
+    if not math.isfinite(d) or not d > 0.0:
+        raise ValueError(f"max_distance must be finite and > 0, not {max_distance!r}")
+    r = _int_in("rounds", rounds, 1, _lib.ROBUST_MAX_ROUNDS)
+    q = _number("divisor", divisor)
+    if not math.isfinite(q) or not q > 1.0:
+        raise ValueError(f"divisor must be finite and > 1, not {divisor!r}")
+    s = 0.0
+    if start_scale is not None:
+        s = _number("start_scale", start_scale)
+        if not math.isfinite(s) or not s > 0.0:
+            raise ValueError(f"start_scale must be finite and > 0 (None: chosen from the residuals), not {start_scale!r}")
+    return d, r, q, s
+
+
+def _robust_context():
+    ctx = backend.get_context()
+    if not hasattr(ctx, "pose_robust"):
+        raise _lib.BackendError("this backend has no robust pose fit")
+    dist.detach(ctx)
+    return ctx
+
+
+def _robust(ctx, on_device, S, D, m, poses, d, r, q, s):
+    """sicp_pose_robust on rows that are where they are: (poses (b, 12), inliers (b,) int32, scales (b,), the record as a dict)."""
+    if not on_device:
+        out, inl, scales, st = ctx.pose_robust(S, D, poses, d, r, q, s)
+    else:
+        b = 1 if poses is None else len(poses)
+        out, inl, scales = np.empty((b, 12), np.float64), np.empty(b, np.int32), np.empty(b, np.float64)
+        st = ctx.pose_robust(S.data_ptr(), D.data_ptr(), None if poses is None else poses.ctypes.data, d, r, q, s, m=m, b=b,
+                             poses_ptr=out.ctypes.data, inliers_ptr=inl.ctypes.data, scales_ptr=scales.ctypes.data)
+    return out, inl, scales, st.as_dict() if hasattr(st, "as_dict") else dict(st)
+
+
+def robust_pose(src, dst, *, max_distance, H=None, rounds=64, divisor=1.4, start_scale=None):
+    """The rigid pose that brings ``src[c]`` onto ``dst[c]`` for the matches that agree with each other, wrong matches among them
+    (contract (G)): every round weights every row by the Geman-McClure weight ``(s / (s + d2))**2`` of its
+    squared residual under the current pose and refits the weighted least-squares pose (Horn, ``fit_pose``'s arithmetic); ``s``
+    starts at ``start_scale`` (None: twice the largest squared residual under the start) and is divided by ``divisor`` after
+    every round, never below ``max_distance**2`` -- graduated non-convexity, as Fast Global Registration runs it.  No seed, no
+    hypotheses: the same bits on every run.  The answer is the pose of the last round.
+
+    ``src``, ``dst`` as for ``fit_pose``; ``H``: the start -- None (the identity), one 4x4 pose or a stack (b, 4, 4).  Returns
+    ``(H, inliers)``: float64 poses in H's shape ((4, 4) for None) and the rows within ``max_distance`` (strict) of their partner
+    under them (an int, or a (b,) int64 array); a start with a non-finite entry, or without a single row at a finite distance,
+    comes back as zeros with -1."""
+    d, r, q, s = robust_arguments(max_distance, rounds, divisor, start_scale)
+    poses, single = None, True
+    if H is not None:
+        if _is_torch(H):
+            H = H.detach().cpu().numpy()
+        H = np.asarray(H, dtype=np.float64)
+        if H.shape[-2:] != (4, 4) or H.ndim not in (2, 3) or H.shape[0] < 1:
+            raise ValueError(f"H must have shape (4, 4) or (b, 4, 4), b >= 1, not {H.shape}")
+        single = H.ndim == 2
+        stack = H.reshape(-1, 4, 4)
+        poses = np.ascontiguousarray(np.concatenate([stack[:, :3, :3].reshape(-1, 9), stack[:, :3, 3]], axis=1))
+    on_device, src, dst, m = _matched_rows(src, dst)
+    _refuse_distributed("robust_pose")
+    ctx = _robust_context()
+    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+    out, inl, _, _ = _robust(ctx, on_device, S, D, m, poses, d, r, q, s)
+    Hs = np.stack([_as_H(p) if n >= 0 else np.zeros((4, 4)) for p, n in zip(out, inl)])
+    return (Hs[0], int(inl[0])) if single else (Hs, inl.astype(np.int64))
+
+
 def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighbors=10, viewpoint_fixed=None, viewpoint_movable=None,
                     mutual=True, **ransac_kwargs):
     """A coarse pose of ``movable`` onto ``fixed`` without an initial guess -- in the direction of ``run()``'s H --: the FPFH
@@ -367,13 +441,29 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     with the same ``max_distance``) and ranks them again by ``(-inliers, index)``; ``index`` stays the row of the triple, ``stats``
     the record of the hypotheses, ``refined`` the refit's.
 
+    ``method="robust"`` (default ``"ransac"``) ends the chain with ``robust_pose`` from the identity over all matches instead of
+    the triples; its keywords are then ``rounds``, ``divisor`` and ``start_scale``, and ``ransac_pose``'s are refused.  The
+    result has one candidate ``(H, inliers, -1)`` -- none when the fit is void -- and the robust fit's record (n_poses, n_void,
+    best, best_inliers) as ``stats``.
+
     Returns ``ransac_pose``'s GlobalResult with ``n_matches`` set; fewer than three matches give a result without a pose.
     ICP stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
-    unknown = set(ransac_kwargs) - {"hypotheses", "edge_ratio", "seed", "triples", "top", "refine"}
+    method = ransac_kwargs.pop("method", "ransac")
+    if not isinstance(method, str):
+        raise TypeError(f"method must be 'ransac' or 'robust', not {method!r}")
+    if method not in ("ransac", "robust"):
+        raise ValueError(f"method must be 'ransac' or 'robust', not {method!r}")
+    robust = method == "robust"
+    unknown = set(ransac_kwargs) - ({"rounds", "divisor", "start_scale"} if robust else
+                                    {"hypotheses", "edge_ratio", "seed", "triples", "top", "refine"})
     if unknown:
-        raise TypeError(f"register_global() got an unexpected keyword argument {sorted(unknown)[0]!r}")
-    refine = _int_in("refine", ransac_kwargs.pop("refine", 0), 0, _lib.POSEFIT_MAX_ROUNDS)
-    ransac_arguments(max_distance, **ransac_kwargs)
+        raise TypeError(f"register_global() got an unexpected keyword argument {sorted(unknown)[0]!r}" +
+                        (" (method='robust')" if robust else ""))
+    if robust:
+        fit = robust_arguments(max_distance, **ransac_kwargs)
+    else:
+        refine = _int_in("refine", ransac_kwargs.pop("refine", 0), 0, _lib.POSEFIT_MAX_ROUNDS)
+        ransac_arguments(max_distance, **ransac_kwargs)
     if not isinstance(mutual, (bool, np.bool_)):
         raise TypeError(f"mutual must be True or False, not {mutual!r}")
     if _is_torch(fixed) != _is_torch(movable):
@@ -385,9 +475,18 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     keep = idx >= 0
     n_matches = int(keep.sum())
     if n_matches < 3:
-        return GlobalResult([], dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1), n_matches)
+        none = dict(n_poses=0, n_void=0, best=-1, best_inliers=-1) if robust else \
+            dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1)
+        return GlobalResult([], none, n_matches)
     if not _is_torch(movable):
         fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
+    if robust:
+        # the matched rows through sicp_pose_robust from the identity while they are where they are
+        on_device, src, dst, m = _matched_rows(movable[keep], fixed[idx[keep]])
+        ctx = _robust_context()
+        S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+        poses, inl, _, stats = _robust(ctx, on_device, S, D, m, None, *fit)
+        return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches)
     res = _ransac_pose(movable[keep], fixed[idx[keep]], max_distance, refine=refine, **ransac_kwargs)
     res.n_matches = n_matches
     return res
