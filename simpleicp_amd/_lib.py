@@ -334,6 +334,23 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _matched_rows(src, dst):
+    """The matched rows of a host-form call as float64 arrays, and whether both are (m, 3)."""
+    s, d = _f64(src), _f64(dst)
+    return s, d, s.ndim == 2 and s.shape[1] == 3 and d.shape == s.shape
+
+
+def _pose_call_arrays(src, dst, poses):
+    """Host form of pose_refit / pose_robust: the checked arrays (poses None: one pose), the number of poses, and the (n, 12)
+    poses and (n,) inliers that leave."""
+    s, d, ok = _matched_rows(src, dst)
+    p = None if poses is None else _f64(poses)
+    if not ok or (p is not None and (p.ndim != 2 or p.shape[1] != 12)):
+        raise ValueError("src and dst must be (m, 3), poses (b, 12) or None")
+    n = 1 if p is None else p.shape[0]
+    return s, d, p, n, np.empty((n, 12), np.float64), np.empty(n, np.int32)
+
+
 def device_count():
     n = C.c_int(0)
     load().sicp_device_count(C.byref(n))
@@ -806,9 +823,9 @@ class Context:
                                                    None if poses_ptr is None else C.c_void_p(int(poses_ptr)),
                                                    C.c_void_p(int(inliers_ptr)), C.byref(st)))
             return st
-        s, d = _f64(src), _f64(dst)
+        s, d, ok = _matched_rows(src, dst)
         tri = np.ascontiguousarray(triples, dtype=np.int32)
-        if s.ndim != 2 or s.shape[1] != 3 or d.shape != s.shape or tri.ndim != 2 or tri.shape[1] != 3:
+        if not ok or tri.ndim != 2 or tri.shape[1] != 3:
             raise ValueError("src and dst must be (m, 3), triples (h, 3)")
         poses = np.empty((tri.shape[0], 12), np.float64) if want_poses else None
         inl = np.empty(tri.shape[0], np.int32)
@@ -831,12 +848,7 @@ class Context:
                                               None if poses is None else C.c_void_p(int(poses)), int(b), float(max_distance), int(rounds),
                                               C.c_void_p(int(poses_ptr)), C.c_void_p(int(inliers_ptr)), C.byref(st)))
             return st
-        s, d = _f64(src), _f64(dst)
-        p = None if poses is None else _f64(poses)
-        if s.ndim != 2 or s.shape[1] != 3 or d.shape != s.shape or (p is not None and (p.ndim != 2 or p.shape[1] != 12)):
-            raise ValueError("src and dst must be (m, 3), poses (b, 12) or None")
-        n = 1 if p is None else p.shape[0]
-        out, inl = np.empty((n, 12), np.float64), np.empty(n, np.int32)
+        s, d, p, n, out, inl = _pose_call_arrays(src, dst, poses)
         self._chk(self._L.sicp_pose_refit(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds), _ptr(out),
                                           _ptr(inl), C.byref(st)))
         return out, inl, st
@@ -860,12 +872,8 @@ class Context:
                                                float(divisor), float(start_scale), C.c_void_p(int(poses_ptr)), C.c_void_p(int(inliers_ptr)),
                                                C.c_void_p(int(scales_ptr)), C.byref(st)))
             return st
-        s, d = _f64(src), _f64(dst)
-        p = None if poses is None else _f64(poses)
-        if s.ndim != 2 or s.shape[1] != 3 or d.shape != s.shape or (p is not None and (p.ndim != 2 or p.shape[1] != 12)):
-            raise ValueError("src and dst must be (m, 3), poses (b, 12) or None")
-        n = 1 if p is None else p.shape[0]
-        out, inl, scales = np.empty((n, 12), np.float64), np.empty(n, np.int32), np.empty(n, np.float64)
+        s, d, p, n, out, inl = _pose_call_arrays(src, dst, poses)
+        scales = np.empty(n, np.float64)
         self._chk(self._L.sicp_pose_robust(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds),
                                            float(divisor), float(start_scale), _ptr(out), _ptr(inl), _ptr(scales), C.byref(st)))
         return out, inl, scales, st

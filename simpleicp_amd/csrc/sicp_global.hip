@@ -6,9 +6,9 @@
 // pattern orders like the value, so the key's order IS the contract's (d2, j).  The row width is a template parameter (4, 16, 36,
 // 64): the columns past dim hold 0 on both sides and add +0.0 to a sum that is >= +0, which changes no bit.
 // RANSAC (k_ransac): one wave per hypothesis, every lane forming the same pose, then the lanes striding over the m rows; counts by
-// ballot and popcount; k_ransac_best picks the lowest index among the best.  Integer atomics only.
-#include "sicp_host.h"
-#include "sicp_grid_dev.h"
+// ballot and popcount; the row's residual, the pose's store and the kernel that picks the lowest index among the best
+// (k_pose_best) are sicp_pose_dev.h's.  Integer atomics only.
+#include "sicp_pose_dev.h"
 #include "../../include/simpleicp_hip_global.h"
 
 namespace sicp {
@@ -107,8 +107,8 @@ __device__ __forceinline__ void rs_frame(const V3 &a0, const V3 &a1, const V3 &a
 }
 
 // One wave per hypothesis.  poses (nullable): (h, 12); inl: (h).
-// st: [RS_VOID] += void, [RS_PRUNED] += pruned, [RS_BEST1] = max over the hypotheses of inliers + 1.
-enum { RS_VOID = 0, RS_PRUNED = 1, RS_BEST1 = 2, RS_BEST = 3 };
+// st: [POSE_VOID] += void, [RS_PRUNED] += pruned, [POSE_BEST1] = max over the hypotheses of inliers + 1.
+constexpr int RS_PRUNED = 1;
 __global__ __launch_bounds__(RS_BLOCK) void k_ransac(const double *__restrict__ src, const double *__restrict__ dst,
                                                      const int32_t *__restrict__ tri, double *__restrict__ poses,
                                                      int32_t *__restrict__ inl, unsigned long long *__restrict__ st, long m, long h,
@@ -158,10 +158,8 @@ __global__ __launch_bounds__(RS_BLOCK) void k_ransac(const double *__restrict__ 
                 const long c = c0 + lane;
                 bool in = false;
                 if (c < m) {
-                    double X, Y, Z;
-                    xf(H, src[3 * c], src[3 * c + 1], src[3 * c + 2], X, Y, Z);
-                    const double dx = X - dst[3 * c], dy = Y - dst[3 * c + 1], dz = Z - dst[3 * c + 2];
-                    in = fma(dz, dz, fma(dy, dy, dx * dx)) < md2;
+                    double p[3], q[3];
+                    in = pose_row(src, dst, c, H, p, q) < md2;
                 }
                 cnt += __popcll((long long)__ballot(in));
             }
@@ -171,35 +169,13 @@ __global__ __launch_bounds__(RS_BLOCK) void k_ransac(const double *__restrict__ 
         n_pruned += verdict == -2 ? 1 : 0;
         if (lane == 0) {
             inl[k] = verdict == 0 ? cnt : verdict;
-            if (poses) {
-                double *o = poses + 12 * k;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    o[3 * r] = H.m[4 * r]; o[3 * r + 1] = H.m[4 * r + 1]; o[3 * r + 2] = H.m[4 * r + 2];
-                    o[9 + r] = H.m[4 * r + 3];
-                }
-            }
+            if (poses) pose_store(H, poses + 12 * k);
         }
     }
     if (lane == 0) {
-        if (n_void) atomicAdd(st + RS_VOID, n_void);
+        if (n_void) atomicAdd(st + POSE_VOID, n_void);
         if (n_pruned) atomicAdd(st + RS_PRUNED, n_pruned);
-        if (best1) atomicMax(st + RS_BEST1, best1);
-    }
-}
-
-// st[RS_BEST] (all ones before) = the lowest index whose inliers + 1 == st[RS_BEST1]
-__global__ __launch_bounds__(RS_BLOCK) void k_ransac_best(const int32_t *__restrict__ inl, long h, unsigned long long *__restrict__ st)
-{
-    const unsigned long long best1 = st[RS_BEST1];
-    if (best1 == 0) return;
-    const int lane = threadIdx.x & 63;
-    const long stride = (long)gridDim.x * RS_BLOCK;
-    for (long base = (long)blockIdx.x * RS_BLOCK; base < h; base += stride) {
-        const long k = base + threadIdx.x;
-        const bool is = k < h && inl[k] >= 0 && (unsigned long long)inl[k] + 1 == best1;
-        const unsigned long long who = (unsigned long long)__ballot(is);
-        if (who && lane == __ffsll((long long)who) - 1) atomicMin(st + RS_BEST, (unsigned long long)k);      // (the wave's lowest)
+        if (best1) atomicMax(st + POSE_BEST1, best1);
     }
 }
 
@@ -207,14 +183,6 @@ __global__ __launch_bounds__(RS_BLOCK) void k_ransac_best(const int32_t *__restr
 }  // namespace sicp
 
 namespace {
-
-static_assert(RS_BEST < CAND_WORDS, "the record's counters fit the ctx's counter words");
-
-int gl_check_ctx(sicp_ctx *c, const char *who)
-{
-    if (!c) return fail(SICP_ERR_INVALID, "null ctx");
-    return check_no_exchange(c, who, "the rows of one rank are not the job's");
-}
 
 template <int DP>
 void launch_match(sicp_ctx *c, dim3 grid, const float *q, const float *t, long nq, long nt, int dim, long chunk, long nchunks)
@@ -229,7 +197,7 @@ SICP_EXPORT int sicp_global_version(void) { return SICP_GLOBAL_VERSION; }
 SICP_EXPORT int sicp_feature_match(sicp_ctx *c, const float *query, int64_t nq, const float *target, int64_t nt, int dim,
                                    int32_t *idx_out, float *d2_out, sicp_match_stats *out)
 {
-    CHK(gl_check_ctx(c, "sicp_feature_match"));
+    CHK(check_rows_ctx(c, "sicp_feature_match"));
     if (!query) return fail(SICP_ERR_INVALID, "query is null");
     if (!target) return fail(SICP_ERR_INVALID, "target is null");
     if (!idx_out) return fail(SICP_ERR_INVALID, "idx_out is null");
@@ -279,46 +247,29 @@ SICP_EXPORT int sicp_ransac_triplets(sicp_ctx *c, const double *src, const doubl
                                      double max_distance, double edge_ratio, double *poses_out, int32_t *inliers_out,
                                      sicp_ransac_stats *out)
 {
-    CHK(gl_check_ctx(c, "sicp_ransac_triplets"));
-    if (!src) return fail(SICP_ERR_INVALID, "src is null");
-    if (!dst) return fail(SICP_ERR_INVALID, "dst is null");
+    CHK(check_rows_ctx(c, "sicp_ransac_triplets"));
+    CHK(check_matched(src, dst));
     if (!triples) return fail(SICP_ERR_INVALID, "triples is null");
     if (!inliers_out) return fail(SICP_ERR_INVALID, "inliers_out is null");
     if (!out) return fail(SICP_ERR_INVALID, "out is null");
-    if (m < 3) return fail(SICP_ERR_INVALID, "m must be >= 3 (%lld given)", (long long)m);
-    if (m >= (1LL << 31)) return fail(SICP_ERR_INVALID, "m must be < 2^31 (%lld given)", (long long)m);
+    CHK(check_matched_count(m));
     if (h < 1) return fail(SICP_ERR_INVALID, "h must be >= 1 (%lld given)", (long long)h);
-    if (!std::isfinite(max_distance) || !(max_distance > 0.0)) return fail(SICP_ERR_INVALID, "max_distance must be finite and > 0");
+    CHK(check_max_distance(max_distance, false));
     if (!(edge_ratio >= 0.0 && edge_ratio <= 1.0)) return fail(SICP_ERR_INVALID, "edge_ratio must be >= 0 and <= 1");
     HIPCHK(hipSetDevice(c->device));
     return op_run(c, [&]() -> int {
-        const double *s, *d;
+        PoseRows R;
         const int32_t *tri;
-        double *poses;
-        int32_t *inl;
-        CHK(stage_in(c, src, (size_t)3 * m, c->gl_src, &s));
-        CHK(stage_in(c, dst, (size_t)3 * m, c->gl_dst, &d));
+        CHK(pose_rows_enter(c, src, dst, m, nullptr, h, poses_out, inliers_out, &R));
         CHK(stage_in(c, triples, (size_t)3 * h, c->gl_tri, &tri));
-        CHK(stage_out(c, poses_out, (size_t)12 * h, c->gl_pose, &poses));
-        CHK(stage_out(c, inliers_out, (size_t)h, c->gl_idx, &inl));
-        CHK(counters_clear(c));
-        HIPCHK(hipMemsetAsync(c->cand_small.p + RS_BEST, 0xff, sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(k_ransac, dim3((unsigned)std::min<long>((h + RS_WAVES - 1) / RS_WAVES, RS_MAX_BLOCKS)), dim3(RS_BLOCK), 0, c->stream,
-                           s, d, tri, poses, inl, c->cand_small.p, (long)m, (long)h, max_distance * max_distance, edge_ratio * edge_ratio);
+                           R.src, R.dst, tri, R.poses, R.inl, c->cand_small.p, (long)m, (long)h, max_distance * max_distance,
+                           edge_ratio * edge_ratio);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_ransac_best, dim3((unsigned)std::min<long>((h + RS_BLOCK - 1) / RS_BLOCK, RS_MAX_BLOCKS)), dim3(RS_BLOCK), 0,
-                           c->stream, inl, (long)h, c->cand_small.p);
-        HIPCHK(hipGetLastError());
-        CHK(counters_fetch(c));
-        CHK(stage_leave(c, poses_out, (size_t)12 * h, poses));
-        CHK(stage_leave(c, inliers_out, (size_t)h, inl));
-        CHK(sync(c));
-        const unsigned long long *hs = counters_host(c);
+        CHK(pose_best_enqueue(c, k_pose_best, R.inl, (long)h));
+        CHK(pose_rows_leave(c, poses_out, inliers_out, h, R, out));
         out->n_hypotheses = h;
-        out->n_void = (int64_t)hs[RS_VOID];
-        out->n_pruned = (int64_t)hs[RS_PRUNED];
-        out->best = hs[RS_BEST1] ? (int64_t)hs[RS_BEST] : -1;
-        out->best_inliers = (int64_t)hs[RS_BEST1] - 1;
+        out->n_pruned = (int64_t)counters_host(c)[RS_PRUNED];
         return SICP_OK;
     });
 }

@@ -1,6 +1,7 @@
 // sicp_horn.h -- Horn's closed-form rotation (device code only): the 4 x 4 matrix of the centred cross sums, the fixed cyclic
 // Jacobi sweeps, the quaternion, R and t -- contract (L) step 1 (include/simpleicp_hip_posefit.h).
 // sicp_posefit.hip fits with it under a mask, sicp_robust.hip under weights: one text, the same bits.
+// The sweeps and folds around it are sicp_pose_dev.h's.
 #ifndef SICP_HORN_H
 #define SICP_HORN_H
 

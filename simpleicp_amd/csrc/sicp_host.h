@@ -543,6 +543,111 @@ int stage_leave(sicp_ctx *c, T *p, size_t count, const T *dev)
     if (p && dev != p) HIPCHK(hipMemcpyAsync(p, dev, count * sizeof(T), hipMemcpyDefault, c->stream));
     return SICP_OK;
 }
+
+// ---- a pose operator's frame ("A pose operator's frame"): what the entries over matched rows src[c] <-> dst[c] share ----
+constexpr int POSE_BLOCK = 256;                    // threads of the kernels with one thread per pose
+constexpr int POSE_BEST_BLOCKS = 1024;             // grid limit of the best kernel: its workgroups stride from there on
+constexpr int POSE_MAX_POSES_Y = 32768;            // grid limit of the poses' dimension: the workgroups stride from there on
+enum { POSE_VOID = 0, POSE_BEST1 = 2, POSE_BEST = 3 };   // the shared counter words (BEST1 = max of inliers + 1); word 1 is the operator's
+static_assert(POSE_BEST < CAND_WORDS && POSE_BEST != CAND_COUNT && POSE_BEST1 != CAND_COUNT, "the record's counters fit the ctx's counter words");
+// the checks, in the order the entries make them
+inline int check_rows_ctx(sicp_ctx *c, const char *who)
+{
+    if (!c) return fail(SICP_ERR_INVALID, "null ctx");
+    return check_no_exchange(c, who, "the rows of one rank are not the job's");
+}
+inline int check_matched(const double *src, const double *dst)
+{
+    if (!src) return fail(SICP_ERR_INVALID, "src is null");
+    if (!dst) return fail(SICP_ERR_INVALID, "dst is null");
+    return SICP_OK;
+}
+inline int check_matched_count(int64_t m)
+{
+    if (m < 3) return fail(SICP_ERR_INVALID, "m must be >= 3 (%lld given)", (long long)m);
+    if (m >= (1LL << 31)) return fail(SICP_ERR_INVALID, "m must be < 2^31 (%lld given)", (long long)m);
+    return SICP_OK;
+}
+inline int check_poses_rounds(const double *poses_in, int64_t b, int rounds, int max_rounds)
+{
+    if (b < 1) return fail(SICP_ERR_INVALID, "b must be >= 1 (%lld given)", (long long)b);
+    if (b >= (1LL << 31)) return fail(SICP_ERR_INVALID, "b must be < 2^31 (%lld given)", (long long)b);
+    if (!poses_in && b != 1) return fail(SICP_ERR_INVALID, "poses_in is null: b must be 1 then (%lld given)", (long long)b);
+    if (rounds < 1 || rounds > max_rounds) return fail(SICP_ERR_INVALID, "rounds must be >= 1 and <= %d (%d given)", max_rounds, rounds);
+    return SICP_OK;
+}
+inline int check_max_distance(double max_distance, bool or_inf)
+{
+    if (or_inf) {
+        if (std::isnan(max_distance) || !(max_distance > 0.0)) return fail(SICP_ERR_INVALID, "max_distance must be > 0 (finite or +inf)");
+    } else if (!std::isfinite(max_distance) || !(max_distance > 0.0)) {
+        return fail(SICP_ERR_INVALID, "max_distance must be finite and > 0");
+    }
+    return SICP_OK;
+}
+// the call's arrays as the kernels take them, and the counter words cleared: src and dst (m rows), poses_in (null, or n poses), the
+// n poses (nullable) and n counts that leave
+struct PoseRows {
+    const double *src, *dst, *poses_in = nullptr;
+    double *poses;
+    int32_t *inl;
+};
+inline int pose_rows_enter(sicp_ctx *c, const double *src, const double *dst, int64_t m, const double *poses_in, int64_t n, double *poses_out,
+                           int32_t *inliers_out, PoseRows *R)
+{
+    CHK(stage_in(c, src, (size_t)3 * m, c->gl_src, &R->src));
+    CHK(stage_in(c, dst, (size_t)3 * m, c->gl_dst, &R->dst));
+    if (poses_in) CHK(stage_in(c, poses_in, (size_t)12 * n, c->pf_in, &R->poses_in));
+    CHK(stage_out(c, poses_out, (size_t)12 * n, c->gl_pose, &R->poses));
+    CHK(stage_out(c, inliers_out, (size_t)n, c->gl_idx, &R->inl));
+    CHK(counters_clear(c));
+    HIPCHK(hipMemsetAsync(c->cand_small.p + POSE_BEST, 0xff, sizeof(unsigned long long), c->stream));
+    return SICP_OK;
+}
+// ... behind the best kernel: the counters fetched, the staged outputs copied out, the stream drained; the record's shared fields
+// (the operator's own word is counters_host(c)[1])
+template <class Stats>
+int pose_rows_leave(sicp_ctx *c, double *poses_out, int32_t *inliers_out, int64_t n, const PoseRows &R, Stats *out)
+{
+    CHK(counters_fetch(c));
+    CHK(stage_leave(c, poses_out, (size_t)12 * n, R.poses));
+    CHK(stage_leave(c, inliers_out, (size_t)n, R.inl));
+    CHK(sync(c));
+    const unsigned long long *hs = counters_host(c);
+    out->n_void = (int64_t)hs[POSE_VOID];
+    out->best = hs[POSE_BEST1] ? (int64_t)hs[POSE_BEST] : -1;
+    out->best_inliers = (int64_t)hs[POSE_BEST1] - 1;
+    return SICP_OK;
+}
+// the record's best index among the n counts at inl, by the unit's k_pose_best (sicp_pose_dev.h), enqueued behind the kernels that
+// wrote them and the counter words: one grid rule for every operator
+typedef void (*PoseBestKernel)(const int32_t *, long, unsigned long long *);
+inline int pose_best_enqueue(sicp_ctx *c, PoseBestKernel best, const int32_t *inl, long n)
+{
+    void *args[] = {&inl, &n, &c->cand_small.p};
+    HIPCHK(hipLaunchKernel((const void *)best, dim3(std::min(cdiv(n, (long)POSE_BLOCK), (unsigned)POSE_BEST_BLOCKS)), dim3(POSE_BLOCK), args, 0,
+                           c->stream));
+    return SICP_OK;
+}
+// the geometry of the sweeps over m rows and b poses: the tree's P, the spans of `span` rows and the level of `fold` above them, the
+// grids of a first stage, of a second stage and of the kernels with one thread per pose
+struct PoseGrids {
+    long P, nb, nb2;
+    dim3 sweep, fold, poses;
+};
+inline PoseGrids pose_grids(long m, long b, long span, long fold)
+{
+    PoseGrids G;
+    G.P = 1;
+    while (G.P < m) G.P *= 2;
+    G.nb = cdiv(m, span);
+    G.nb2 = cdiv(G.nb, fold);
+    G.sweep = dim3((unsigned)G.nb, (unsigned)std::min<long>(b, POSE_MAX_POSES_Y));
+    G.fold = dim3((unsigned)std::min<long>(b, POSE_MAX_POSES_Y));
+    G.poses = dim3(cdiv(b, (long)POSE_BLOCK));
+    return G;
+}
+
 // a chunked k-NN over rows of a slot (sicp_search.cpp): rows per search -- the ctx's switch, else as many as keep a chunk's
 // (chunk, k) distances and indices at 256 MiB; c->kq / k_d2 / k_idx for chunks of up to `most` rows; rows d_rows[lo, lo + cnt)
 // (null: rows lo, lo + 1, ...) as query columns in c->kq (stride round_up(cnt, QPAD)); ... searched: (cnt, k) in c->k_d2 / c->k_idx

@@ -1,15 +1,13 @@
 // sicp_posefit.hip -- least-squares poses of matched rows (include/simpleicp_hip_posefit.h; contract (L)).
 //
-// The shape is sicp_eval.hip's, once per sweep of the contract.  First stage (k_pf_sweep): the grid is (spans of PT_SPAN rows) x
-// (poses); every thread rebuilds the mask of its row from the pose (contracts (T) and (D): nine fused multiply-adds), forms its
-// terms -- sweep A: the six coordinates and the count, sweep B: the nine centred products -- and the pair tree (sicp_pairtree.h)
-// leaves one partial per term, span and pose.  Second stage (k_pf_fold): one workgroup per pose folds the partials; after sweep A
-// one lane settles "keep the best" with the count the sweep carried and forms the centroids, after sweep B it runs the 4 x 4
-// Jacobi and writes the next pose into the pose's state.  The rounds are enqueued back to back; a pose whose rounds are over
-// (PfState::done) costs its workgroups one load.  Counts by ballot and popcount; the record's counters are integer atomics.
-#include "sicp_host.h"
-#include "sicp_grid_dev.h"
-#include "sicp_pairtree.h"
+// The frame is sicp_pose_dev.h's, once per sweep of the contract: this file holds what is the refit's own.  First stage
+// (k_pose_sweep<PfTerms>): every thread rebuilds the mask of its row from the pose and forms its terms -- sweep A: the six
+// coordinates and the count, sweep B: the nine centred products.  Second stage: after sweep A (k_pf_fold_a, which also folds the
+// counts and, behind the last round, writes the outputs: more than the frame's one settle step, so it keeps its own loop) one
+// lane settles "keep the best" with the count the sweep carried and forms the centroids, after sweep B (k_pose_fold<PfSettleB>)
+// it runs the 4 x 4 Jacobi (sicp_horn.h) and writes the next pose into the pose's state.  The rounds are enqueued back to back; a
+// pose whose rounds are over (PfState::done) costs its workgroups one load.  The record's counters are integer atomics.
+#include "sicp_pose_dev.h"
 #include "sicp_horn.h"
 #include "../../include/simpleicp_hip_posefit.h"
 
@@ -17,8 +15,6 @@ namespace sicp {
 namespace {
 
 constexpr int PF_A = 6, PF_B = 9;                  // terms of sweep A (p | q) and of sweep B (K row-major)
-constexpr int PF_MAX_POSES_Y = 32768;              // grid limit of the poses' dimension: the workgroups stride from there on
-constexpr int PF_BLOCK = 256;
 
 // a pose's state between the launches.  Poses are R row-major, then t.
 struct PfState {
@@ -30,11 +26,11 @@ struct PfState {
 constexpr int PF_WORDS = sizeof(PfState) / sizeof(double);
 static_assert(sizeof(PfState) % sizeof(double) == 0, "the states lie in a buffer of doubles");
 
-enum { PF_VOID = 0, PF_IMPROVED = 1, PF_BEST1 = 2, PF_BEST = 3 };   // the counter words (st[PF_BEST1] = max of inliers + 1)
+constexpr int PF_IMPROVED = 1;                     // the refit's own counter word, beside POSE_VOID, POSE_BEST1, POSE_BEST
 
-__global__ __launch_bounds__(PF_BLOCK) void k_pf_init(const double *__restrict__ poses_in, long b, PfState *__restrict__ st)
+__global__ __launch_bounds__(POSE_BLOCK) void k_pf_init(const double *__restrict__ poses_in, long b, PfState *__restrict__ st)
 {
-    const long k = (long)blockIdx.x * PF_BLOCK + threadIdx.x;
+    const long k = (long)blockIdx.x * POSE_BLOCK + threadIdx.x;
     if (k >= b) return;
     PfState S;
     bool ok = true;
@@ -55,79 +51,33 @@ __global__ __launch_bounds__(PF_BLOCK) void k_pf_init(const double *__restrict__
     st[k] = S;
 }
 
-// First stage.  part: per pose T rows of nb doubles, span s's sums in column s; cnt (sweep A): per pose nb counts.
-template <int T>
-__global__ __launch_bounds__(PT_BLOCK) void k_pf_sweep(const double *__restrict__ src, const double *__restrict__ dst,
-                                                       const PfState *__restrict__ st, long m, long b, long P, double md2,
-                                                       double *__restrict__ part, long nb, unsigned *__restrict__ cnt)
-{
-    __shared__ double node[PT_TILES * PT_WAVES][T];
-    __shared__ unsigned found[PT_TILES * PT_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long base = (long)blockIdx.x * PT_SPAN;
-    for (long k = blockIdx.y; k < b; k += gridDim.y) {
-        const PfState *S = st + k;
-        if (S->done) continue;                                         // (the same for the whole workgroup)
-        const bool plain = S->plain != 0;
-        Xf H;
+// a row's terms in a sweep (T = PF_A: the six coordinates, the spans' counts leave too; PF_B: the nine centred products)
+template <int N>
+struct PfTerms {
+    static constexpr int T = N;
+    static constexpr bool COUNTS = N == PF_A;
+    using State = PfState;
+    double md2, cp[3], cq[3];
+    bool plain;
+    __device__ __forceinline__ PfTerms(const PfState &S, double md2_) : md2(md2_), plain(S.plain != 0)
+    {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            H.m[4 * r] = S->cur[3 * r]; H.m[4 * r + 1] = S->cur[3 * r + 1]; H.m[4 * r + 2] = S->cur[3 * r + 2];
-            H.m[4 * r + 3] = S->cur[9 + r];
-        }
-        double cp[3] = {0.0, 0.0, 0.0}, cq[3] = {0.0, 0.0, 0.0};
-        if constexpr (T == PF_B) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { cp[j] = S->cp[j]; cq[j] = S->cq[j]; }
-        }
-#pragma unroll
-        for (int t = 0; t < PT_TILES; ++t) {
-            const long e = base + (long)t * PT_BLOCK + threadIdx.x;
-            double v[T];
-            bool in = false;
-            if (e < m) {
-                const double px = src[3 * e], py = src[3 * e + 1], pz = src[3 * e + 2];
-                const double qx = dst[3 * e], qy = dst[3 * e + 1], qz = dst[3 * e + 2];
-                if (plain) {
-                    in = finite_f64(px) && finite_f64(py) && finite_f64(pz) && finite_f64(qx) && finite_f64(qy) && finite_f64(qz);
-                } else {
-                    double X, Y, Z;
-                    xf(H, px, py, pz, X, Y, Z);
-                    const double dx = X - qx, dy = Y - qy, dz = Z - qz;
-                    in = fma(dz, dz, fma(dy, dy, dx * dx)) < md2;
-                }
-                if constexpr (T == PF_A) {
-                    v[0] = px; v[1] = py; v[2] = pz; v[3] = qx; v[4] = qy; v[5] = qz;
-                } else {
-                    const double a[3] = {px - cp[0], py - cp[1], pz - cp[2]}, g[3] = {qx - cq[0], qy - cq[1], qz - cq[2]};
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) v[3 * i + j] = a[i] * g[j];
-                }
-            }
-            if (!in) {
-#pragma unroll
-                for (int j = 0; j < T; ++j) v[j] = 0.0;
-            }
-            const unsigned long long hits = __ballot(in);
-            pt_wave(v, e, P);
-            if (lane == 0) {
-#pragma unroll
-                for (int j = 0; j < T; ++j) node[t * PT_WAVES + wave][j] = v[j];
-                found[t * PT_WAVES + wave] = (unsigned)__popcll(hits);
-            }
-        }
-        const double s = pt_nodes<PT_TILES * PT_WAVES>(node, base, P);   // (its barriers also fence `found`)
-        if (threadIdx.x < T) part[((long)k * T + threadIdx.x) * nb + blockIdx.x] = s;
-        if (T == PF_A && threadIdx.x == T) {
-            unsigned n = 0;
-            for (int i = 0; i < PT_TILES * PT_WAVES; ++i) n += found[i];
-            cnt[k * nb + blockIdx.x] = n;
-        }
-        __syncthreads();                                               // (`found` may be written again)
+        for (int j = 0; j < 3; ++j) { cp[j] = N == PF_B ? S.cp[j] : 0.0; cq[j] = N == PF_B ? S.cq[j] : 0.0; }
     }
-}
+    __device__ __forceinline__ bool operator()(const double (&p)[3], const double (&q)[3], double d2, double (&v)[N]) const
+    {
+        if constexpr (N == PF_A) {
+            v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = q[0]; v[4] = q[1]; v[5] = q[2];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) v[3 * i + j] = (p[i] - cp[i]) * (q[j] - cq[j]);
+        }
+        if (plain) return finite_f64(p[0]) && finite_f64(p[1]) && finite_f64(p[2]) && finite_f64(q[0]) && finite_f64(q[1]) && finite_f64(q[2]);
+        return d2 < md2;
+    }
+};
 
 // Second stage of sweep A, one workgroup per pose: the tree over the nb partials (between part and part2), the counts as integers;
 // then cur's count settles "keep the best", and the centroids are formed.  last: the scoring sweep behind the last round --
@@ -182,142 +132,85 @@ __global__ __launch_bounds__(PT_FOLD) void k_pf_fold_a(PfState *__restrict__ st,
 #pragma unroll
                 for (int j = 0; j < 12; ++j) poses_out[12 * k + j] = bc >= 0 ? S->best[j] : 0.0;
                 inl_out[k] = (int32_t)bc;
-                if (S->done == 2) atomicAdd(counters + PF_VOID, 1ull);
+                if (S->done == 2) atomicAdd(counters + POSE_VOID, 1ull);
                 if (bc > S->in_cnt) atomicAdd(counters + PF_IMPROVED, 1ull);
-                if (bc >= 0) atomicMax(counters + PF_BEST1, (unsigned long long)bc + 1);
+                if (bc >= 0) atomicMax(counters + POSE_BEST1, (unsigned long long)bc + 1);
             }
         }
         __syncthreads();
     }
 }
 
-// Second stage of sweep B: the nine sums, then one lane runs the Jacobi and the pose.  A pose that is not finite, or that
-// repeats cur bit for bit, ends the rounds; any other becomes cur.
-__global__ __launch_bounds__(PT_FOLD) void k_pf_fold_b(PfState *__restrict__ st, double *part, double *part2, long nb, long nb2, long b)
-{
-    __shared__ double node[PT_FOLD_WAVES][PF_B];
-    for (long k = blockIdx.x; k < b; k += gridDim.x) {
-        PfState *S = st + k;
-        const bool over = S->done != 0;
-        __syncthreads();
-        if (over) continue;
-        double *a = part + k * PF_B * nb;
-        long sa = nb;
-        pt_fold(a, sa, part2 + k * PF_B * nb2, nb2, nb, node);
-        if (threadIdx.x == 0) {
-            double K[9], o[12];
+// Sweep B's sums: one lane runs the Jacobi and the pose.  A pose that is not finite, or that repeats cur bit for bit, ends the
+// rounds; any other becomes cur.
+struct PfSettleB {
+    static constexpr int T = PF_B;
+    using State = PfState;
+    __device__ __forceinline__ void operator()(PfState &S, const double (&K)[PF_B]) const
+    {
+        double o[12];
+        const double cp[3] = {S.cp[0], S.cp[1], S.cp[2]}, cq[3] = {S.cq[0], S.cq[1], S.cq[2]};
+        const bool ok = pf_pose(K, cp, cq, o);
+        bool same = S.plain == 0;
 #pragma unroll
-            for (int j = 0; j < 9; ++j) K[j] = a[(long)j * sa];
-            const double cp[3] = {S->cp[0], S->cp[1], S->cp[2]}, cq[3] = {S->cq[0], S->cq[1], S->cq[2]};
-            const bool ok = pf_pose(K, cp, cq, o);
-            bool same = S->plain == 0;
+        for (int j = 0; j < 12; ++j) same = same && __double_as_longlong(o[j]) == __double_as_longlong(S.cur[j]);
+        if (!ok || same) {
+            S.done = 1;
+        } else {
 #pragma unroll
-            for (int j = 0; j < 12; ++j) same = same && __double_as_longlong(o[j]) == __double_as_longlong(S->cur[j]);
-            if (!ok || same) {
-                S->done = 1;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 12; ++j) S->cur[j] = o[j];
-                S->plain = 0;
-            }
+            for (int j = 0; j < 12; ++j) S.cur[j] = o[j];
+            S.plain = 0;
         }
-        __syncthreads();
     }
-}
-
-// st[PF_BEST] (all ones before) = the lowest k whose inliers + 1 == st[PF_BEST1]
-__global__ __launch_bounds__(PF_BLOCK) void k_pf_best(const int32_t *__restrict__ inl, long b, unsigned long long *__restrict__ st)
-{
-    const unsigned long long best1 = st[PF_BEST1];
-    if (best1 == 0) return;
-    const int lane = threadIdx.x & 63;
-    const long stride = (long)gridDim.x * PF_BLOCK;
-    for (long base = (long)blockIdx.x * PF_BLOCK; base < b; base += stride) {
-        const long k = base + threadIdx.x;
-        const bool is = k < b && inl[k] >= 0 && (unsigned long long)inl[k] + 1 == best1;
-        const unsigned long long who = (unsigned long long)__ballot(is);
-        if (who && lane == __ffsll((long long)who) - 1) atomicMin(st + PF_BEST, (unsigned long long)k);
-    }
-}
+};
 
 }  // namespace
 }  // namespace sicp
-
-namespace {
-static_assert(PF_BEST < CAND_WORDS && PF_BEST != CAND_COUNT, "the record's counters fit the ctx's counter words");
-}
 
 SICP_EXPORT int sicp_posefit_version(void) { return SICP_POSEFIT_VERSION; }
 
 SICP_EXPORT int sicp_pose_refit(sicp_ctx *c, const double *src, const double *dst, int64_t m, const double *poses_in, int64_t b,
                                 double max_distance, int rounds, double *poses_out, int32_t *inliers_out, sicp_posefit_stats *out)
 {
-    if (!c) return fail(SICP_ERR_INVALID, "null ctx");
-    CHK(check_no_exchange(c, "sicp_pose_refit", "the rows of one rank are not the job's"));
-    if (!src) return fail(SICP_ERR_INVALID, "src is null");
-    if (!dst) return fail(SICP_ERR_INVALID, "dst is null");
+    CHK(check_rows_ctx(c, "sicp_pose_refit"));
+    CHK(check_matched(src, dst));
     if (!poses_out) return fail(SICP_ERR_INVALID, "poses_out is null");
     if (!inliers_out) return fail(SICP_ERR_INVALID, "inliers_out is null");
     if (!out) return fail(SICP_ERR_INVALID, "out is null");
-    if (m < 3) return fail(SICP_ERR_INVALID, "m must be >= 3 (%lld given)", (long long)m);
-    if (m >= (1LL << 31)) return fail(SICP_ERR_INVALID, "m must be < 2^31 (%lld given)", (long long)m);
-    if (b < 1) return fail(SICP_ERR_INVALID, "b must be >= 1 (%lld given)", (long long)b);
-    if (b >= (1LL << 31)) return fail(SICP_ERR_INVALID, "b must be < 2^31 (%lld given)", (long long)b);
-    if (!poses_in && b != 1) return fail(SICP_ERR_INVALID, "poses_in is null: b must be 1 then (%lld given)", (long long)b);
-    if (rounds < 1 || rounds > SICP_POSEFIT_MAX_ROUNDS)
-        return fail(SICP_ERR_INVALID, "rounds must be >= 1 and <= %d (%d given)", SICP_POSEFIT_MAX_ROUNDS, rounds);
-    if (std::isnan(max_distance) || !(max_distance > 0.0)) return fail(SICP_ERR_INVALID, "max_distance must be > 0 (finite or +inf)");
+    CHK(check_matched_count(m));
+    CHK(check_poses_rounds(poses_in, b, rounds, SICP_POSEFIT_MAX_ROUNDS));
+    CHK(check_max_distance(max_distance, true));
     HIPCHK(hipSetDevice(c->device));
     return op_run(c, [&]() -> int {
-        const double *s, *d, *pin = nullptr;
-        double *poses;
-        int32_t *inl;
-        CHK(stage_in(c, src, (size_t)3 * m, c->gl_src, &s));
-        CHK(stage_in(c, dst, (size_t)3 * m, c->gl_dst, &d));
-        if (poses_in) CHK(stage_in(c, poses_in, (size_t)12 * b, c->pf_in, &pin));
-        CHK(stage_out(c, poses_out, (size_t)12 * b, c->gl_pose, &poses));
-        CHK(stage_out(c, inliers_out, (size_t)b, c->gl_idx, &inl));
-        const long nb = cdiv((long)m, PT_SPAN), nb2 = cdiv(nb, (long)PT_FOLD);
+        PoseRows R;
+        CHK(pose_rows_enter(c, src, dst, m, poses_in, b, poses_out, inliers_out, &R));
+        const PoseGrids G = pose_grids((long)m, (long)b, PT_SPAN, PT_FOLD);
         CHK(c->pf_state.reserve((size_t)b * PF_WORDS));
-        CHK(c->pf_part.reserve((size_t)b * PF_B * nb));
-        CHK(c->pf_part2.reserve((size_t)b * PF_B * nb2));
-        CHK(c->pf_cnt.reserve((size_t)b * nb));
-        CHK(counters_clear(c));
-        HIPCHK(hipMemsetAsync(c->cand_small.p + PF_BEST, 0xff, sizeof(unsigned long long), c->stream));
+        CHK(c->pf_part.reserve((size_t)b * PF_B * G.nb));
+        CHK(c->pf_part2.reserve((size_t)b * PF_B * G.nb2));
+        CHK(c->pf_cnt.reserve((size_t)b * G.nb));
         PfState *st = (PfState *)c->pf_state.p;
-        long P = 1;
-        while (P < m) P *= 2;
         const double md2 = max_distance * max_distance;
-        const dim3 sweep_grid((unsigned)nb, (unsigned)std::min<long>(b, PF_MAX_POSES_Y));
-        const dim3 fold_grid((unsigned)std::min<long>(b, PF_MAX_POSES_Y));
-        hipLaunchKernelGGL(k_pf_init, dim3((unsigned)cdiv((long)b, (long)PF_BLOCK)), dim3(PF_BLOCK), 0, c->stream, pin, (long)b, st);
+        hipLaunchKernelGGL(k_pf_init, G.poses, dim3(POSE_BLOCK), 0, c->stream, R.poses_in, (long)b, st);
         HIPCHK(hipGetLastError());
         for (int r = 0; r <= rounds; ++r) {                           // (the pass behind the last round only scores its pose)
             const int last = r == rounds;
-            hipLaunchKernelGGL(k_pf_sweep<PF_A>, sweep_grid, dim3(PT_BLOCK), 0, c->stream, s, d, st, (long)m, (long)b, P, md2, c->pf_part.p,
-                               nb, c->pf_cnt.p);
-            hipLaunchKernelGGL(k_pf_fold_a, fold_grid, dim3(PT_FOLD), 0, c->stream, st, c->pf_part.p, c->pf_part2.p, c->pf_cnt.p, nb, nb2,
-                               (long)b, last, poses, inl, c->cand_small.p);
+            hipLaunchKernelGGL(k_pose_sweep<PfTerms<PF_A>>, G.sweep, dim3(PT_BLOCK), 0, c->stream, R.src, R.dst, st, (long)m, (long)b, G.P, md2,
+                               c->pf_part.p, G.nb, c->pf_cnt.p);
+            hipLaunchKernelGGL(k_pf_fold_a, G.fold, dim3(PT_FOLD), 0, c->stream, st, c->pf_part.p, c->pf_part2.p, c->pf_cnt.p, G.nb, G.nb2,
+                               (long)b, last, R.poses, R.inl, c->cand_small.p);
             if (!last) {
-                hipLaunchKernelGGL(k_pf_sweep<PF_B>, sweep_grid, dim3(PT_BLOCK), 0, c->stream, s, d, st, (long)m, (long)b, P, md2,
-                                   c->pf_part.p, nb, c->pf_cnt.p);
-                hipLaunchKernelGGL(k_pf_fold_b, fold_grid, dim3(PT_FOLD), 0, c->stream, st, c->pf_part.p, c->pf_part2.p, nb, nb2, (long)b);
+                hipLaunchKernelGGL(k_pose_sweep<PfTerms<PF_B>>, G.sweep, dim3(PT_BLOCK), 0, c->stream, R.src, R.dst, st, (long)m, (long)b, G.P,
+                                   md2, c->pf_part.p, G.nb, c->pf_cnt.p);
+                hipLaunchKernelGGL(k_pose_fold<PfSettleB>, G.fold, dim3(PT_FOLD), 0, c->stream, st, c->pf_part.p, c->pf_part2.p, G.nb, G.nb2,
+                                   (long)b, PfSettleB{});
             }
             HIPCHK(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_pf_best, dim3((unsigned)std::min<long>(cdiv((long)b, (long)PF_BLOCK), 1024)), dim3(PF_BLOCK), 0, c->stream, inl,
-                           (long)b, c->cand_small.p);
-        HIPCHK(hipGetLastError());
-        CHK(counters_fetch(c));
-        CHK(stage_leave(c, poses_out, (size_t)12 * b, poses));
-        CHK(stage_leave(c, inliers_out, (size_t)b, inl));
-        CHK(sync(c));
-        const unsigned long long *hs = counters_host(c);
+        CHK(pose_best_enqueue(c, k_pose_best, R.inl, (long)b));
+        CHK(pose_rows_leave(c, poses_out, inliers_out, b, R, out));
         out->n_poses = b;
-        out->n_void = (int64_t)hs[PF_VOID];
-        out->n_improved = (int64_t)hs[PF_IMPROVED];
-        out->best = hs[PF_BEST1] ? (int64_t)hs[PF_BEST] : -1;
-        out->best_inliers = (int64_t)hs[PF_BEST1] - 1;
+        out->n_improved = (int64_t)counters_host(c)[PF_IMPROVED];
         return SICP_OK;
     });
 }

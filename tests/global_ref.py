@@ -169,3 +169,24 @@ def ransac(src, dst, triples, max_distance, edge_ratio):
     rec = dict(n_hypotheses=len(inliers), n_void=int((verdict == -1).sum()), n_pruned=int((verdict == -2).sum()), best=best,
                best_inliers=best_inliers)
     return np.concatenate([R.reshape(-1, 9), t], axis=1), inliers, rec
+
+
+# ---- a threshold that tells the fused sum of contract (D) from the unfused one ----
+def d2_fused_and_plain(R, t, src, dst):
+    """d2 of every row under one pose (R (3, 3), t (3,)) as contract (D) forms it, and the same three squares with every product and
+    every sum rounded on its own (contract (T) fused in both): what a scoring without fused multiply-adds would compare."""
+    src, dst = np.ascontiguousarray(src, dtype=np.float64), np.ascontiguousarray(dst, dtype=np.float64)
+    x, y, z = src[:, 0], src[:, 1], src[:, 2]
+    d = [(fma(R[r, 2], z, fma(R[r, 1], y, R[r, 0] * x)) + t[r]) - dst[:, r] for r in range(3)]
+    return fma(d[2], d[2], fma(d[1], d[1], d[0] * d[0])), (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+
+
+def threshold_between(fused, plain):
+    """A max_distance whose square is the larger of the two sums of some row, so that the row counts under the smaller sum only,
+    and under which the two counts differ; the first row that has one.  None: no row has."""
+    for c in np.flatnonzero(fused != plain):
+        hi = max(fused[c], plain[c])
+        for md in (np.sqrt(hi), np.nextafter(np.sqrt(hi), 0.0), np.nextafter(np.sqrt(hi), np.inf)):
+            if md * md == hi and int((fused < hi).sum()) != int((plain < hi).sum()):
+                return float(md)
+    return None

@@ -269,6 +269,21 @@ def test_ransac_ties_and_nothing_valid(ctx):
     assert rec["best_inliers"] >= 0 and rec["best"] == int(np.flatnonzero(inl == inl.max())[0])
 
 
+def test_ransac_counts_by_the_fused_sum(ctx):
+    """A max_distance whose square lies between the fused d2 of contract (D) and the same sum rounded product by product, for a
+    row under hypothesis 0: the count of that hypothesis is the fused sum's, one apart from the other."""
+    rng = np.random.default_rng(77)
+    src, dst = noisy_copy(rng, 2048, wrong=0.3)
+    tri = np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8], [9, 10, 11], [12, 13, 14], [15, 16, 17], [18, 19, 20], [21, 22, 23]], np.int32)
+    verdict, R, t = global_ref.poses(src, dst, tri, 0.0)
+    assert verdict[0] == 0
+    fused, plain = global_ref.d2_fused_and_plain(R[0], t[0], src, dst)
+    md = global_ref.threshold_between(fused, plain)
+    assert md is not None and (fused < md * md).sum() != (plain < md * md).sum()
+    _, inl, _ = check_ransac(ctx, src, dst, tri, md, 0.0)
+    assert inl[0] == (fused < md * md).sum()
+
+
 def test_ransac_host_and_device_memory_give_the_same_bits(ctx):
     from simpleicp_amd import _lib
     rng = np.random.default_rng(31)

@@ -1,5 +1,5 @@
 """The stride and tile seams of sicp_feature_match, sicp_ransac_triplets and sicp_pose_refit (contracts (M), (R) and (L), DESIGN.md
-sections 18 and 19): every loop of k_match, k_match_finish, k_ransac, k_pf_sweep, the folds and k_pf_best runs a second pass, every
+sections 18 and 19): every loop of k_match, k_match_finish, k_ransac, k_pose_sweep, the folds and k_pose_best runs a second pass, every
 row width of k_match is instantiated at, below and past its edge, a chunk holds several LDS tiles, and pt_fold runs two levels
 with 6 and 9 terms and more than one pose.  Everything is compared bit for bit with the numpy references of tests/global_ref.py and
 tests/posefit_ref.py; what the inputs must be like for a seam to matter (where the best record lies, that counts differ, that the
@@ -280,7 +280,7 @@ STRIDES = {
 
 @pytest.mark.parametrize("b", sorted(STRIDES))
 def test_refit_more_poses_than_the_grids(ctx, b):
-    """32768 + 5 poses: k_pf_sweep (over blockIdx.y) and both folds take a second pose.  1024 * 256 + 300: so does k_pf_best, where
+    """32768 + 5 poses: k_pose_sweep (over blockIdx.y) and both folds take a second pose.  1024 * 256 + 300: so does k_pose_best, where
     the best and its copy 190 rows further on both lie in the strided pass.  All poses are void but a few, each of which ends with a
     count of its own."""
     rows, best_at, twin_at, seed = STRIDES[b]
@@ -296,7 +296,7 @@ def test_refit_more_poses_than_the_grids(ctx, b):
     poses[others] = live[order[1:]]
     n_live = len(rows)
     if twin_at is not None:
-        poses[twin_at] = poses[best_at]                               # a tie inside the strided pass of k_pf_best: the lower row
+        poses[twin_at] = poses[best_at]                               # a tie inside the strided pass of k_pose_best: the lower row
         n_live += 1
     reference = posefit_ref.refit(src, dst, poses, 0.03, 2)
     rinl, rec = reference[1], reference[2]

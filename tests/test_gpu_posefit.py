@@ -86,6 +86,19 @@ def test_refit_equals_the_reference(ctx, m, b, rounds):
         assert rec["n_improved"] > 0
 
 
+def test_refit_masks_by_the_fused_sum(ctx):
+    """A max_distance whose square lies between the fused d2 of contract (D) and the same sum rounded product by product, for a
+    row under the first input pose: that row is in the mask of exactly one of the two, so the round's fit tells them apart."""
+    rng = np.random.default_rng(78)
+    src, dst = noisy_copy(rng, 2048, wrong=0.3)
+    poses = perturbed(rng, 4, degrees=0.5, shift=0.002)
+    fused, plain = global_ref.d2_fused_and_plain(poses[0, :9].reshape(3, 3), poses[0, 9:], src, dst)
+    md = global_ref.threshold_between(fused, plain)
+    assert md is not None and (fused < md * md).sum() != (plain < md * md).sum()
+    for rounds in (1, 2):
+        check(ctx, src, dst, poses, md, rounds)
+
+
 def test_unbounded_distance_and_the_plain_fit(ctx):
     import simpleicp_amd
     rng = np.random.default_rng(1025)
