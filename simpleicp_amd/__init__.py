@@ -22,10 +22,11 @@ from .tensors import outlier_keep, run_tensors, voxel_keep                     #
 
 from .evaluation import Evaluation, evaluate_registration        # noqa: E402
 from .features import fpfh_features                              # noqa: E402
-from .registration import fit_pose, match_features, ransac_pose, refine_pose, register_global, robust_pose, GlobalResult   # noqa: E402
+from .registration import (consistent_matches, fit_pose, match_features, ransac_pose, refine_pose, register_global,   # noqa: E402
+                           robust_pose, ConsistencyResult, GlobalResult)
 from . import io                                                 # noqa: E402,F401
 
 __all__ = ["SimpleICP", "SimpleICPException", "PointCloud", "PointCloudException",
            "RigidBodyParameters", "Parameter", "run_batch", "BatchResult", "run_tensors", "voxel_keep", "outlier_keep", "Evaluation",
            "evaluate_registration", "fpfh_features", "match_features", "ransac_pose", "register_global", "GlobalResult", "fit_pose",
-           "refine_pose", "robust_pose"]
+           "refine_pose", "robust_pose", "consistent_matches", "ConsistencyResult"]

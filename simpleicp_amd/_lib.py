@@ -92,6 +92,12 @@ ROBUST_EXPORTS = ["sicp_robust_version", "sicp_pose_robust"]
 ROBUST_VERSION = 1
 ROBUST_MAX_ROUNDS = 256
 
+# include/simpleicp_hip_consistency.h: matches pruned by pairwise length consistency (compatibility graph, core numbers), the same
+# kind of companion
+CONSISTENCY_EXPORTS = ["sicp_consistency_version", "sicp_match_consistency"]
+CONSISTENCY_VERSION = 1
+CONSISTENCY_MAX_ROWS = 32768
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -162,6 +168,14 @@ class RobustStats(C.Structure):
         return dict(n_poses=int(self.n_poses), n_void=int(self.n_void), best=int(self.best), best_inliers=int(self.best_inliers))
 
 
+class ConsistencyStats(C.Structure):
+    """struct sicp_consistency_stats (contract (C)): 56 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_rows", "n_valid", "n_edges", "max_degree", "max_core", "n_max_core", "n_subrounds")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -226,6 +240,8 @@ FEATURES = {
         "sicp_pose_refit": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _cint, _vp, _vp, C.POINTER(PosefitStats)]}),
     "robust": _Feature(ROBUST_EXPORTS, "simpleicp_hip_robust.h", "robust-pose", ROBUST_VERSION, {
         "sicp_pose_robust": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _cint, _dbl, _dbl, _vp, _vp, _vp, C.POINTER(RobustStats)]}),
+    "consistency": _Feature(CONSISTENCY_EXPORTS, "simpleicp_hip_consistency.h", "match-consistency", CONSISTENCY_VERSION, {
+        "sicp_match_consistency": [_vp, _vp, _vp, _i64, _dbl, _dbl, _vp, _vp, C.POINTER(ConsistencyStats)]}),
 }
 
 _lib = None
@@ -388,6 +404,7 @@ fpfh_version = partial(_feature_version, "fpfh")
 global_version = partial(_feature_version, "global")
 posefit_version = partial(_feature_version, "posefit")
 robust_version = partial(_feature_version, "robust")
+consistency_version = partial(_feature_version, "consistency")
 
 
 def select_positions(m, Q):
@@ -877,6 +894,28 @@ class Context:
         self._chk(self._L.sicp_pose_robust(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds),
                                            float(divisor), float(start_scale), _ptr(out), _ptr(inl), _ptr(scales), C.byref(st)))
         return out, inl, scales, st
+
+    # -- matches pruned by pairwise length consistency (contract (C)) --
+    def match_consistency(self, src, dst, tolerance, min_length, m=None, degree_ptr=None, core_ptr=None):
+        """sicp_match_consistency: rows i and j of the matched rows src[c] <-> dst[c] are compatible when their distance in src and
+        their distance in dst differ by at most `tolerance` and neither is below `min_length` (contract (C)); every row's degree
+        and core number in that graph.  Host form: (m, 3) float64 arrays; returns ((m,) int32 degrees, (m,) int32 core numbers,
+        ConsistencyStats).  Pointer form: src and dst are addresses (ints) of host or device memory, m given; the degrees are left
+        at degree_ptr and the core numbers at core_ptr (m int32 each), and the ConsistencyStats alone is returned."""
+        consistency_version()
+        st = ConsistencyStats()
+        if degree_ptr is not None:
+            self._chk(self._L.sicp_match_consistency(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m), float(tolerance),
+                                                     float(min_length), C.c_void_p(int(degree_ptr)), C.c_void_p(int(core_ptr)),
+                                                     C.byref(st)))
+            return st
+        s, d, ok = _matched_rows(src, dst)
+        if not ok:
+            raise ValueError("src and dst must be (m, 3)")
+        degree, core = np.empty(s.shape[0], np.int32), np.empty(s.shape[0], np.int32)
+        self._chk(self._L.sicp_match_consistency(self._h, _ptr(s), _ptr(d), s.shape[0], float(tolerance), float(min_length), _ptr(degree),
+                                                 _ptr(core), C.byref(st)))
+        return degree, core, st
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):

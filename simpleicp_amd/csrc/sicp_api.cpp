@@ -258,6 +258,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_ROBUST")) c->robust_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
+    if (const char *e = std::getenv("SICP_CONSISTENCY")) c->consistency_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
     // SICP_SOLVE_TRACE: per-iteration traces on stderr -- any value: the tail's cycle counters; "host": the host's enqueue timings too;
     // "sel" / "eval": the fine splits of a -DSICP_SEL_FINE_TRACE / -DSICP_EVAL_FINE_TRACE build (build.build_variant)
     if (const char *e = std::getenv("SICP_SOLVE_TRACE")) {
@@ -311,6 +312,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->gl_src.release(); c->gl_dst.release(); c->gl_pose.release();
     c->pf_in.release(); c->pf_state.release(); c->pf_part.release(); c->pf_part2.release(); c->pf_cnt.release();
     c->rb_state.release(); c->rb_scale.release();
+    c->cs_bits.release(); c->cs_front.release(); c->cs_work.release(); c->cs_core.release(); c->cs_state.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
     if (c->h_lm) (void)hipHostFree(c->h_lm);

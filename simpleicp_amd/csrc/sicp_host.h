@@ -341,6 +341,13 @@ struct sicp_ctx {
     // sums lie in pf_part / pf_part2, the other arrays are staged where sicp_posefit.hip stages them)
     DevBuf<double> rb_state, rb_scale;
     int robust_path = 0;           // SICP_ROBUST: 1 "sweeps", 2 "one" -- the path of sicp_pose_robust where both apply (0: chosen per call)
+    // length consistency of matches (sicp_consistency.hip): the compatibility matrix as bits (m rows of ceil(m / 64) words), the
+    // peeling's remaining degrees, frontier bits and level words, the staged core numbers (src and dst are staged in gl_src / gl_dst,
+    // the degrees in gl_idx)
+    DevBuf<unsigned long long> cs_bits, cs_front;
+    DevBuf<int32_t> cs_work, cs_core;
+    DevBuf<unsigned> cs_state;
+    int consistency_path = 0;      // SICP_CONSISTENCY: 1 "sweeps", 2 "one" -- the peeling of sicp_match_consistency where both apply (0: chosen per call)
     // exchange: an RCCL communicator of the library's own (sicp_comm_init) or a host callback (sicp_set_exchange)
     sicp_exchange_fn xfn = nullptr;
     void *xuser = nullptr;

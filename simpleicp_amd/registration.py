@@ -13,6 +13,10 @@ through that refit before it ranks them.
 Contract (G), DESIGN.md section 20 (include/simpleicp_hip_robust.h): ``robust_pose`` fits a pose to all matches at once under
 Geman-McClure weights whose scale is tightened round by round, and ``register_global(..., method="robust")`` ends the chain with
 it instead of the random triples.
+
+Contract (C), DESIGN.md section 21 (include/simpleicp_hip_consistency.h): ``consistent_matches`` tests every pair of matches for
+equal lengths in both clouds and keeps the maximal core of that graph, and ``register_global(..., prune=tolerance)`` sends the
+matches through it before either estimator sees them.
 """
 from __future__ import annotations
 
@@ -31,12 +35,14 @@ class GlobalResult:
     (n_hypotheses, n_void, n_pruned, best, best_inliers); ``candidates``: the ``top`` best as ``(H, inliers, index)``, ordered by
     ``(-inliers, index)``; ``n_matches``: the matches the poses were drawn from (``register_global`` only); ``refined``: the
     record of the refit the candidates went through (n_poses, n_void, n_improved, best, best_inliers -- ``best`` a position among
-    the unrefined candidates), None without one."""
+    the unrefined candidates), None without one; ``n_consistent``: the matches the pruning left for the estimator
+    (``register_global(..., prune=...)`` only, None without it; ``n_matches`` stays the count before it)."""
 
-    def __init__(self, candidates, stats, n_matches=None, refined=None):
+    def __init__(self, candidates, stats, n_matches=None, refined=None, n_consistent=None):
         self.candidates = list(candidates)
         self.stats = dict(stats)
         self.n_matches = n_matches
+        self.n_consistent = n_consistent
         self.refined = None if refined is None else dict(refined)
         self.H, self.inliers, self.index = self.candidates[0] if self.candidates else (None, -1, -1)
 
@@ -430,6 +436,80 @@ def robust_pose(src, dst, *, max_distance, H=None, rounds=64, divisor=1.4, start
     return (Hs[0], int(inl[0])) if single else (Hs, inl.astype(np.int64))
 
 
+# ---- matches pruned by pairwise length consistency (contract (C)) ----
+class ConsistencyResult:
+    """What ``consistent_matches`` returns.  ``keep``: (m,) bool, the rows of the maximal core -- ``core == max_core`` where
+    ``max_core >= 1``, else all False; ``core``, ``degree``: (m,) int32, every row's core number and its number of compatible
+    rows; ``stats``: the call's record (n_rows, n_valid, n_edges, max_degree, max_core, n_max_core, n_subrounds).  Tensors for
+    tensors, arrays for arrays."""
+
+    def __init__(self, keep, core, degree, stats):
+        self.keep, self.core, self.degree, self.stats = keep, core, degree, dict(stats)
+
+    def __repr__(self):
+        return f"ConsistencyResult(kept={int(self.keep.sum())}, stats={self.stats})"
+
+
+def consistency_arguments(tolerance, min_length=0.0):
+    """(tolerance, min_length), checked: TypeError / ValueError."""
+    t = _number("tolerance", tolerance)
+    if not math.isfinite(t) or not t > 0.0:
+        raise ValueError(f"tolerance must be finite and > 0, not {tolerance!r}")
+    l = _number("min_length", min_length)
+    if not math.isfinite(l) or l < 0.0:
+        raise ValueError(f"min_length must be finite and >= 0, not {min_length!r}")
+    return t, l
+
+
+def _consistency_rows(src, dst):
+    """_matched_rows, and the operator's cap."""
+    on_device, src, dst, m = _matched_rows(src, dst)
+    if m > _lib.CONSISTENCY_MAX_ROWS:
+        raise ValueError(f"consistent_matches takes at most {_lib.CONSISTENCY_MAX_ROWS} matches, not {m}: thin the matches first "
+                         "(nothing is subsampled silently)")
+    return on_device, src, dst, m
+
+
+def _consistency_context():
+    ctx = backend.get_context()
+    if not hasattr(ctx, "match_consistency"):
+        raise _lib.BackendError("this backend has no match consistency")
+    dist.detach(ctx)
+    return ctx
+
+
+def _consistency(ctx, on_device, S, D, m, t, l):
+    """sicp_match_consistency on rows that are where they are: the ConsistencyResult (tensors on the tensor road)."""
+    if not on_device:
+        degree, core, st = ctx.match_consistency(S, D, t, l)
+    else:
+        import torch
+        degree = torch.empty(m, dtype=torch.int32, device=S.device)
+        core = torch.empty(m, dtype=torch.int32, device=S.device)
+        st = ctx.match_consistency(S.data_ptr(), D.data_ptr(), t, l, m=m, degree_ptr=degree.data_ptr(), core_ptr=core.data_ptr())
+    stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
+    keep = core == stats["max_core"] if stats["max_core"] >= 1 else core < 0       # (no core number is negative: all False)
+    return ConsistencyResult(keep, core, degree, stats)
+
+
+def consistent_matches(src, dst, *, tolerance, min_length=0.0):
+    """The matches that agree with each other in length (contract (C)): a rigid motion keeps lengths, so rows
+    i and j can both be right only if ``|src[i] - src[j]|`` and ``|dst[i] - dst[j]|`` differ by at most ``tolerance``; pairs closer
+    than ``min_length`` in either cloud say little and are not compatible.  These tests form a graph on the matches -- the right
+    ones a clique in it --, and what is kept is its maximal core: the rows of the largest core number (TEASER++'s k-core
+    heuristic).  All integers, no seed: the same result on every run.
+
+    ``src``, ``dst``: (m, 3) matched points, 3 <= m <= 32 768 (thin the matches first if there are more), both numpy arrays or both
+    CUDA torch tensors; float32 is widened exactly.  Returns a ``ConsistencyResult``; a pose estimator then takes
+    ``src[res.keep]``, ``dst[res.keep]``."""
+    t, l = consistency_arguments(tolerance, min_length)
+    on_device, src, dst, m = _consistency_rows(src, dst)
+    _refuse_distributed("consistent_matches")
+    ctx = _consistency_context()
+    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+    return _consistency(ctx, on_device, S, D, m, t, l)
+
+
 def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighbors=10, viewpoint_fixed=None, viewpoint_movable=None,
                     mutual=True, **ransac_kwargs):
     """A coarse pose of ``movable`` onto ``fixed`` without an initial guess -- in the direction of ``run()``'s H --: the FPFH
@@ -446,8 +526,19 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     result has one candidate ``(H, inliers, -1)`` -- none when the fit is void -- and the robust fit's record (n_poses, n_void,
     best, best_inliers) as ``stats``.
 
+    ``prune=tolerance`` (default None: nothing), under either method, sends the matched rows through ``consistent_matches``
+    (``min_length=prune_min_length``, default 0.0) before the estimator, which then sees only the rows of the maximal core:
+    ``n_consistent`` is their number, ``n_matches`` stays the count before the pruning, fewer than three rows left give the result
+    without a pose, and ``index`` (and ``triples``) are rows of the pruned set.  More than 32 768 matches raise ``ValueError``.
+
     Returns ``ransac_pose``'s GlobalResult with ``n_matches`` set; fewer than three matches give a result without a pose.
     ICP stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
+    prune = ransac_kwargs.pop("prune", None)
+    if prune is None:
+        if "prune_min_length" in ransac_kwargs:
+            raise TypeError("register_global() got prune_min_length without prune")
+    else:
+        prune = consistency_arguments(prune, ransac_kwargs.pop("prune_min_length", 0.0))
     method = ransac_kwargs.pop("method", "ransac")
     if not isinstance(method, str):
         raise TypeError(f"method must be 'ransac' or 'robust', not {method!r}")
@@ -474,19 +565,29 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     idx = match_features(f_mov, f_fix, mutual=bool(mutual))
     keep = idx >= 0
     n_matches = int(keep.sum())
+    none = dict(n_poses=0, n_void=0, best=-1, best_inliers=-1) if robust else \
+        dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1)
     if n_matches < 3:
-        none = dict(n_poses=0, n_void=0, best=-1, best_inliers=-1) if robust else \
-            dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1)
         return GlobalResult([], none, n_matches)
     if not _is_torch(movable):
         fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
+    src, dst, n_consistent = movable[keep], fixed[idx[keep]], None
+    if prune is not None:
+        # the matched rows through sicp_match_consistency while they are where they are: the estimator sees the maximal core
+        on_device, src, dst, m = _consistency_rows(src, dst)
+        ctx = _consistency_context()
+        src, dst = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+        kept = _consistency(ctx, on_device, src, dst, m, *prune).keep
+        src, dst, n_consistent = src[kept], dst[kept], int(kept.sum())
+        if n_consistent < 3:
+            return GlobalResult([], none, n_matches, n_consistent=n_consistent)
     if robust:
         # the matched rows through sicp_pose_robust from the identity while they are where they are
-        on_device, src, dst, m = _matched_rows(movable[keep], fixed[idx[keep]])
+        on_device, src, dst, m = _matched_rows(src, dst)
         ctx = _robust_context()
         S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
         poses, inl, _, stats = _robust(ctx, on_device, S, D, m, None, *fit)
-        return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches)
-    res = _ransac_pose(movable[keep], fixed[idx[keep]], max_distance, refine=refine, **ransac_kwargs)
-    res.n_matches = n_matches
+        return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches, n_consistent=n_consistent)
+    res = _ransac_pose(src, dst, max_distance, refine=refine, **ransac_kwargs)
+    res.n_matches, res.n_consistent = n_matches, n_consistent
     return res
