@@ -98,6 +98,11 @@ CONSISTENCY_EXPORTS = ["sicp_consistency_version", "sicp_match_consistency"]
 CONSISTENCY_VERSION = 1
 CONSISTENCY_MAX_ROWS = 32768
 
+# include/simpleicp_hip_keypoints.h: ISS keypoints, the same kind of companion
+KEYPOINTS_EXPORTS = ["sicp_keypoints_version", "sicp_keypoints"]
+KEYPOINTS_VERSION = 1
+KEYPOINTS_MAX_K = 128
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -176,6 +181,14 @@ class ConsistencyStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class KeypointStats(C.Structure):
+    """struct sicp_keypoint_stats (contract (I)): 48 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_salient", "n_keypoints", "n_small", "n_clipped_salient", "n_clipped_nms")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -242,6 +255,8 @@ FEATURES = {
         "sicp_pose_robust": [_vp, _vp, _vp, _i64, _vp, _i64, _dbl, _cint, _dbl, _dbl, _vp, _vp, _vp, C.POINTER(RobustStats)]}),
     "consistency": _Feature(CONSISTENCY_EXPORTS, "simpleicp_hip_consistency.h", "match-consistency", CONSISTENCY_VERSION, {
         "sicp_match_consistency": [_vp, _vp, _vp, _i64, _dbl, _dbl, _vp, _vp, C.POINTER(ConsistencyStats)]}),
+    "keypoints": _Feature(KEYPOINTS_EXPORTS, "simpleicp_hip_keypoints.h", "keypoint", KEYPOINTS_VERSION, {
+        "sicp_keypoints": [_vp, _cint, _cint, _dbl, _cint, _dbl, _dbl, _dbl, _i64, _vp, _vp, _vp, C.POINTER(KeypointStats)]}),
 }
 
 _lib = None
@@ -405,6 +420,7 @@ global_version = partial(_feature_version, "global")
 posefit_version = partial(_feature_version, "posefit")
 robust_version = partial(_feature_version, "robust")
 consistency_version = partial(_feature_version, "consistency")
+keypoints_version = partial(_feature_version, "keypoints")
 
 
 def select_positions(m, Q):
@@ -801,6 +817,31 @@ class Context:
         cnt = np.empty((n, FPFH_BINS + 1), np.uint16) if want_counts else None
         self._chk(self._L.sicp_fpfh(self._h, slot, _ptr(normals), int(k), float(radius), _ptr(vp), _ptr(out), _ptr(cnt), C.byref(st)))
         return out, cnt, st
+
+    # -- ISS keypoints (contract (I)) --
+    def keypoints(self, slot, k_s, salient_radius=np.inf, k_n=None, nms_radius=np.inf, gamma21=0.975, gamma32=0.975, min_neighbors=5,
+                  keep_ptr=None, saliency_ptr=None, eig_ptr=None, want_saliency=False):
+        """sicp_keypoints: the ISS keypoints of the slot -- the points whose k_s nearest points within salient_radius (strict; inf
+        = none; the point itself included) have eigenvalues e2 < gamma21 * e1, e3 < gamma32 * e2, e3 > 0 and which no point of
+        their k_n nearest within nms_radius beats in e3 (k_n None: k_s).  Returns (bool verdicts (n,), (n,) float64 saliency
+        or None, (n, 3) float64 eigenvalues e1 e2 e3 or None, KeypointStats) -- the two arrays with want_saliency; with keep_ptr
+        (device memory, n bytes) the verdicts are left there, the saliency at saliency_ptr (n doubles) and the eigenvalues at
+        eig_ptr (3 n doubles) if given, and the KeypointStats alone is returned."""
+        keypoints_version()
+        n = self.size(slot)
+        kn = int(k_s) if k_n is None else int(k_n)
+        st = KeypointStats()
+        args = (int(k_s), float(salient_radius), kn, float(nms_radius), float(gamma21), float(gamma32), int(min_neighbors))
+        if keep_ptr is not None:
+            self._chk(self._L.sicp_keypoints(self._h, slot, *args, C.c_void_p(int(keep_ptr)),
+                                             None if saliency_ptr is None else C.c_void_p(int(saliency_ptr)),
+                                             None if eig_ptr is None else C.c_void_p(int(eig_ptr)), C.byref(st)))
+            return st
+        keep = np.empty(max(n, 1), np.uint8)
+        sal = np.empty(n, np.float64) if want_saliency else None
+        eig = np.empty((n, 3), np.float64) if want_saliency else None
+        self._chk(self._L.sicp_keypoints(self._h, slot, *args, _ptr(keep), _ptr(sal), _ptr(eig), C.byref(st)))
+        return keep[:n].view(np.bool_), sal, eig, st
 
     # -- descriptor matching and RANSAC poses (contracts (M) and (R)) --
     def feature_match(self, query, target, nq=None, nt=None, dim=None, idx_ptr=None, d2_ptr=None, want_d2=True):

@@ -256,6 +256,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FSCAN_CAP")) c->fscan_cap = std::atol(e);
     if (const char *e = std::getenv("SICP_OUTLIER_CHUNK")) c->outlier_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_KEYPOINT_CHUNK")) c->keypoint_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_ROBUST")) c->robust_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
     if (const char *e = std::getenv("SICP_CONSISTENCY")) c->consistency_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
@@ -308,6 +309,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
     c->ol_d.release(); c->ol_part.release(); c->ol_cnt.release();
     c->fp_nrm.release(); c->fp_out.release(); c->fp_cnt.release();
+    c->kp_sal.release(); c->kp_eig.release();
     c->gl_key.release(); c->gl_q.release(); c->gl_t.release(); c->gl_d2.release(); c->gl_idx.release(); c->gl_tri.release();
     c->gl_src.release(); c->gl_dst.release(); c->gl_pose.release();
     c->pf_in.release(); c->pf_state.release(); c->pf_part.release(); c->pf_part2.release(); c->pf_cnt.release();

@@ -326,6 +326,10 @@ struct sicp_ctx {
     DevBuf<float> fp_nrm, fp_out;
     DevBuf<uint16_t> fp_cnt;
     long fpfh_chunk = 0;           // SICP_FPFH_CHUNK: points per search of sicp_fpfh (0: chosen per call)
+    // ISS keypoints (sicp_keypoints.hip): the saliency of pass 1 by point (the salient rows lie in cand_rows, the verdict bytes on
+    // their way out in cand_keep), the staging buffers of the eigenvalues
+    DevBuf<double> kp_sal, kp_eig;
+    long keypoint_chunk = 0;       // SICP_KEYPOINT_CHUNK: points per search of sicp_keypoints (0: chosen per call)
     // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
     // the call's arrays
     DevBuf<unsigned long long> gl_key;

@@ -1,4 +1,5 @@
-"""FPFH descriptors: 33 floats per point, the local shape descriptor a global registration matches clouds by.
+"""FPFH descriptors: 33 floats per point, the local shape descriptor a global registration matches clouds by -- and ISS keypoints,
+the points worth describing (``keypoint_keep``; contract (I), DESIGN.md section 22, include/simpleicp_hip_keypoints.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -142,3 +143,114 @@ def _on_device(X, normals, k, r, kn, vp, return_counts):
         ctx.estimate_normals_into(_lib.FIX, sel.data_ptr(), n, kn, nv.data_ptr(), pl.data_ptr())
     ctx.fpfh(_lib.FIX, nv, k, r, vp, fpfh_ptr=out.data_ptr(), counts_ptr=None if cnt is None else cnt.data_ptr())
     return (out, cnt) if return_counts else out
+
+
+# ---- ISS keypoints (contract (I)) ----
+
+
+def _radius_of(name, radius):
+    if radius is None:
+        return math.inf
+    if isinstance(radius, (bool, str, bytes)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name} must be a number > 0 or None, not {radius!r}")
+    r = float(radius)
+    if math.isnan(r) or not r > 0.0:
+        raise ValueError(f"{name} must be > 0 (None: no radius), not {radius!r}")
+    return r
+
+
+def _gamma_of(name, gamma):
+    if isinstance(gamma, (bool, str, bytes)) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name} must be a number > 0, not {gamma!r}")
+    g = float(gamma)
+    if not math.isfinite(g) or not g > 0.0:
+        raise ValueError(f"{name} must be finite and > 0, not {gamma!r}")
+    return g
+
+
+def keypoint_arguments(neighbors=32, salient_radius=None, nms_neighbors=None, nms_radius=None, gamma21=0.975, gamma32=0.975,
+                       min_neighbors=5):
+    """(k_s, salient radius -- inf: none --, k_n, nms radius, gamma21, gamma32, min_neighbors), checked: TypeError / ValueError."""
+    k_s = _int_in("neighbors", neighbors, 2, _lib.KEYPOINTS_MAX_K)
+    k_n = k_s if nms_neighbors is None else _int_in("nms_neighbors", nms_neighbors, 2, _lib.KEYPOINTS_MAX_K)
+    return (k_s, _radius_of("salient_radius", salient_radius), k_n, _radius_of("nms_radius", nms_radius), _gamma_of("gamma21", gamma21),
+            _gamma_of("gamma32", gamma32), _int_in("min_neighbors", min_neighbors, 1, 2**62))
+
+
+def _check_keypoint_counts(n, a):
+    if a[0] > n:
+        raise ValueError(f"neighbors ({a[0]}) exceeds the number of points ({n})")
+    if a[2] > n:
+        raise ValueError(f"nms_neighbors ({a[2]}) exceeds the number of points ({n})")
+
+
+def _stats_dict(st):
+    return st.as_dict() if hasattr(st, "as_dict") else dict(st)
+
+
+def keypoint_keep(X, *, neighbors=32, salient_radius=None, nms_neighbors=None, nms_radius=None, gamma21=0.975, gamma32=0.975,
+                  min_neighbors=5, return_saliency=False):
+    """The ISS keypoints of X (Intrinsic Shape Signatures; contract (I)) as a bool mask (n,): True where
+    the point's neighbourhood is not flat, not a line and not a ball, and where it is the most salient point around.
+    ``X[keypoint_keep(X)]`` are the keypoints, as ``X[voxel_keep(X, c)]`` is the thinned cloud.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any
+    strides; ingest and stream rule are run_tensors').  A tensor gives a torch.bool tensor on its device, anything else numpy.
+    ``neighbors``: k of the support, the point itself included (2 .. 128); ``salient_radius``: only neighbours strictly closer
+    count (None: all k).  The eigenvalues e1 >= e2 >= e3 of the support's covariance make the point salient iff
+    e2 < ``gamma21`` * e1, e3 < ``gamma32`` * e2 and e3 > 0, with at least ``min_neighbors`` points counted; its saliency is e3.
+    ``nms_neighbors`` (None: ``neighbors``) and ``nms_radius`` (None: none): a salient point is a keypoint iff none of these
+    neighbours has a larger saliency -- of equals the lowest index stays -- and at least ``min_neighbors`` of them are counted.
+    ``return_saliency``: also the (n,) float64 saliency (0 where not salient), the (n, 3) float64 eigenvalues and the call's
+    record as a dict (n_points, n_salient, n_keypoints, n_small, n_clipped_salient, n_clipped_nms -- the clipped counts say how
+    many balls held more points than k).  The library's fixed slot holds X afterwards."""
+    from .pointcloud import PointCloud
+    from .tensors import _is_device_tensor
+    a = keypoint_arguments(neighbors, salient_radius, nms_neighbors, nms_radius, gamma21, gamma32, min_neighbors)
+    if not isinstance(return_saliency, (bool, np.bool_)):
+        raise TypeError(f"return_saliency must be True or False, not {return_saliency!r}")
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        return _keypoints_on_device(X, a, bool(return_saliency))
+    if isinstance(X, PointCloud):
+        n = len(X)
+    else:
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError("X must be a PointCloud, an (n, 3) array or a CUDA tensor")
+        n = X.shape[0]
+    if n == 0:
+        keep = np.zeros(0, bool)
+        none = dict(n_points=0, n_salient=0, n_keypoints=0, n_small=0, n_clipped_salient=0, n_clipped_nms=0)
+        return (keep, np.empty(0), np.empty((0, 3)), none) if return_saliency else keep
+    _check_keypoint_counts(n, a)
+    if dist.is_distributed():
+        from .icp import SimpleICPException
+        raise SimpleICPException("keypoint_keep does not run in a torch.distributed job: choose the keypoints with one process first")
+    ctx = backend.get_context()
+    if not hasattr(ctx, "keypoints"):
+        raise _lib.BackendError("this backend has no ISS keypoints")
+    ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this call)
+    dist.detach(ctx)
+    if isinstance(X, PointCloud):
+        X._upload(ctx, _lib.FIX)
+    else:
+        ctx.upload(_lib.FIX, X)
+    keep, sal, eig, st = ctx.keypoints(_lib.FIX, *a, want_saliency=bool(return_saliency))
+    return (keep, sal, eig, _stats_dict(st)) if return_saliency else keep
+
+
+def _keypoints_on_device(X, a, return_saliency):
+    import torch
+    from .tensors import _keep_opening
+    if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[0] > 0:
+        _check_keypoint_counts(X.shape[0], a)
+    ctx, n, _, keep = _keep_opening("keypoint_keep", X, None, needs=("keypoints", "ISS keypoints"))
+    sal = torch.empty(n, dtype=torch.float64, device=X.device) if return_saliency else None
+    eig = torch.empty((n, 3), dtype=torch.float64, device=X.device) if return_saliency else None
+    if ctx is None:
+        none = dict(n_points=0, n_salient=0, n_keypoints=0, n_small=0, n_clipped_salient=0, n_clipped_nms=0)
+        return (keep, sal, eig, none) if return_saliency else keep
+    st = ctx.keypoints(_lib.FIX, *a, keep_ptr=keep.data_ptr(), saliency_ptr=None if sal is None else sal.data_ptr(),
+                       eig_ptr=None if eig is None else eig.data_ptr())
+    keep = keep.view(torch.bool)
+    return (keep, sal, eig, _stats_dict(st)) if return_saliency else keep

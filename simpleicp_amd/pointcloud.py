@@ -56,6 +56,7 @@ def voxel_arguments(voxel_size, origin=None, exc=ValueError):
 
 class PointCloud(pd.DataFrame):
     last_outlier_stats = None             # select_statistical_inliers leaves its statistics here (a dict)
+    last_keypoint_stats = None            # select_keypoints leaves its record here (a dict)
 
     def __init__(self, *args, **kwargs) -> None:
         kwargs.pop("remapping", None)     # accepted and ignored, like the reference (pointcloud.py:25)
@@ -303,6 +304,30 @@ class PointCloud(pd.DataFrame):
         keep, _, st = ctx.outlier_statistical(_lib.FIX, int(neighbors), ratio, rows=None if len(cur) == self._num_points else cur)
         self.last_outlier_stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
         self._set_idx_selected(cur[keep])
+
+    def select_keypoints(self, neighbors: int = 32, salient_radius=None, nms_neighbors=None, nms_radius=None, gamma21: float = 0.975,
+                         gamma32: float = 0.975, min_neighbors: int = 5, _ctx=None) -> None:
+        """Keeps, among the selected points, the ISS keypoints of the WHOLE cloud and deselects the rest (contract (I), DESIGN.md
+        section 22; the keywords are ``keypoint_keep``'s): support and suppression are always among ALL points of the cloud, so a
+        selected point may lose to one that is not selected.  The record of the call is left in ``last_keypoint_stats``.  Not in
+        the reference; composes with select_in_range, select_voxels and select_n_points."""
+        from .features import _check_keypoint_counts, _stats_dict, keypoint_arguments
+        try:
+            a = keypoint_arguments(neighbors, salient_radius, nms_neighbors, nms_radius, gamma21, gamma32, min_neighbors)
+        except (TypeError, ValueError) as e:
+            raise PointCloudException(str(e)) from None
+        cur = self.idx_selected
+        if len(cur) == 0:
+            return
+        try:
+            _check_keypoint_counts(self._num_points, a)
+        except ValueError as e:
+            raise PointCloudException(str(e)) from None
+        ctx = _ctx or backend.get_context()
+        self._upload(ctx, _lib.FIX)
+        keep, _, _, st = ctx.keypoints(_lib.FIX, *a)
+        self.last_keypoint_stats = _stats_dict(st)
+        self._set_idx_selected(cur[np.asarray(keep)[cur]])
 
     def select_radius_inliers(self, radius: float, min_points: int, _ctx=None) -> None:
         """Keeps, among the selected points, those with more than ``min_points`` points of the cloud (ALL its points, the point

@@ -25,7 +25,7 @@ import math
 import numpy as np
 
 from . import _lib, backend, dist
-from .features import _int_in, fpfh_features
+from .features import _int_in, fpfh_features, keypoint_arguments, keypoint_keep
 from .tensors import _is_device_tensor
 
 
@@ -36,13 +36,15 @@ class GlobalResult:
     ``(-inliers, index)``; ``n_matches``: the matches the poses were drawn from (``register_global`` only); ``refined``: the
     record of the refit the candidates went through (n_poses, n_void, n_improved, best, best_inliers -- ``best`` a position among
     the unrefined candidates), None without one; ``n_consistent``: the matches the pruning left for the estimator
-    (``register_global(..., prune=...)`` only, None without it; ``n_matches`` stays the count before it)."""
+    (``register_global(..., prune=...)`` only, None without it; ``n_matches`` stays the count before it); ``n_keypoints``: the
+    ``(fixed, movable)`` numbers of keypoints the chain ran on (``register_global(..., keypoints=...)`` only, None without it)."""
 
-    def __init__(self, candidates, stats, n_matches=None, refined=None, n_consistent=None):
+    def __init__(self, candidates, stats, n_matches=None, refined=None, n_consistent=None, n_keypoints=None):
         self.candidates = list(candidates)
         self.stats = dict(stats)
         self.n_matches = n_matches
         self.n_consistent = n_consistent
+        self.n_keypoints = n_keypoints
         self.refined = None if refined is None else dict(refined)
         self.H, self.inliers, self.index = self.candidates[0] if self.candidates else (None, -1, -1)
 
@@ -531,8 +533,23 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     ``n_consistent`` is their number, ``n_matches`` stays the count before the pruning, fewer than three rows left give the result
     without a pose, and ``index`` (and ``triples``) are rows of the pruned set.  More than 32 768 matches raise ``ValueError``.
 
+    ``keypoints=`` (default None: nothing changes, bit for bit), under either method: True, or a dict of ``keypoint_keep``'s
+    keywords.  Both clouds are described over all their points as before; then descriptors and coordinates are gathered at each
+    cloud's ISS keypoints and the rest of the chain -- matching, pruning, the estimator -- runs on those rows alone.
+    ``n_keypoints = (fixed, movable)`` is their number, fewer than three on a side give the result without a pose, and ``index``
+    (and ``triples``) are rows of the keypoint sets (of their matched, of their pruned rows), not of the clouds.
+
     Returns ``ransac_pose``'s GlobalResult with ``n_matches`` set; fewer than three matches give a result without a pose.
     ICP stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
+    keypoints = ransac_kwargs.pop("keypoints", None)
+    if keypoints is not None:
+        if keypoints is True:
+            keypoints = {}
+        elif not isinstance(keypoints, dict):
+            raise TypeError(f"keypoints must be None, True or a dict of keypoint_keep's keywords, not {keypoints!r}")
+        if "return_saliency" in keypoints:
+            raise TypeError("keypoints= takes keypoint_keep's keywords without return_saliency")
+        keypoint_arguments(**keypoints)
     prune = ransac_kwargs.pop("prune", None)
     if prune is None:
         if "prune_min_length" in ransac_kwargs:
@@ -562,13 +579,23 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     _refuse_distributed("register_global")
     f_fix = fpfh_features(fixed, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_fixed)
     f_mov = fpfh_features(movable, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_movable)
+    none = dict(n_poses=0, n_void=0, best=-1, best_inliers=-1) if robust else \
+        dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1)
+    n_keypoints = None
+    if keypoints is not None:
+        # descriptors and coordinates gathered at each cloud's keypoints, where they are: the chain goes on with those rows
+        if not _is_torch(movable):
+            fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
+        k_fix, k_mov = keypoint_keep(fixed, **keypoints), keypoint_keep(movable, **keypoints)
+        n_keypoints = (int(k_fix.sum()), int(k_mov.sum()))
+        if min(n_keypoints) < 3:
+            return GlobalResult([], none, 0, n_keypoints=n_keypoints)
+        fixed, movable, f_fix, f_mov = fixed[k_fix], movable[k_mov], f_fix[k_fix], f_mov[k_mov]
     idx = match_features(f_mov, f_fix, mutual=bool(mutual))
     keep = idx >= 0
     n_matches = int(keep.sum())
-    none = dict(n_poses=0, n_void=0, best=-1, best_inliers=-1) if robust else \
-        dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1)
     if n_matches < 3:
-        return GlobalResult([], none, n_matches)
+        return GlobalResult([], none, n_matches, n_keypoints=n_keypoints)
     if not _is_torch(movable):
         fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
     src, dst, n_consistent = movable[keep], fixed[idx[keep]], None
@@ -580,14 +607,15 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
         kept = _consistency(ctx, on_device, src, dst, m, *prune).keep
         src, dst, n_consistent = src[kept], dst[kept], int(kept.sum())
         if n_consistent < 3:
-            return GlobalResult([], none, n_matches, n_consistent=n_consistent)
+            return GlobalResult([], none, n_matches, n_consistent=n_consistent, n_keypoints=n_keypoints)
     if robust:
         # the matched rows through sicp_pose_robust from the identity while they are where they are
         on_device, src, dst, m = _matched_rows(src, dst)
         ctx = _robust_context()
         S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
         poses, inl, _, stats = _robust(ctx, on_device, S, D, m, None, *fit)
-        return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches, n_consistent=n_consistent)
+        return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches, n_consistent=n_consistent,
+                            n_keypoints=n_keypoints)
     res = _ransac_pose(src, dst, max_distance, refine=refine, **ransac_kwargs)
-    res.n_matches, res.n_consistent = n_matches, n_consistent
+    res.n_matches, res.n_consistent, res.n_keypoints = n_matches, n_consistent, n_keypoints
     return res
