@@ -118,75 +118,60 @@ class EvalRecord(C.Structure):
                 ("sum_pp", C.c_double * 6)]
 
 
-class OutlierStats(C.Structure):
+class _Stats(C.Structure):
+    """A call's record, one field per counter or moment: as_dict() gives them in the structure's order, the int64 fields as int,
+    the doubles as float."""
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+def _stats_dict(st):
+    """A call's record as a dict, whether the context returned one of the structures above or (another backend) a mapping."""
+    return st.as_dict() if hasattr(st, "as_dict") else dict(st)
+
+
+class OutlierStats(_Stats):
     """struct sicp_outlier_stats (contract (O)): 40 bytes."""
     _fields_ = [("n_candidates", C.c_int64), ("n_kept", C.c_int64), ("mean", C.c_double), ("std", C.c_double),
                 ("threshold", C.c_double)]
 
-    def as_dict(self):
-        return dict(n_candidates=int(self.n_candidates), n_kept=int(self.n_kept), mean=float(self.mean), std=float(self.std),
-                    threshold=float(self.threshold))
 
-
-class FpfhStats(C.Structure):
+class FpfhStats(_Stats):
     """struct sicp_fpfh_stats (contract (F)): 32 bytes."""
     _fields_ = [("n_points", C.c_int64), ("n_pairs", C.c_int64), ("n_void_pairs", C.c_int64), ("n_empty", C.c_int64)]
 
-    def as_dict(self):
-        return dict(n_points=int(self.n_points), n_pairs=int(self.n_pairs), n_void_pairs=int(self.n_void_pairs),
-                    n_empty=int(self.n_empty))
 
-
-class MatchStats(C.Structure):
+class MatchStats(_Stats):
     """struct sicp_match_stats (contract (M)): 24 bytes."""
     _fields_ = [("n_query", C.c_int64), ("n_target", C.c_int64), ("n_unmatched", C.c_int64)]
 
-    def as_dict(self):
-        return dict(n_query=int(self.n_query), n_target=int(self.n_target), n_unmatched=int(self.n_unmatched))
 
-
-class RansacStats(C.Structure):
+class RansacStats(_Stats):
     """struct sicp_ransac_stats (contract (R)): 40 bytes."""
     _fields_ = [("n_hypotheses", C.c_int64), ("n_void", C.c_int64), ("n_pruned", C.c_int64), ("best", C.c_int64),
                 ("best_inliers", C.c_int64)]
 
-    def as_dict(self):
-        return dict(n_hypotheses=int(self.n_hypotheses), n_void=int(self.n_void), n_pruned=int(self.n_pruned), best=int(self.best),
-                    best_inliers=int(self.best_inliers))
 
-
-class PosefitStats(C.Structure):
+class PosefitStats(_Stats):
     """struct sicp_posefit_stats (contract (L)): 40 bytes."""
     _fields_ = [("n_poses", C.c_int64), ("n_void", C.c_int64), ("n_improved", C.c_int64), ("best", C.c_int64),
                 ("best_inliers", C.c_int64)]
 
-    def as_dict(self):
-        return dict(n_poses=int(self.n_poses), n_void=int(self.n_void), n_improved=int(self.n_improved), best=int(self.best),
-                    best_inliers=int(self.best_inliers))
 
-
-class RobustStats(C.Structure):
+class RobustStats(_Stats):
     """struct sicp_robust_stats (contract (G)): 32 bytes."""
     _fields_ = [("n_poses", C.c_int64), ("n_void", C.c_int64), ("best", C.c_int64), ("best_inliers", C.c_int64)]
 
-    def as_dict(self):
-        return dict(n_poses=int(self.n_poses), n_void=int(self.n_void), best=int(self.best), best_inliers=int(self.best_inliers))
 
-
-class ConsistencyStats(C.Structure):
+class ConsistencyStats(_Stats):
     """struct sicp_consistency_stats (contract (C)): 56 bytes."""
     _fields_ = [(name, C.c_int64) for name in ("n_rows", "n_valid", "n_edges", "max_degree", "max_core", "n_max_core", "n_subrounds")]
 
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
-
-class KeypointStats(C.Structure):
+class KeypointStats(_Stats):
     """struct sicp_keypoint_stats (contract (I)): 48 bytes."""
     _fields_ = [(name, C.c_int64) for name in ("n_points", "n_salient", "n_keypoints", "n_small", "n_clipped_salient", "n_clipped_nms")]
-
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class IterParams(C.Structure):
@@ -351,14 +336,21 @@ def load():
 
 
 def _ptr(a):
-    """numpy array / torch tensor / None -> void* (host-or-device pointer)."""
+    """numpy array / torch tensor / address as an int / None -> void* (host-or-device pointer)."""
     if a is None:
         return None
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(C.c_void_p)
     if hasattr(a, "data_ptr"):          # torch.Tensor (host or device)
         return C.c_void_p(a.data_ptr())
+    if isinstance(a, (int, np.integer)):
+        return C.c_void_p(int(a))
     raise TypeError(f"unsupported buffer type {type(a)}")
+
+
+def _chk(L, rc):
+    if rc != OK:
+        raise BackendError(L.sicp_last_error().decode(), rc)
 
 
 def _f64(a):
@@ -372,14 +364,14 @@ def _matched_rows(src, dst):
 
 
 def _pose_call_arrays(src, dst, poses):
-    """Host form of pose_refit / pose_robust: the checked arrays (poses None: one pose), the number of poses, and the (n, 12)
-    poses and (n,) inliers that leave."""
+    """Host form of pose_refit / pose_robust: the checked arrays (poses None: one pose), and the (b, 12) poses and (b,) inliers
+    that leave."""
     s, d, ok = _matched_rows(src, dst)
     p = None if poses is None else _f64(poses)
     if not ok or (p is not None and (p.ndim != 2 or p.shape[1] != 12)):
         raise ValueError("src and dst must be (m, 3), poses (b, 12) or None")
-    n = 1 if p is None else p.shape[0]
-    return s, d, p, n, np.empty((n, 12), np.float64), np.empty(n, np.int32)
+    b = 1 if p is None else p.shape[0]
+    return s, d, p, np.empty((b, 12), np.float64), np.empty(b, np.int32)
 
 
 def device_count():
@@ -429,9 +421,7 @@ def select_positions(m, Q):
     L = load()
     out = np.empty(max(min(int(m), int(Q)), 1), np.int64)
     cnt = C.c_int64()
-    rc = L.sicp_select_positions(int(m), int(Q), _ptr(out), C.byref(cnt))
-    if rc != OK:
-        raise BackendError(L.sicp_last_error().decode(), rc)
+    _chk(L, L.sicp_select_positions(int(m), int(Q), _ptr(out), C.byref(cnt)))
     return out[:cnt.value]
 
 
@@ -469,9 +459,7 @@ def icp_run_batch(members):
         m.min_change = float(kw.get("min_change", 1.0))
     fb = C.c_int64()
     L = load()
-    rc = L.sicp_icp_run_batch(arr, len(members), C.byref(fb))
-    if rc != OK:
-        raise BackendError(L.sicp_last_error().decode(), rc)
+    _chk(L, L.sicp_icp_run_batch(arr, len(members), C.byref(fb)))
     out = []
     for i in range(len(members)):
         m = arr[i]
@@ -496,8 +484,7 @@ class Context:
 
     # -- plumbing --
     def _chk(self, rc):
-        if rc != OK:
-            raise BackendError(self._L.sicp_last_error().decode(), rc)
+        _chk(self._L, rc)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -648,31 +635,28 @@ class Context:
     def set_planarity(self, slot, planarity=None, rows=None, n_global=None):
         """The cloud's `planarity` column (corrpts.py:158-163 tests the movable cloud's too): a dense float32 vector
         by global point index, or (rows, values) pairs with NaN elsewhere; None = no such column."""
-        if planarity is None:
-            self._chk(self._L.sicp_cloud_set_planarity(self._h, slot, None, None, 0, 0))
-            return
-        pl = np.ascontiguousarray(planarity, dtype=np.float32)
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
-        if r is not None and len(r) != len(pl):
-            raise ValueError("rows and planarity must have the same length")
-        n = int(n_global if n_global is not None else (len(pl) if r is None else self.size(slot)))
-        dummy = np.zeros(1, np.float32)
-        self._chk(self._L.sicp_cloud_set_planarity(self._h, slot, _ptr(r), _ptr(pl if len(pl) else dummy), len(pl), n))
+        self._set_columns(self._L.sicp_cloud_set_planarity, "planarity", 1, slot, planarity, rows, n_global)
 
     def set_normals(self, slot, normals=None, rows=None, n_global=None):
         """The cloud's normal columns (sicp_cloud_set_normals), like set_planarity: a dense (n, 3) float32 block by global point
         index, or (rows, normals) pairs with NaN elsewhere; None = no such columns."""
         normals_version()
-        if normals is None:
-            self._chk(self._L.sicp_cloud_set_normals(self._h, slot, None, None, 0, 0))
+        self._set_columns(self._L.sicp_cloud_set_normals, "normals", 3, slot, normals, rows, n_global)
+
+    def _set_columns(self, entry, what, width, slot, values, rows, n_global):
+        """set_planarity and set_normals: `width` float32 columns per point through `entry`."""
+        if values is None:
+            self._chk(entry(self._h, slot, None, None, 0, 0))
             return
-        nv = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if width > 1:
+            v = v.reshape(-1, width)
         r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
-        if r is not None and len(r) != len(nv):
-            raise ValueError("rows and normals must have the same length")
-        n = int(n_global if n_global is not None else (len(nv) if r is None else self.size(slot)))
-        dummy = np.zeros(3, np.float32)
-        self._chk(self._L.sicp_cloud_set_normals(self._h, slot, _ptr(r), _ptr(nv if len(nv) else dummy), len(nv), n))
+        if r is not None and len(r) != len(v):
+            raise ValueError(f"rows and {what} must have the same length")
+        n = int(n_global if n_global is not None else (len(v) if r is None else self.size(slot)))
+        dummy = np.zeros(width, np.float32)
+        self._chk(entry(self._h, slot, _ptr(r), _ptr(v if len(v) else dummy), len(v), n))
 
     def normal_angle_set(self, cos_max=None, k=10):
         """The ctx setting sicp_icp_run / sicp_icp_iterate honour (sicp_normal_angle_set): reject correspondences whose normals
@@ -721,13 +705,9 @@ class Context:
         m = self.size(slot) if r is None else len(r)
         o = None if origin is None else _f64(origin).reshape(3)
         kept = C.c_int64()
-        if keep_ptr is not None:
-            self._chk(self._L.sicp_voxel_select(self._h, slot, _ptr(r), m, float(voxel_size), _ptr(o), C.c_void_p(int(keep_ptr)),
-                                                C.byref(kept)))
-            return kept.value
-        out = np.empty(max(m, 1), dtype=np.uint8)
+        out = np.empty(max(m, 1), dtype=np.uint8) if keep_ptr is None else keep_ptr
         self._chk(self._L.sicp_voxel_select(self._h, slot, _ptr(r), m, float(voxel_size), _ptr(o), _ptr(out), C.byref(kept)))
-        return out[:m].view(np.bool_)
+        return out[:m].view(np.bool_) if keep_ptr is None else kept.value
 
     def voxel_select_masked(self, slot, mask_ptr, n, voxel_size, origin=None, keep_ptr=None):
         """sicp_voxel_select_masked: the candidates are the points whose byte of the device mask (n bytes at mask_ptr) is non-zero;
@@ -758,15 +738,11 @@ class Context:
         outlier_version()
         r, N = self._outlier_shape(slot, rows, mask_ptr)
         st = OutlierStats()
-        mp = None if mask_ptr is None else C.c_void_p(int(mask_ptr))
-        if keep_ptr is not None:
-            self._chk(self._L.sicp_outlier_statistical(self._h, slot, _ptr(r), N, mp, int(k), float(std_ratio), C.c_void_p(int(keep_ptr)),
-                                                       None if mean_ptr is None else C.c_void_p(int(mean_ptr)), C.byref(st)))
-            return st
-        keep, d = np.empty(max(N, 1), np.uint8), np.empty(max(N, 1), np.float64)
-        self._chk(self._L.sicp_outlier_statistical(self._h, slot, _ptr(r), N, mp, int(k), float(std_ratio), _ptr(keep), _ptr(d),
-                                                   C.byref(st)))
-        return keep[:N].view(np.bool_), d[:N], st
+        host = keep_ptr is None
+        keep, d = (np.empty(max(N, 1), np.uint8), np.empty(max(N, 1), np.float64)) if host else (keep_ptr, mean_ptr)
+        self._chk(self._L.sicp_outlier_statistical(self._h, slot, _ptr(r), N, _ptr(mask_ptr), int(k), float(std_ratio), _ptr(keep),
+                                                   _ptr(d), C.byref(st)))
+        return (keep[:N].view(np.bool_), d[:N], st) if host else st
 
     def outlier_radius(self, slot, radius, min_points, rows=None, mask_ptr=None, keep_ptr=None, count_ptr=None):
         """sicp_outlier_radius: the candidates (as outlier_statistical takes them) with more than min_points points of the slot,
@@ -776,15 +752,11 @@ class Context:
         outlier_version()
         r, N = self._outlier_shape(slot, rows, mask_ptr)
         kept = C.c_int64()
-        mp = None if mask_ptr is None else C.c_void_p(int(mask_ptr))
-        if keep_ptr is not None:
-            self._chk(self._L.sicp_outlier_radius(self._h, slot, _ptr(r), N, mp, float(radius), int(min_points), C.c_void_p(int(keep_ptr)),
-                                                  None if count_ptr is None else C.c_void_p(int(count_ptr)), C.byref(kept)))
-            return kept.value
-        keep, cnt = np.empty(max(N, 1), np.uint8), np.empty(max(N, 1), np.uint32)
-        self._chk(self._L.sicp_outlier_radius(self._h, slot, _ptr(r), N, mp, float(radius), int(min_points), _ptr(keep), _ptr(cnt),
-                                              C.byref(kept)))
-        return keep[:N].view(np.bool_), cnt[:N], kept.value
+        host = keep_ptr is None
+        keep, cnt = (np.empty(max(N, 1), np.uint8), np.empty(max(N, 1), np.uint32)) if host else (keep_ptr, count_ptr)
+        self._chk(self._L.sicp_outlier_radius(self._h, slot, _ptr(r), N, _ptr(mask_ptr), float(radius), int(min_points), _ptr(keep),
+                                              _ptr(cnt), C.byref(kept)))
+        return (keep[:N].view(np.bool_), cnt[:N], kept.value) if host else kept.value
 
     def outlier_radius_cells(self, slot, radius):
         """sicp_outlier_radius_cells: (cells along x, y, z, their product) of the box a ball of this radius spans on the slot's
@@ -809,14 +781,13 @@ class Context:
             raise ValueError("normals must have shape (n, 3), one row per point of the slot")
         vp = None if viewpoint is None else _f64(viewpoint).reshape(3)
         st = FpfhStats()
-        if fpfh_ptr is not None:
-            self._chk(self._L.sicp_fpfh(self._h, slot, _ptr(normals), int(k), float(radius), _ptr(vp), C.c_void_p(int(fpfh_ptr)),
-                                        None if counts_ptr is None else C.c_void_p(int(counts_ptr)), C.byref(st)))
-            return st
-        out = np.empty((n, FPFH_BINS), np.float32)
-        cnt = np.empty((n, FPFH_BINS + 1), np.uint16) if want_counts else None
+        host = fpfh_ptr is None
+        out, cnt = fpfh_ptr, counts_ptr
+        if host:
+            out = np.empty((n, FPFH_BINS), np.float32)
+            cnt = np.empty((n, FPFH_BINS + 1), np.uint16) if want_counts else None
         self._chk(self._L.sicp_fpfh(self._h, slot, _ptr(normals), int(k), float(radius), _ptr(vp), _ptr(out), _ptr(cnt), C.byref(st)))
-        return out, cnt, st
+        return (out, cnt, st) if host else st
 
     # -- ISS keypoints (contract (I)) --
     def keypoints(self, slot, k_s, salient_radius=np.inf, k_n=None, nms_radius=np.inf, gamma21=0.975, gamma32=0.975, min_neighbors=5,
@@ -832,16 +803,14 @@ class Context:
         kn = int(k_s) if k_n is None else int(k_n)
         st = KeypointStats()
         args = (int(k_s), float(salient_radius), kn, float(nms_radius), float(gamma21), float(gamma32), int(min_neighbors))
-        if keep_ptr is not None:
-            self._chk(self._L.sicp_keypoints(self._h, slot, *args, C.c_void_p(int(keep_ptr)),
-                                             None if saliency_ptr is None else C.c_void_p(int(saliency_ptr)),
-                                             None if eig_ptr is None else C.c_void_p(int(eig_ptr)), C.byref(st)))
-            return st
-        keep = np.empty(max(n, 1), np.uint8)
-        sal = np.empty(n, np.float64) if want_saliency else None
-        eig = np.empty((n, 3), np.float64) if want_saliency else None
+        host = keep_ptr is None
+        keep, sal, eig = keep_ptr, saliency_ptr, eig_ptr
+        if host:
+            keep = np.empty(max(n, 1), np.uint8)
+            sal = np.empty(n, np.float64) if want_saliency else None
+            eig = np.empty((n, 3), np.float64) if want_saliency else None
         self._chk(self._L.sicp_keypoints(self._h, slot, *args, _ptr(keep), _ptr(sal), _ptr(eig), C.byref(st)))
-        return keep[:n].view(np.bool_), sal, eig, st
+        return (keep[:n].view(np.bool_), sal, eig, st) if host else st
 
     # -- descriptor matching and RANSAC poses (contracts (M) and (R)) --
     def feature_match(self, query, target, nq=None, nt=None, dim=None, idx_ptr=None, d2_ptr=None, want_d2=True):
@@ -852,19 +821,17 @@ class Context:
         given (nq float32), and the MatchStats alone is returned."""
         global_version()
         st = MatchStats()
-        if idx_ptr is not None:
-            self._chk(self._L.sicp_feature_match(self._h, C.c_void_p(int(query)), int(nq), C.c_void_p(int(target)), int(nt), int(dim),
-                                                 C.c_void_p(int(idx_ptr)), None if d2_ptr is None else C.c_void_p(int(d2_ptr)),
-                                                 C.byref(st)))
-            return st
-        q, t = np.ascontiguousarray(query, dtype=np.float32), np.ascontiguousarray(target, dtype=np.float32)
-        if q.ndim != 2 or t.ndim != 2 or q.shape[1] != t.shape[1]:
-            raise ValueError("query and target must be (nq, dim) and (nt, dim)")
-        idx = np.empty(q.shape[0], np.int32)
-        d2 = np.empty(q.shape[0], np.float32) if want_d2 else None
-        self._chk(self._L.sicp_feature_match(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], q.shape[1], _ptr(idx), _ptr(d2),
-                                             C.byref(st)))
-        return idx, d2, st
+        host = idx_ptr is None
+        q, t, idx, d2 = query, target, idx_ptr, d2_ptr
+        if host:
+            q, t = np.ascontiguousarray(query, dtype=np.float32), np.ascontiguousarray(target, dtype=np.float32)
+            if q.ndim != 2 or t.ndim != 2 or q.shape[1] != t.shape[1]:
+                raise ValueError("query and target must be (nq, dim) and (nt, dim)")
+            nq, nt, dim = q.shape[0], t.shape[0], q.shape[1]
+            idx = np.empty(nq, np.int32)
+            d2 = np.empty(nq, np.float32) if want_d2 else None
+        self._chk(self._L.sicp_feature_match(self._h, _ptr(q), int(nq), _ptr(t), int(nt), int(dim), _ptr(idx), _ptr(d2), C.byref(st)))
+        return (idx, d2, st) if host else st
 
     def ransac_triplets(self, src, dst, triples, max_distance, edge_ratio, m=None, h=None, poses_ptr=None, inliers_ptr=None,
                         want_poses=True):
@@ -875,21 +842,19 @@ class Context:
         at inliers_ptr (h int32), the poses at poses_ptr if given (h * 12 doubles), and the RansacStats alone is returned."""
         global_version()
         st = RansacStats()
-        if inliers_ptr is not None:
-            self._chk(self._L.sicp_ransac_triplets(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m), C.c_void_p(int(triples)),
-                                                   int(h), float(max_distance), float(edge_ratio),
-                                                   None if poses_ptr is None else C.c_void_p(int(poses_ptr)),
-                                                   C.c_void_p(int(inliers_ptr)), C.byref(st)))
-            return st
-        s, d, ok = _matched_rows(src, dst)
-        tri = np.ascontiguousarray(triples, dtype=np.int32)
-        if not ok or tri.ndim != 2 or tri.shape[1] != 3:
-            raise ValueError("src and dst must be (m, 3), triples (h, 3)")
-        poses = np.empty((tri.shape[0], 12), np.float64) if want_poses else None
-        inl = np.empty(tri.shape[0], np.int32)
-        self._chk(self._L.sicp_ransac_triplets(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(tri), tri.shape[0], float(max_distance),
+        host = inliers_ptr is None
+        s, d, tri, poses, inl = src, dst, triples, poses_ptr, inliers_ptr
+        if host:
+            s, d, ok = _matched_rows(src, dst)
+            tri = np.ascontiguousarray(triples, dtype=np.int32)
+            if not ok or tri.ndim != 2 or tri.shape[1] != 3:
+                raise ValueError("src and dst must be (m, 3), triples (h, 3)")
+            m, h = s.shape[0], tri.shape[0]
+            poses = np.empty((h, 12), np.float64) if want_poses else None
+            inl = np.empty(h, np.int32)
+        self._chk(self._L.sicp_ransac_triplets(self._h, _ptr(s), _ptr(d), int(m), _ptr(tri), int(h), float(max_distance),
                                                float(edge_ratio), _ptr(poses), _ptr(inl), C.byref(st)))
-        return poses, inl, st
+        return (poses, inl, st) if host else st
 
     # -- least-squares poses of matched rows (contract (L)) --
     def pose_refit(self, src, dst, poses, max_distance, rounds, m=None, b=None, poses_ptr=None, inliers_ptr=None):
@@ -901,15 +866,13 @@ class Context:
         (b * 12 doubles), the inliers at inliers_ptr (b int32), and the PosefitStats alone is returned."""
         posefit_version()
         st = PosefitStats()
-        if inliers_ptr is not None:
-            self._chk(self._L.sicp_pose_refit(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m),
-                                              None if poses is None else C.c_void_p(int(poses)), int(b), float(max_distance), int(rounds),
-                                              C.c_void_p(int(poses_ptr)), C.c_void_p(int(inliers_ptr)), C.byref(st)))
-            return st
-        s, d, p, n, out, inl = _pose_call_arrays(src, dst, poses)
-        self._chk(self._L.sicp_pose_refit(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds), _ptr(out),
+        host = inliers_ptr is None
+        s, d, p, out, inl = _pose_call_arrays(src, dst, poses) if host else (src, dst, poses, poses_ptr, inliers_ptr)
+        if host:
+            m, b = s.shape[0], len(inl)
+        self._chk(self._L.sicp_pose_refit(self._h, _ptr(s), _ptr(d), int(m), _ptr(p), int(b), float(max_distance), int(rounds), _ptr(out),
                                           _ptr(inl), C.byref(st)))
-        return out, inl, st
+        return (out, inl, st) if host else st
 
     # -- robust poses of matched rows (contract (G)) --
     def pose_robust(self, src, dst, poses, max_distance, rounds, divisor, start_scale=0.0, m=None, b=None, poses_ptr=None,
@@ -924,17 +887,15 @@ class Context:
         returned."""
         robust_version()
         st = RobustStats()
-        if inliers_ptr is not None:
-            self._chk(self._L.sicp_pose_robust(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m),
-                                               None if poses is None else C.c_void_p(int(poses)), int(b), float(max_distance), int(rounds),
-                                               float(divisor), float(start_scale), C.c_void_p(int(poses_ptr)), C.c_void_p(int(inliers_ptr)),
-                                               C.c_void_p(int(scales_ptr)), C.byref(st)))
-            return st
-        s, d, p, n, out, inl = _pose_call_arrays(src, dst, poses)
-        scales = np.empty(n, np.float64)
-        self._chk(self._L.sicp_pose_robust(self._h, _ptr(s), _ptr(d), s.shape[0], _ptr(p), n, float(max_distance), int(rounds),
+        host = inliers_ptr is None
+        s, d, p, out, inl = _pose_call_arrays(src, dst, poses) if host else (src, dst, poses, poses_ptr, inliers_ptr)
+        scales = scales_ptr
+        if host:
+            m, b = s.shape[0], len(inl)
+            scales = np.empty(b, np.float64)
+        self._chk(self._L.sicp_pose_robust(self._h, _ptr(s), _ptr(d), int(m), _ptr(p), int(b), float(max_distance), int(rounds),
                                            float(divisor), float(start_scale), _ptr(out), _ptr(inl), _ptr(scales), C.byref(st)))
-        return out, inl, scales, st
+        return (out, inl, scales, st) if host else st
 
     # -- matches pruned by pairwise length consistency (contract (C)) --
     def match_consistency(self, src, dst, tolerance, min_length, m=None, degree_ptr=None, core_ptr=None):
@@ -945,18 +906,17 @@ class Context:
         at degree_ptr and the core numbers at core_ptr (m int32 each), and the ConsistencyStats alone is returned."""
         consistency_version()
         st = ConsistencyStats()
-        if degree_ptr is not None:
-            self._chk(self._L.sicp_match_consistency(self._h, C.c_void_p(int(src)), C.c_void_p(int(dst)), int(m), float(tolerance),
-                                                     float(min_length), C.c_void_p(int(degree_ptr)), C.c_void_p(int(core_ptr)),
-                                                     C.byref(st)))
-            return st
-        s, d, ok = _matched_rows(src, dst)
-        if not ok:
-            raise ValueError("src and dst must be (m, 3)")
-        degree, core = np.empty(s.shape[0], np.int32), np.empty(s.shape[0], np.int32)
-        self._chk(self._L.sicp_match_consistency(self._h, _ptr(s), _ptr(d), s.shape[0], float(tolerance), float(min_length), _ptr(degree),
+        host = degree_ptr is None
+        s, d, degree, core = src, dst, degree_ptr, core_ptr
+        if host:
+            s, d, ok = _matched_rows(src, dst)
+            if not ok:
+                raise ValueError("src and dst must be (m, 3)")
+            m = s.shape[0]
+            degree, core = np.empty(m, np.int32), np.empty(m, np.int32)
+        self._chk(self._L.sicp_match_consistency(self._h, _ptr(s), _ptr(d), int(m), float(tolerance), float(min_length), _ptr(degree),
                                                  _ptr(core), C.byref(st)))
-        return degree, core, st
+        return (degree, core, st) if host else st
 
     # -- how good a registration is (contract (E)) --
     def evaluate(self, query_slot, search_slot, H=None, max_distance=np.inf, rows=None):
@@ -1018,8 +978,7 @@ class Context:
     def icp_iterate(self, x, obs, obs_weight, min_planarity=0.3, distance_weight=1.0, max_lm_steps=0):
         """One iteration; distance_weight None = automatic (simpleicp.py:233-234).  Returns IterResult;
         raises BackendError(code=ERR_TOO_FEW) when fewer than 6 correspondences survive."""
-        P = IterParams((C.c_double * 6)(*x), (C.c_double * 6)(*obs), (C.c_double * 6)(*obs_weight),
-                       min_planarity, -1.0 if distance_weight is None else distance_weight, int(max_lm_steps))
+        P = self._params(x, obs, obs_weight, min_planarity, distance_weight, max_lm_steps)
         R = IterResult()
         rc = self._L.sicp_icp_iterate(self._h, C.byref(P), C.byref(R))
         if rc != OK:
@@ -1037,8 +996,7 @@ class Context:
                 max_lm_steps=0):
         """The whole loop in one ABI call (sicp_icp_run).  Returns the list of per-iteration IterResult;
         raises BackendError (with `.results`) like icp_iterate when an iteration fails."""
-        P = IterParams((C.c_double * 6)(*x), (C.c_double * 6)(*obs), (C.c_double * 6)(*obs_weight),
-                       min_planarity, -1.0 if distance_weight is None else distance_weight, int(max_lm_steps))
+        P = self._params(x, obs, obs_weight, min_planarity, distance_weight, max_lm_steps)
         n = int(max_iterations)
         res = (IterResult * max(n, 1))()
         done = C.c_int64()
@@ -1109,8 +1067,7 @@ class Context:
     def estimate_parameters(self, x, obs, obs_weight, distance_weight=1.0, pc2_xyz=None, max_lm_steps=0):
         """SimpleICPOptimization.estimate_parameters over the alive correspondences, from x; pc2_xyz: (Q,3) current
         coordinates of the matched movable points (None = as matched).  Returns IterResult."""
-        P = IterParams((C.c_double * 6)(*x), (C.c_double * 6)(*obs), (C.c_double * 6)(*obs_weight),
-                       0.0, -1.0 if distance_weight is None else distance_weight, int(max_lm_steps))
+        P = self._params(x, obs, obs_weight, 0.0, distance_weight, max_lm_steps)
         R = IterResult()
         p2 = None
         if pc2_xyz is not None:
@@ -1152,9 +1109,7 @@ class Context:
         """128-byte ncclUniqueId (rank 0 creates it, every rank passes the same bytes to comm_init)."""
         buf = C.create_string_buffer(128)
         L = load()
-        rc = L.sicp_comm_unique_id(buf)
-        if rc != OK:
-            raise BackendError(L.sicp_last_error().decode(), rc)
+        _chk(L, L.sicp_comm_unique_id(buf))
         return buf.raw
 
     def comm_init(self, unique_id, rank, world, gn_shard=False):

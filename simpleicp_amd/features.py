@@ -27,14 +27,7 @@ def fpfh_arguments(neighbors, radius, normal_neighbors, viewpoint):
     """(k, radius as a float -- inf: none --, normal_neighbors, viewpoint as three floats or None), checked: TypeError / ValueError."""
     k = _int_in("neighbors", neighbors, 2, _lib.FPFH_MAX_K)
     kn = _int_in("normal_neighbors", normal_neighbors, 2, 2**31 - 1)
-    if radius is None:
-        r = math.inf
-    else:
-        if isinstance(radius, (bool, str, bytes)) or not isinstance(radius, (int, float, np.integer, np.floating)):
-            raise TypeError(f"radius must be a number > 0 or None, not {radius!r}")
-        r = float(radius)
-        if math.isnan(r) or not r > 0.0:
-            raise ValueError(f"radius must be > 0 (None: no radius), not {radius!r}")
+    r = _radius_of("radius", radius)
     vp = None
     if viewpoint is not None:
         try:
@@ -53,9 +46,35 @@ def _check_counts(n, k, kn, estimating):
         raise ValueError(f"normal_neighbors ({kn}) exceeds the number of points ({n})")
 
 
-def _need_backend(ctx):
-    if not hasattr(ctx, "fpfh"):
-        raise _lib.BackendError("this backend has no FPFH descriptors")
+def _host_points(X):
+    """X of a host call as it is uploaded -- a PointCloud as it is, anything else as an (n, 3) float64 array -- and its number of
+    points."""
+    from .pointcloud import PointCloud
+    if isinstance(X, PointCloud):
+        return X, len(X)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError("X must be a PointCloud, an (n, 3) array or a CUDA tensor")
+    return X, X.shape[0]
+
+
+def _host_opening(who, instead, X, needs):
+    """The common opening of fpfh_features and keypoint_keep on the host road, after their own checks (the tensor road's is
+    tensors._keep_opening): the context, with X in the library's fixed slot.  needs: (entry point, what it is in words) the context
+    must have."""
+    if dist.is_distributed():
+        from .icp import SimpleICPException
+        raise SimpleICPException(f"{who} does not run in a torch.distributed job: {instead} with one process first")
+    ctx = backend.get_context()
+    if not hasattr(ctx, needs[0]):
+        raise _lib.BackendError(f"this backend has no {needs[1]}")
+    ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this call)
+    dist.detach(ctx)
+    if isinstance(X, np.ndarray):
+        ctx.upload(_lib.FIX, X)
+    else:
+        X._upload(ctx, _lib.FIX)
+    return ctx
 
 
 def fpfh_features(X, normals=None, *, neighbors=32, radius=None, normal_neighbors=10, viewpoint=None, return_counts=False):
@@ -76,16 +95,10 @@ def fpfh_features(X, normals=None, *, neighbors=32, radius=None, normal_neighbor
     k, r, kn, vp = fpfh_arguments(neighbors, radius, normal_neighbors, viewpoint)
     if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
         return _on_device(X, normals, k, r, kn, vp, bool(return_counts))
+    X, n = _host_points(X)
     own = None
-    if isinstance(X, PointCloud):
-        n = len(X)
-        if normals is None and all(c in X for c in ("nx", "ny", "nz")):
-            own = np.stack([np.asarray(X[c].to_numpy(), dtype=np.float32) for c in ("nx", "ny", "nz")], axis=1)
-    else:
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[1] != 3:
-            raise ValueError("X must be a PointCloud, an (n, 3) array or a CUDA tensor")
-        n = X.shape[0]
+    if isinstance(X, PointCloud) and normals is None and all(c in X for c in ("nx", "ny", "nz")):
+        own = np.stack([np.asarray(X[c].to_numpy(), dtype=np.float32) for c in ("nx", "ny", "nz")], axis=1)
     if normals is not None:
         own = np.ascontiguousarray(normals, dtype=np.float32)
         if own.shape != (n, 3):
@@ -94,17 +107,7 @@ def fpfh_features(X, normals=None, *, neighbors=32, radius=None, normal_neighbor
         out = np.empty((0, _lib.FPFH_BINS), np.float32)
         return (out, np.empty((0, _lib.FPFH_BINS + 1), np.uint16)) if return_counts else out
     _check_counts(n, k, kn, own is None)
-    if dist.is_distributed():
-        from .icp import SimpleICPException
-        raise SimpleICPException("fpfh_features does not run in a torch.distributed job: describe the clouds with one process first")
-    ctx = backend.get_context()
-    _need_backend(ctx)
-    ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this call)
-    dist.detach(ctx)
-    if isinstance(X, PointCloud):
-        X._upload(ctx, _lib.FIX)
-    else:
-        ctx.upload(_lib.FIX, X)
+    ctx = _host_opening("fpfh_features", "describe the clouds", X, ("fpfh", "FPFH descriptors"))
     if own is None:                   # (host callers hold no device allocator: the normals make the round trip, 12 bytes per point)
         own = ctx.estimate_normals(_lib.FIX, np.arange(n, dtype=np.int64), kn)[0]
     out, cnt, _ = ctx.fpfh(_lib.FIX, own, k, r, vp, want_counts=bool(return_counts))
@@ -113,7 +116,7 @@ def fpfh_features(X, normals=None, *, neighbors=32, radius=None, normal_neighbor
 
 def _on_device(X, normals, k, r, kn, vp, return_counts):
     import torch
-    from .tensors import _keep_opening
+    from .tensors import _keep_opening, _wait_for_torch
     if normals is not None and not isinstance(normals, (torch.Tensor, np.ndarray)):
         raise TypeError("normals must be a torch.Tensor or a numpy array of shape (n, 3)")
     if isinstance(X, torch.Tensor) and X.dim() == 2:
@@ -138,7 +141,7 @@ def _on_device(X, normals, k, r, kn, vp, return_counts):
     else:
         nv = torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32)).to(dev)
     # what torch queued for this call on its current stream (the index vector, the normals' copy) comes before the library reads it
-    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
+    _wait_for_torch(ctx, dev)
     if normals is None:
         ctx.estimate_normals_into(_lib.FIX, sel.data_ptr(), n, kn, nv.data_ptr(), pl.data_ptr())
     ctx.fpfh(_lib.FIX, nv, k, r, vp, fpfh_ptr=out.data_ptr(), counts_ptr=None if cnt is None else cnt.data_ptr())
@@ -184,8 +187,7 @@ def _check_keypoint_counts(n, a):
         raise ValueError(f"nms_neighbors ({a[2]}) exceeds the number of points ({n})")
 
 
-def _stats_dict(st):
-    return st.as_dict() if hasattr(st, "as_dict") else dict(st)
+_NO_KEYPOINTS = dict(n_points=0, n_salient=0, n_keypoints=0, n_small=0, n_clipped_salient=0, n_clipped_nms=0)
 
 
 def keypoint_keep(X, *, neighbors=32, salient_radius=None, nms_neighbors=None, nms_radius=None, gamma21=0.975, gamma32=0.975,
@@ -204,39 +206,20 @@ def keypoint_keep(X, *, neighbors=32, salient_radius=None, nms_neighbors=None, n
     ``return_saliency``: also the (n,) float64 saliency (0 where not salient), the (n, 3) float64 eigenvalues and the call's
     record as a dict (n_points, n_salient, n_keypoints, n_small, n_clipped_salient, n_clipped_nms -- the clipped counts say how
     many balls held more points than k).  The library's fixed slot holds X afterwards."""
-    from .pointcloud import PointCloud
     from .tensors import _is_device_tensor
     a = keypoint_arguments(neighbors, salient_radius, nms_neighbors, nms_radius, gamma21, gamma32, min_neighbors)
     if not isinstance(return_saliency, (bool, np.bool_)):
         raise TypeError(f"return_saliency must be True or False, not {return_saliency!r}")
     if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
         return _keypoints_on_device(X, a, bool(return_saliency))
-    if isinstance(X, PointCloud):
-        n = len(X)
-    else:
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[1] != 3:
-            raise ValueError("X must be a PointCloud, an (n, 3) array or a CUDA tensor")
-        n = X.shape[0]
+    X, n = _host_points(X)
     if n == 0:
         keep = np.zeros(0, bool)
-        none = dict(n_points=0, n_salient=0, n_keypoints=0, n_small=0, n_clipped_salient=0, n_clipped_nms=0)
-        return (keep, np.empty(0), np.empty((0, 3)), none) if return_saliency else keep
+        return (keep, np.empty(0), np.empty((0, 3)), dict(_NO_KEYPOINTS)) if return_saliency else keep
     _check_keypoint_counts(n, a)
-    if dist.is_distributed():
-        from .icp import SimpleICPException
-        raise SimpleICPException("keypoint_keep does not run in a torch.distributed job: choose the keypoints with one process first")
-    ctx = backend.get_context()
-    if not hasattr(ctx, "keypoints"):
-        raise _lib.BackendError("this backend has no ISS keypoints")
-    ctx._corr_owner = None            # (an operator-level CorrPts object loses the device state to this call)
-    dist.detach(ctx)
-    if isinstance(X, PointCloud):
-        X._upload(ctx, _lib.FIX)
-    else:
-        ctx.upload(_lib.FIX, X)
+    ctx = _host_opening("keypoint_keep", "choose the keypoints", X, ("keypoints", "ISS keypoints"))
     keep, sal, eig, st = ctx.keypoints(_lib.FIX, *a, want_saliency=bool(return_saliency))
-    return (keep, sal, eig, _stats_dict(st)) if return_saliency else keep
+    return (keep, sal, eig, _lib._stats_dict(st)) if return_saliency else keep
 
 
 def _keypoints_on_device(X, a, return_saliency):
@@ -248,9 +231,8 @@ def _keypoints_on_device(X, a, return_saliency):
     sal = torch.empty(n, dtype=torch.float64, device=X.device) if return_saliency else None
     eig = torch.empty((n, 3), dtype=torch.float64, device=X.device) if return_saliency else None
     if ctx is None:
-        none = dict(n_points=0, n_salient=0, n_keypoints=0, n_small=0, n_clipped_salient=0, n_clipped_nms=0)
-        return (keep, sal, eig, none) if return_saliency else keep
+        return (keep, sal, eig, dict(_NO_KEYPOINTS)) if return_saliency else keep
     st = ctx.keypoints(_lib.FIX, *a, keep_ptr=keep.data_ptr(), saliency_ptr=None if sal is None else sal.data_ptr(),
                        eig_ptr=None if eig is None else eig.data_ptr())
     keep = keep.view(torch.bool)
-    return (keep, sal, eig, _stats_dict(st)) if return_saliency else keep
+    return (keep, sal, eig, _lib._stats_dict(st)) if return_saliency else keep

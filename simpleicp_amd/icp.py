@@ -186,10 +186,6 @@ def _movable_rows(pc2):
     return msel, (len(msel) if partial else pc2.num_points)
 
 
-def _stats_dict(st):
-    return st.as_dict() if hasattr(st, "as_dict") else dict(st)
-
-
 def _set_normal_angle(ctx, cos_max, neighbors, pc2=None, msel=None, n_search=0):
     """The context's normal-angle setting for the run about to start -- set on every run, off (cos_max None) included, so that a
     pooled context never inherits it --, with pc2's own nx, ny, nz columns when it has them (of the selected subset when pc2 is
@@ -325,7 +321,7 @@ def _prepare(selection, kw, extras, H, info=None):
         # is then always an inlier); the neighbours are searched among ALL points of the fixed cloud
         if selection.is_empty():
             raise SimpleICPException("The fixed point cloud has no selected points left for the outlier removal.")
-        stats = _stats_dict(selection.outliers(*extras.outlier))
+        stats = _lib._stats_dict(selection.outliers(*extras.outlier))
         info(f"Remove statistical outliers ... kept {stats['n_kept']} of {stats['n_candidates']} points "
              f"(mean {stats['mean']:.5f}, std {stats['std']:.5f}, threshold {stats['threshold']:.5f})")
     if extras.voxel is not None:

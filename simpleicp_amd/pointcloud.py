@@ -302,7 +302,7 @@ class PointCloud(pd.DataFrame):
             return
         self._upload(ctx, _lib.FIX)
         keep, _, st = ctx.outlier_statistical(_lib.FIX, int(neighbors), ratio, rows=None if len(cur) == self._num_points else cur)
-        self.last_outlier_stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
+        self.last_outlier_stats = _lib._stats_dict(st)
         self._set_idx_selected(cur[keep])
 
     def select_keypoints(self, neighbors: int = 32, salient_radius=None, nms_neighbors=None, nms_radius=None, gamma21: float = 0.975,
@@ -311,7 +311,7 @@ class PointCloud(pd.DataFrame):
         section 22; the keywords are ``keypoint_keep``'s): support and suppression are always among ALL points of the cloud, so a
         selected point may lose to one that is not selected.  The record of the call is left in ``last_keypoint_stats``.  Not in
         the reference; composes with select_in_range, select_voxels and select_n_points."""
-        from .features import _check_keypoint_counts, _stats_dict, keypoint_arguments
+        from .features import _check_keypoint_counts, keypoint_arguments
         try:
             a = keypoint_arguments(neighbors, salient_radius, nms_neighbors, nms_radius, gamma21, gamma32, min_neighbors)
         except (TypeError, ValueError) as e:
@@ -326,7 +326,7 @@ class PointCloud(pd.DataFrame):
         ctx = _ctx or backend.get_context()
         self._upload(ctx, _lib.FIX)
         keep, _, _, st = ctx.keypoints(_lib.FIX, *a)
-        self.last_keypoint_stats = _stats_dict(st)
+        self.last_keypoint_stats = _lib._stats_dict(st)
         self._set_idx_selected(cur[np.asarray(keep)[cur]])
 
     def select_radius_inliers(self, radius: float, min_points: int, _ctx=None) -> None:

@@ -21,12 +21,14 @@ matches through it before either estimator sees them.
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib, backend, dist
+from ._lib import _stats_dict
 from .features import _int_in, fpfh_features, keypoint_arguments, keypoint_keep
-from .tensors import _is_device_tensor
+from .tensors import _is_device_tensor, _wait_for_torch
 
 
 class GlobalResult:
@@ -58,10 +60,11 @@ def _refuse_distributed(who):
         raise SimpleICPException(f"{who} does not run in a torch.distributed job: register the clouds with one process first")
 
 
-def _context(entry):
+def _context(entry, what="global registration"):
+    """The library's context, detached from any job, for a call of its `entry`: what the entry is in words, for a backend without."""
     ctx = backend.get_context()
     if not hasattr(ctx, entry):
-        raise _lib.BackendError("this backend has no global registration")
+        raise _lib.BackendError(f"this backend has no {what}")
     dist.detach(ctx)
     return ctx
 
@@ -81,12 +84,6 @@ def _check_tensor(name, t, width):
         raise ValueError(f"{name} is on {t.device}, the library's context on cuda:{device}")
     if t.dim() != 2 or (width is not None and t.shape[1] != width):
         raise ValueError(f"{name} must have shape (n, {'dim' if width is None else width}), not {tuple(t.shape)}")
-
-
-def _wait_for_torch(ctx, dev):
-    """The stream rule of run_tensors: the library's stream waits for torch's current stream before it reads anything."""
-    import torch
-    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
 
 
 # ---- matching ----
@@ -178,11 +175,16 @@ def _number(name, v):
     return float(v)
 
 
+def _positive(name, v):
+    d = _number(name, v)
+    if not math.isfinite(d) or not d > 0.0:
+        raise ValueError(f"{name} must be finite and > 0, not {v!r}")
+    return d
+
+
 def ransac_arguments(max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1):
     """(max_distance, hypotheses, edge_ratio, seed, triples as (h, 3) int32 or None, top), checked: TypeError / ValueError."""
-    d = _number("max_distance", max_distance)
-    if not math.isfinite(d) or not d > 0.0:
-        raise ValueError(f"max_distance must be finite and > 0, not {max_distance!r}")
+    d = _positive("max_distance", max_distance)
     h = _int_in("hypotheses", hypotheses, 1, 2**31 - 1)
     r = _number("edge_ratio", edge_ratio)
     if not 0.0 <= r <= 1.0:
@@ -207,6 +209,18 @@ def _as_H(pose):
     H[:3, :3] = np.asarray(pose[:9], dtype=np.float64).reshape(3, 3)
     H[:3, 3] = pose[9:12]
     return H
+
+
+def _packed_poses(H):
+    """H -- one 4x4 pose or a stack (b, 4, 4), an array or a tensor -- as the (b, 12) float64 rows the entry points take (R
+    row-major, then t), and whether it was one pose."""
+    if _is_torch(H):
+        H = H.detach().cpu().numpy()
+    H = np.asarray(H, dtype=np.float64)
+    if H.shape[-2:] != (4, 4) or H.ndim not in (2, 3) or H.shape[0] < 1:
+        raise ValueError(f"H must have shape (4, 4) or (b, 4, 4), b >= 1, not {H.shape}")
+    stack = H.reshape(-1, 4, 4)
+    return np.ascontiguousarray(np.concatenate([stack[:, :3, :3].reshape(-1, 9), stack[:, :3, 3]], axis=1)), H.ndim == 2
 
 
 def _best(inliers, top):
@@ -249,9 +263,24 @@ def _on_device_f64(ctx, src, dst):
     return S, D
 
 
-def _refit(ctx, on_device, S, D, m, poses, max_distance, rounds):
+# matched rows where an operator reads them: the context, whether they are device tensors, both sets as float64, their number
+_Rows = namedtuple("_Rows", "ctx on_device S D m")
+
+
+def _open_rows(who, src, dst, entry, what, checked=_matched_rows):
+    """The opening of an operator over matched rows: the rows checked, the job refused, the context that has `entry` (`what`: the
+    entry in words), and on the tensor road the float64 tensors with the library's stream behind torch's."""
+    on_device, src, dst, m = checked(src, dst)
+    _refuse_distributed(who)
+    ctx = _context(entry, what)
+    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
+    return _Rows(ctx, on_device, S, D, m)
+
+
+def _refit(rows, poses, max_distance, rounds):
     """sicp_pose_refit on rows that are where they are: (poses (b, 12), inliers (b,) int32, the record as a dict).  The poses
     (None: the plain fit) and the results are a few hundred bytes of host memory on either road."""
+    ctx, on_device, S, D, m = rows
     if not on_device:
         out, inl, st = ctx.pose_refit(S, D, poses, max_distance, rounds)
     else:
@@ -259,7 +288,7 @@ def _refit(ctx, on_device, S, D, m, poses, max_distance, rounds):
         out, inl = np.empty((b, 12), np.float64), np.empty(b, np.int32)
         st = ctx.pose_refit(S.data_ptr(), D.data_ptr(), None if poses is None else poses.ctypes.data, max_distance, rounds, m=m, b=b,
                             poses_ptr=out.ctypes.data, inliers_ptr=inl.ctypes.data)
-    return out, inl, st.as_dict() if hasattr(st, "as_dict") else dict(st)
+    return out, inl, _stats_dict(st)
 
 
 def _ransac_pose(src, dst, max_distance, hypotheses=4096, edge_ratio=0.9, seed=0, triples=None, top=1, refine=0):
@@ -288,11 +317,11 @@ def _ransac_pose(src, dst, max_distance, hypotheses=4096, edge_ratio=0.9, seed=0
         allp, inl, st = ctx.ransac_triplets(src, dst, tri, d, r)
         rows = _best(inl, top)
         poses = allp[rows]
-    stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
+    stats = _stats_dict(st)
     counts, refined = inl[rows], None
     if refine and len(rows):
         # the `top` candidates refitted on their own inliers (contract (L)) while the rows are where they are, then ranked again
-        poses, counts, refined = _refit(ctx, on_device, S, D, m, np.ascontiguousarray(poses, dtype=np.float64), d, refine)
+        poses, counts, refined = _refit(_Rows(ctx, on_device, S, D, m), np.ascontiguousarray(poses, dtype=np.float64), d, refine)
         again = np.lexsort((rows, -counts.astype(np.int64)))
         poses, counts, rows = poses[again], counts[again], rows[again]
     return GlobalResult([(_as_H(p), int(n), int(k)) for p, n, k in zip(poses, counts, rows)], stats, refined=refined)
@@ -318,14 +347,6 @@ def _refit_distance(max_distance):
     return d
 
 
-def _refit_context():
-    ctx = backend.get_context()
-    if not hasattr(ctx, "pose_refit"):
-        raise _lib.BackendError("this backend has no pose refit")
-    dist.detach(ctx)
-    return ctx
-
-
 def fit_pose(src, dst):
     """The rigid pose that brings ``src[c]`` closest to ``dst[c]`` in the least-squares sense over all rows whose six coordinates
     are finite (Kabsch / Horn; contract (L)): centroids and centred cross sums by the fixed pair tree, the
@@ -333,11 +354,7 @@ def fit_pose(src, dst):
 
     ``src``, ``dst``: (m, 3) matched points, m >= 3, both numpy arrays or both CUDA torch tensors; float32 is widened exactly.
     Returns the 4x4 float64 ``H``; None when fewer than three rows are finite or the fit is not."""
-    on_device, src, dst, m = _matched_rows(src, dst)
-    _refuse_distributed("fit_pose")
-    ctx = _refit_context()
-    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
-    poses, inl, _ = _refit(ctx, on_device, S, D, m, None, math.inf, 1)
+    poses, inl, _ = _refit(_open_rows("fit_pose", src, dst, "pose_refit", "pose refit"), None, math.inf, 1)
     return _as_H(poses[0]) if inl[0] >= 0 else None
 
 
@@ -352,28 +369,16 @@ def refine_pose(src, dst, H, *, max_distance, rounds=3):
     with -1."""
     d = _refit_distance(max_distance)
     r = _int_in("rounds", rounds, 1, _lib.POSEFIT_MAX_ROUNDS)
-    if _is_torch(H):
-        H = H.detach().cpu().numpy()
-    H = np.asarray(H, dtype=np.float64)
-    if H.shape[-2:] != (4, 4) or H.ndim not in (2, 3) or H.shape[0] < 1:
-        raise ValueError(f"H must have shape (4, 4) or (b, 4, 4), b >= 1, not {H.shape}")
-    on_device, src, dst, m = _matched_rows(src, dst)
-    _refuse_distributed("refine_pose")
-    stack = H.reshape(-1, 4, 4)
-    poses = np.ascontiguousarray(np.concatenate([stack[:, :3, :3].reshape(-1, 9), stack[:, :3, 3]], axis=1))
-    ctx = _refit_context()
-    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
-    out, inl, _ = _refit(ctx, on_device, S, D, m, poses, d, r)
+    poses, single = _packed_poses(H)
+    out, inl, _ = _refit(_open_rows("refine_pose", src, dst, "pose_refit", "pose refit"), poses, d, r)
     Hs = np.stack([_as_H(p) if n >= 0 else np.zeros((4, 4)) for p, n in zip(out, inl)])
-    return (Hs[0], int(inl[0])) if H.ndim == 2 else (Hs, inl.astype(np.int64))
+    return (Hs[0], int(inl[0])) if single else (Hs, inl.astype(np.int64))
 
 
 # ---- robust poses (contract (G)) ----
 def robust_arguments(max_distance, rounds=64, divisor=1.4, start_scale=None):
     """(max_distance, rounds, divisor, start_scale: 0.0 for None), checked: TypeError / ValueError."""
-    d = _number("max_distance", max_distance)
-    if not math.isfinite(d) or not d > 0.0:
-        raise ValueError(f"max_distance must be finite and > 0, not {max_distance!r}")
+    d = _positive("max_distance", max_distance)
     r = _int_in("rounds", rounds, 1, _lib.ROBUST_MAX_ROUNDS)
     q = _number("divisor", divisor)
     if not math.isfinite(q) or not q > 1.0:
@@ -386,16 +391,9 @@ def robust_arguments(max_distance, rounds=64, divisor=1.4, start_scale=None):
     return d, r, q, s
 
 
-def _robust_context():
-    ctx = backend.get_context()
-    if not hasattr(ctx, "pose_robust"):
-        raise _lib.BackendError("this backend has no robust pose fit")
-    dist.detach(ctx)
-    return ctx
-
-
-def _robust(ctx, on_device, S, D, m, poses, d, r, q, s):
+def _robust(rows, poses, d, r, q, s):
     """sicp_pose_robust on rows that are where they are: (poses (b, 12), inliers (b,) int32, scales (b,), the record as a dict)."""
+    ctx, on_device, S, D, m = rows
     if not on_device:
         out, inl, scales, st = ctx.pose_robust(S, D, poses, d, r, q, s)
     else:
@@ -403,7 +401,7 @@ def _robust(ctx, on_device, S, D, m, poses, d, r, q, s):
         out, inl, scales = np.empty((b, 12), np.float64), np.empty(b, np.int32), np.empty(b, np.float64)
         st = ctx.pose_robust(S.data_ptr(), D.data_ptr(), None if poses is None else poses.ctypes.data, d, r, q, s, m=m, b=b,
                              poses_ptr=out.ctypes.data, inliers_ptr=inl.ctypes.data, scales_ptr=scales.ctypes.data)
-    return out, inl, scales, st.as_dict() if hasattr(st, "as_dict") else dict(st)
+    return out, inl, scales, _stats_dict(st)
 
 
 def robust_pose(src, dst, *, max_distance, H=None, rounds=64, divisor=1.4, start_scale=None):
@@ -421,19 +419,8 @@ def robust_pose(src, dst, *, max_distance, H=None, rounds=64, divisor=1.4, start
     d, r, q, s = robust_arguments(max_distance, rounds, divisor, start_scale)
     poses, single = None, True
     if H is not None:
-        if _is_torch(H):
-            H = H.detach().cpu().numpy()
-        H = np.asarray(H, dtype=np.float64)
-        if H.shape[-2:] != (4, 4) or H.ndim not in (2, 3) or H.shape[0] < 1:
-            raise ValueError(f"H must have shape (4, 4) or (b, 4, 4), b >= 1, not {H.shape}")
-        single = H.ndim == 2
-        stack = H.reshape(-1, 4, 4)
-        poses = np.ascontiguousarray(np.concatenate([stack[:, :3, :3].reshape(-1, 9), stack[:, :3, 3]], axis=1))
-    on_device, src, dst, m = _matched_rows(src, dst)
-    _refuse_distributed("robust_pose")
-    ctx = _robust_context()
-    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
-    out, inl, _, _ = _robust(ctx, on_device, S, D, m, poses, d, r, q, s)
+        poses, single = _packed_poses(H)
+    out, inl, _, _ = _robust(_open_rows("robust_pose", src, dst, "pose_robust", "robust pose fit"), poses, d, r, q, s)
     Hs = np.stack([_as_H(p) if n >= 0 else np.zeros((4, 4)) for p, n in zip(out, inl)])
     return (Hs[0], int(inl[0])) if single else (Hs, inl.astype(np.int64))
 
@@ -454,9 +441,7 @@ class ConsistencyResult:
 
 def consistency_arguments(tolerance, min_length=0.0):
     """(tolerance, min_length), checked: TypeError / ValueError."""
-    t = _number("tolerance", tolerance)
-    if not math.isfinite(t) or not t > 0.0:
-        raise ValueError(f"tolerance must be finite and > 0, not {tolerance!r}")
+    t = _positive("tolerance", tolerance)
     l = _number("min_length", min_length)
     if not math.isfinite(l) or l < 0.0:
         raise ValueError(f"min_length must be finite and >= 0, not {min_length!r}")
@@ -472,16 +457,9 @@ def _consistency_rows(src, dst):
     return on_device, src, dst, m
 
 
-def _consistency_context():
-    ctx = backend.get_context()
-    if not hasattr(ctx, "match_consistency"):
-        raise _lib.BackendError("this backend has no match consistency")
-    dist.detach(ctx)
-    return ctx
-
-
-def _consistency(ctx, on_device, S, D, m, t, l):
+def _consistency(rows, t, l):
     """sicp_match_consistency on rows that are where they are: the ConsistencyResult (tensors on the tensor road)."""
+    ctx, on_device, S, D, m = rows
     if not on_device:
         degree, core, st = ctx.match_consistency(S, D, t, l)
     else:
@@ -489,7 +467,7 @@ def _consistency(ctx, on_device, S, D, m, t, l):
         degree = torch.empty(m, dtype=torch.int32, device=S.device)
         core = torch.empty(m, dtype=torch.int32, device=S.device)
         st = ctx.match_consistency(S.data_ptr(), D.data_ptr(), t, l, m=m, degree_ptr=degree.data_ptr(), core_ptr=core.data_ptr())
-    stats = st.as_dict() if hasattr(st, "as_dict") else dict(st)
+    stats = _stats_dict(st)
     keep = core == stats["max_core"] if stats["max_core"] >= 1 else core < 0       # (no core number is negative: all False)
     return ConsistencyResult(keep, core, degree, stats)
 
@@ -505,11 +483,7 @@ def consistent_matches(src, dst, *, tolerance, min_length=0.0):
     CUDA torch tensors; float32 is widened exactly.  Returns a ``ConsistencyResult``; a pose estimator then takes
     ``src[res.keep]``, ``dst[res.keep]``."""
     t, l = consistency_arguments(tolerance, min_length)
-    on_device, src, dst, m = _consistency_rows(src, dst)
-    _refuse_distributed("consistent_matches")
-    ctx = _consistency_context()
-    S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
-    return _consistency(ctx, on_device, S, D, m, t, l)
+    return _consistency(_open_rows("consistent_matches", src, dst, "match_consistency", "match consistency", _consistency_rows), t, l)
 
 
 def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighbors=10, viewpoint_fixed=None, viewpoint_movable=None,
@@ -601,19 +575,15 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     src, dst, n_consistent = movable[keep], fixed[idx[keep]], None
     if prune is not None:
         # the matched rows through sicp_match_consistency while they are where they are: the estimator sees the maximal core
-        on_device, src, dst, m = _consistency_rows(src, dst)
-        ctx = _consistency_context()
-        src, dst = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
-        kept = _consistency(ctx, on_device, src, dst, m, *prune).keep
-        src, dst, n_consistent = src[kept], dst[kept], int(kept.sum())
+        rows = _open_rows("register_global", src, dst, "match_consistency", "match consistency", _consistency_rows)
+        kept = _consistency(rows, *prune).keep
+        src, dst, n_consistent = rows.S[kept], rows.D[kept], int(kept.sum())
         if n_consistent < 3:
             return GlobalResult([], none, n_matches, n_consistent=n_consistent, n_keypoints=n_keypoints)
     if robust:
         # the matched rows through sicp_pose_robust from the identity while they are where they are
-        on_device, src, dst, m = _matched_rows(src, dst)
-        ctx = _robust_context()
-        S, D = _on_device_f64(ctx, src, dst) if on_device else (src, dst)
-        poses, inl, _, stats = _robust(ctx, on_device, S, D, m, None, *fit)
+        rows = _open_rows("register_global", src, dst, "pose_robust", "robust pose fit")
+        poses, inl, _, stats = _robust(rows, None, *fit)
         return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches, n_consistent=n_consistent,
                             n_keypoints=n_keypoints)
     res = _ransac_pose(src, dst, max_distance, refine=refine, **ransac_kwargs)

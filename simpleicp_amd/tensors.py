@@ -52,6 +52,12 @@ def _check_cloud(name, t, device):
         raise ValueError(f"{name} is on {t.device}, the library's context on cuda:{device}")
 
 
+def _wait_for_torch(ctx, dev):
+    """The stream rule: the library's stream waits for torch's current stream before it reads anything."""
+    import torch
+    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
+
+
 def _upload(ctx, slot, t):
     dt = _lib.DT_F64 if t.element_size() == 8 else _lib.DT_F32
     ctx.upload_strided(slot, t.data_ptr(), dt, t.shape[0], t.stride(0), t.stride(1))
@@ -64,8 +70,7 @@ def prepare(ctx, X_fix, X_mov, kw, extras, info):
     import torch
     pose = _start_pose(kw)
     dev = X_fix.device
-    # the stream rule: the library's stream waits for torch's current stream before it reads anything
-    torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev).wait_stream(torch.cuda.current_stream(dev))
+    _wait_for_torch(ctx, dev)
 
     def alloc(shape, kind):
         b = torch.empty(shape, dtype=getattr(torch, _KINDS[kind]), device=dev)
@@ -155,7 +160,7 @@ def _keep_opening(who, X, mask, needs=None):
     # the library's stream is made to wait for that stream: the library never reads a buffer torch is still writing
     m8 = None if mask is None else mask.contiguous().view(torch.uint8)
     keep = torch.empty(n, dtype=torch.uint8, device=X.device)
-    torch.cuda.ExternalStream(ctx.stream_ptr(), device=X.device).wait_stream(torch.cuda.current_stream(X.device))
+    _wait_for_torch(ctx, X.device)
     _upload(ctx, _lib.FIX, X)
     return ctx, n, m8, keep
 
