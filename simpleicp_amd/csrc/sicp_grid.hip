@@ -430,6 +430,7 @@ __global__ __launch_bounds__(256, SICP_NN16_OCC) void k_grid_nn16(
     for (int pass = 0; pass < 4096 && __any(!done); ++pass) {
         int lo[3], hi[3];
         const double c3[3] = {cxq, cyq, czq};
+        // ball_block's text (sicp_grid_dev.h), written out: with the call the compiler's schedule cost the steady match 0.7-1.3 % (profiles/ballwalk)
         bool all = true;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(256, SICP_NN16_OCC) void k_grid_nn16(
                 if (work) { for (int u = 0; u < 2; ++u) n_cand += ok[u] ? 1 : 0; }
             }
         };
-        // the ball, not its bounding cube (see k_grid_nn); once a hit bounds the answer the ball is the hit's, not the pass's
+        // the ball, not its bounding cube (the ball walk, sicp_grid_dev.h); once a hit bounds the answer the ball is the hit's, not the pass's
         const double r2 = r * r, etol = 1e-6 * G.h;
         double cull2 = __builtin_inf();
         const float inv_ny = 1.0f / (float)ny;
@@ -481,26 +482,10 @@ __global__ __launch_bounds__(256, SICP_NN16_OCC) void k_grid_nn16(
             int xl = lo[0], xh = hi[0];
             lb2 = 0.0;
             if (!all) {
-                const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
-                const double dy = fmax(fmax(yl - etol - cyq, cyq - (yl + G.h + etol)), 0.0);
-                const double dz = fmax(fmax(zl - etol - czq, czq - (zl + G.h + etol)), 0.0);
-                lb2 = fma(dy, dy, dz * dz);
-                const double rem = fmin(r2, cull2) - lb2;
-                if (rem >= 0.0) {
-                    const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
-                    const double fl = floor((cxq - hw - G.mn[0]) * G.inv_h - 1e-6);
-                    const double fh = floor((cxq + hw - G.mn[0]) * G.inv_h + 1e-6);
-                    const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
-                    const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
-                    xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
-                } else {
-                    xh = xl - 1;
-                }
+                lb2 = row_lb2(G, cy, cz, cyq, czq, etol);
+                row_x_clip(G, cxq, fmin(r2, cull2) - lb2, etol, xl, xh);
             }
-            if (xh >= xl) {
-                b = cell_start[row + xl];
-                len = cell_start[row + xh + 1] - b;
-            }
+            row_records(cell_start, row, xl, xh, b, len);
         };
         for (long rb = 0; __any(rb < nrows); rb += GS) {
             uint32_t b = 0, len = 0;
@@ -512,10 +497,7 @@ __global__ __launch_bounds__(256, SICP_NN16_OCC) void k_grid_nn16(
             if (__any(many)) {
                 // groups with many rows: nearest row first, then drop the rows its hit rules out and shrink the others'
                 // x ranges to the hit's ball (one more look at the cell offsets, a fraction of the candidates)
-                unsigned long long key = len > 0 ? (unsigned long long)__double_as_longlong(lb2) : ~0ull, mk = key;
-                { unsigned long long o;
-                  if constexpr (GS == 16) { o = lane_xor64<8>(mk);  mk = o < mk ? o : mk; }  o = lane_xor64<4>(mk);  mk = o < mk ? o : mk;
-                  o = lane_xor64<2>(mk);  mk = o < mk ? o : mk;  o = lane_xor64<1>(mk);  mk = o < mk ? o : mk; }
+                const unsigned long long key = len > 0 ? (unsigned long long)__double_as_longlong(lb2) : ~0ull, mk = gmin<GS>(key);
                 const unsigned geq = (unsigned)(__ballot(len > 0 && key == mk) >> gbase) & GMASK;
                 const int j = (many && geq) ? __ffs((int)geq) - 1 : 0;
                 const uint32_t vb = (uint32_t)__shfl((int)b, gbase + j), vl = (uint32_t)__shfl((int)len, gbase + j);
@@ -523,10 +505,7 @@ __global__ __launch_bounds__(256, SICP_NN16_OCC) void k_grid_nn16(
                 const uint32_t rlv[2] = {many ? vl : 0u, 0u};
                 if (many) todo &= ~(1u << j);
                 scan_rows(rbv, rlv);
-                double gb = best;
-                { double o;
-                  if constexpr (GS == 16) { o = lane_xor_f64<8>(gb);  gb = o < gb ? o : gb; }  o = lane_xor_f64<4>(gb);  gb = o < gb ? o : gb;
-                  o = lane_xor_f64<2>(gb);  gb = o < gb ? o : gb;  o = lane_xor_f64<1>(gb);  gb = o < gb ? o : gb; }
+                const double gb = gmin<GS>(best);
                 if (many && gb < __builtin_inf()) {
                     const double rbnd = sqrt(gb) * (1.0 + 1e-12) + slack;
                     const double c2 = rbnd * rbnd;
@@ -552,15 +531,7 @@ __global__ __launch_bounds__(256, SICP_NN16_OCC) void k_grid_nn16(
         }
         // lexicographic (d2, original index) minimum over the group's 16 lanes (one DPP row)
         const double lbest = best; const uint32_t lidx = bidx;
-#define SICP_LEXMIN_STEP(J)                                                                       \
-        {                                                                                         \
-            const double od = lane_xor_f64<J>(best);                                              \
-            const uint32_t oi = lane_xor32<J>(bidx);                                              \
-            if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; }                 \
-        }
-        if constexpr (GS == 16) SICP_LEXMIN_STEP(8)
-        SICP_LEXMIN_STEP(4) SICP_LEXMIN_STEP(2) SICP_LEXMIN_STEP(1)
-#undef SICP_LEXMIN_STEP
+        lexmin<GS>(best, bidx);
         if (!done) {
             const bool found = bidx != 0xffffffffu;
             const bool winner = found && lbest == best && lidx == bidx;
@@ -627,6 +598,7 @@ __global__ __launch_bounds__(256) void k_grid_knn(
     bool final_pass = false;
     for (int pass = 0; pass < 80; ++pass) {
         int lo[3], hi[3];
+        // ball_block's text (sicp_grid_dev.h), written out: with the call the compiler's schedule cost this kernel 1 % (profiles/ballwalk)
         bool all = true;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -667,14 +639,7 @@ __global__ __launch_bounds__(256) void k_grid_knn(
                     if (above && (d2 < best || (d2 == best && oi < bidx))) { best = d2; bidx = oi; }
                 }
             }
-#define SICP_LEXMIN_STEP(J)                                                                       \
-            {                                                                                     \
-                const double od = lane_xor_f64<J>(best);                                          \
-                const uint32_t oi = lane_xor32<J>(bidx);                                          \
-                if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; }             \
-            }
-            SICP_LEXMIN_STEP(32) SICP_LEXMIN_STEP(16) SICP_LEXMIN_STEP(8) SICP_LEXMIN_STEP(4) SICP_LEXMIN_STEP(2) SICP_LEXMIN_STEP(1)
-#undef SICP_LEXMIN_STEP
+            lexmin<64>(best, bidx);
             const bool ok = bidx != 0xffffffffu;
             if (final_pass || all) {
                 if (lane == 0) {
@@ -800,15 +765,7 @@ __global__ __launch_bounds__(256, 4) void k_grid_knn_sweep(
         int kk = 0;                                   // neighbours found (k, or every point of the cloud if it holds fewer)
         for (int pass = 0; pass < 4096; ++pass) {
             int lo[3], hi[3];
-            bool all = true;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double fl = floor((c3[a] - r - G.mn[a]) * G.inv_h - 1e-6);
-                const double fh = floor((c3[a] + r - G.mn[a]) * G.inv_h + 1e-6);
-                lo[a] = fl < 0.0 ? 0 : (fl > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fl);
-                hi[a] = fh < 0.0 ? 0 : (fh > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fh);
-                all = all && (fl <= 0.0) && (fh >= (double)(G.dim[a] - 1));
-            }
+            const bool all = ball_block(G, c3, r, lo, hi);
             const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
             const long nrows = (long)ny * nz;
             // a candidate at d2 <= thr lies inside the ball with room for every rounding: no point of a culled cell ties or beats it
@@ -831,26 +788,8 @@ __global__ __launch_bounds__(256, 4) void k_grid_knn_sweep(
                     const int cy = lo[1] + oy, cz = lo[2] + oz;
                     const long row = ((long)cz * G.dim[1] + cy) * G.dim[0];
                     int xl = lo[0], xh = hi[0];
-                    if (!all) {
-                        const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
-                        const double dy = fmax(fmax(yl - etol - ay, ay - (yl + G.h + etol)), 0.0);
-                        const double dz = fmax(fmax(zl - etol - az, az - (zl + G.h + etol)), 0.0);
-                        const double rem = r2 - fma(dy, dy, dz * dz);
-                        if (rem >= 0.0) {
-                            const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
-                            const double fl = floor((ax - hw - G.mn[0]) * G.inv_h - 1e-6);
-                            const double fh = floor((ax + hw - G.mn[0]) * G.inv_h + 1e-6);
-                            const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
-                            const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
-                            xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
-                        } else {
-                            xh = xl - 1;
-                        }
-                    }
-                    if (xh >= xl) {
-                        rbeg = cell_start[row + xl];
-                        rlen = cell_start[row + xh + 1] - rbeg;
-                    }
+                    if (!all) row_x_clip(G, ax, r2 - row_lb2(G, cy, cz, ay, az, etol), etol, xl, xh);
+                    row_records(cell_start, row, xl, xh, rbeg, rlen);
                 }
                 unsigned long long todo = __ballot(rlen > 0);
                 while (todo) {
@@ -968,14 +907,7 @@ __global__ __launch_bounds__(256, 4) void k_grid_knn_sweep(
                             if (above && (d2 < best || (d2 == best && oi < bidx))) { best = d2; bidx = oi; bpos = i; }
                         }
                     }
-#define SICP_LEXMIN_STEP(J)                                                                       \
-                    {                                                                             \
-                        const double od = lane_xor_f64<J>(best);                                  \
-                        const uint32_t oi = lane_xor32<J>(bidx), op = lane_xor32<J>(bpos);        \
-                        if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; bpos = op; } \
-                    }
-                    SICP_LEXMIN_STEP(32) SICP_LEXMIN_STEP(16) SICP_LEXMIN_STEP(8) SICP_LEXMIN_STEP(4) SICP_LEXMIN_STEP(2) SICP_LEXMIN_STEP(1)
-#undef SICP_LEXMIN_STEP
+                    lexmin<64>(best, bidx, bpos);
                     if (bidx == 0xffffffffu) break;         // the cloud holds fewer than k points
                     const double4 W = rec[bpos];
                     if (lane == 0) {

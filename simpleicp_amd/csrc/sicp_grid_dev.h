@@ -1,5 +1,14 @@
-// sicp_grid_dev.h -- device helpers shared by the grid kernels (sicp_grid.hip: the exact searches, the k-NN sweeps; sicp_gridf.hip: the
-// filtered many-queries search, the cells' tight boxes) and the device-cloud kernels (sicp_device.hip).  Device code only.
+// sicp_grid_dev.h -- device code every kernel that reads the dense cell table shares (device code only):
+//   * where a point falls (cell_coord, cell_of);
+//   * the BALL WALK's geometry -- ball_block, row_lb2, row_x_clip, row_records: which cells a ball touches, row by row, with the
+//     margins that make every search exact.  The rows' three functions are the one text of it: k_grid_nn / _wait / _batch
+//     (sicp_grid_nn_one.inc), k_grid_nn16, k_grid_knn_sweep, k_grid_knn_sweep4 / _list (sicp_grid.hip, sicp_knn_sweep4.inc),
+//     k_grid_nn16f (sicp_gridf.hip) and k_ball_count (sicp_outlier.hip) call them.  ball_block is called by the two sweeps; the
+//     one-wave search, k_grid_nn16, k_grid_knn, k_grid_nn16f and k_ball_count keep its text written out, each with the register or
+//     the time the call cost it (profiles/ballwalk/README.md): a change to the block's margins is made HERE and in those five.
+//     row_split turns a row number into (y, z);
+//   * the cells' tight boxes (box_lb2, box_trim_row);
+//   * the transform contract (xf), the match epilogue (post_match), wmin_d, okey.
 #ifndef SICP_GRID_DEV_H
 #define SICP_GRID_DEV_H
 
@@ -60,6 +69,74 @@ __device__ __forceinline__ void row_split(long rr, int ny, float inv_ny, bool sm
         oy = r; oz = (int)q;
     } else {
         oy = (int)(rr % ny); oz = (int)(rr / ny);
+    }
+}
+
+// ---- the ball walk: the cells a ball of radius r around a query touches -----------------------------------------------------------
+// A search pass walks the BALL, not its bounding cube: (1) the block of cells [lo, hi] the cube covers; (2) per (cy, cz) row of the
+// block -- rows are contiguous in the cell order -- the squared distance lb2 from the query to the row's (y, z) rectangle: the row is
+// needed only if that is within r; (3) then only the cells within sqrt(r^2 - lb2) of the query along x; (4) whose records are ONE
+// range of the table.  What each caller keeps is what differs: which radius bounds the row (the pass's, a hit's, both), how lanes
+// take rows, what it does with the records.
+// The margins: every floor() leans outwards by 1e-6 of a cell and every rectangle grows by etol = 1e-6 h, the tolerance every cell
+// test of the grid carries -- a point was binned by floor((v - mn) * inv_h) from the same mn and inv_h, so its cell and the cell
+// computed here for a coordinate at most r away differ by rounding of a few ulps of the quotient, orders of magnitude inside 1e-6;
+// the half-width along x is rounded UP (float sqrt times 1.000001f: the float's 6e-8 relative error and the conversion of rem, with
+// room; the cell tolerance covers the rest), and a remainder of zero or a few ulps (a row exactly r away) still gets a positive one.
+// So a cell that holds a point within r of the query -- up to the caller's own slack on r -- is never left out; cells too many only
+// cost candidates, which are judged by their exact distances.
+
+// (1) The block: cells lo[a] .. hi[a] per axis, clamped to the grid.  True (`all`): the cube covers the whole grid -- whole axis
+// covered <=> the ball reaches past both faces of the cloud's box -- and the pass ends the search whatever it finds; callers then
+// take every row in full.
+__device__ __forceinline__ bool ball_block(const GridGeom &G, const double (&c)[3], double r, int (&lo)[3], int (&hi)[3])
+{
+    bool all = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double fl = floor((c[a] - r - G.mn[a]) * G.inv_h - 1e-6);
+        const double fh = floor((c[a] + r - G.mn[a]) * G.inv_h + 1e-6);
+        lo[a] = fl < 0.0 ? 0 : (fl > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fl);
+        hi[a] = fh < 0.0 ? 0 : (fh > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fh);
+        all = all && (fl <= 0.0) && (fh >= (double)(G.dim[a] - 1));
+    }
+    return all;
+}
+
+// (2) Squared distance from (qy, qz) to the (y, z) rectangle of row (cy, cz), faces moved outwards by etol: a lower bound of the
+// squared distance to every point of the row.
+__device__ __forceinline__ double row_lb2(const GridGeom &G, int cy, int cz, double qy, double qz, double etol)
+{
+    const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
+    const double dy = fmax(fmax(yl - etol - qy, qy - (yl + G.h + etol)), 0.0);
+    const double dz = fmax(fmax(zl - etol - qz, qz - (zl + G.h + etol)), 0.0);
+    return fma(dy, dy, dz * dz);
+}
+
+// (3) rem = (the squared radius that bounds the row) - lb2.  rem >= 0: [xl, xh] narrows to the cells within sqrt(rem) of qx;
+// otherwise the row is outside the ball: xh = xl - 1.
+__device__ __forceinline__ void row_x_clip(const GridGeom &G, double qx, double rem, double etol, int &xl, int &xh)
+{
+    if (rem >= 0.0) {
+        // half-width along x, rounded up (float sqrt + margin; the cell tolerance covers the rest)
+        const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
+        const double fl = floor((qx - hw - G.mn[0]) * G.inv_h - 1e-6);
+        const double fh = floor((qx + hw - G.mn[0]) * G.inv_h + 1e-6);
+        const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
+        const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
+        xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
+    } else {
+        xh = xl - 1;                                          // outside the ball
+    }
+}
+
+// (4) The records of the cells [xl, xh] of the row that starts at cell `row` (= (cz * dim1 + cy) * dim0): [b, b + len), left as
+// they are when the range of cells is empty.
+__device__ __forceinline__ void row_records(const uint32_t *__restrict__ cell_start, long row, int xl, int xh, uint32_t &b, uint32_t &len)
+{
+    if (xh >= xl) {
+        b = cell_start[row + xl];
+        len = cell_start[row + xh + 1] - b;
     }
 }
 

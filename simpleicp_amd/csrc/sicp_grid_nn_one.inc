@@ -100,6 +100,8 @@
         const double4 *__restrict__ rcp = cp ? rec2 : rec;
         int lo[3], hi[3];
         const double c3[3] = {cxq, cyq, czq};
+        // ball_block's text (sicp_grid_dev.h), written out: the compiler's allocation -- the call costs the EXT kernels two VGPRs,
+        // k_grid_nn<true, *, true> its third wave (profiles/ballwalk/README.md)
         bool all = true;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -155,27 +157,10 @@
             xl = lo[0]; xh = hi[0];
             lb2 = 0.0;
             if (!all) {
-                const double yl = Gp.mn[1] + (double)cy * Gp.h, zl = Gp.mn[2] + (double)cz * Gp.h;
-                const double dy = fmax(fmax(yl - etol - cyq, cyq - (yl + Gp.h + etol)), 0.0);
-                const double dz = fmax(fmax(zl - etol - czq, czq - (zl + Gp.h + etol)), 0.0);
-                lb2 = fma(dy, dy, dz * dz);
-                const double rem = fmin(r2, cull2) - lb2;
-                if (rem >= 0.0) {
-                    // half-width along x, rounded up (float sqrt + margin; the cell tolerance covers the rest)
-                    const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
-                    const double fl = floor((cxq - hw - Gp.mn[0]) * Gp.inv_h - 1e-6);
-                    const double fh = floor((cxq + hw - Gp.mn[0]) * Gp.inv_h + 1e-6);
-                    const int tl = fl < 0.0 ? 0 : (fl > (double)(Gp.dim[0] - 1) ? Gp.dim[0] - 1 : (int)fl);
-                    const int th = fh < 0.0 ? 0 : (fh > (double)(Gp.dim[0] - 1) ? Gp.dim[0] - 1 : (int)fh);
-                    xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
-                } else {
-                    xh = xl - 1;                                  // outside the ball
-                }
+                lb2 = row_lb2(Gp, cy, cz, cyq, czq, etol);
+                row_x_clip(Gp, cxq, fmin(r2, cull2) - lb2, etol, xl, xh);
             }
-            if (xh >= xl && lb2 <= cull2) {
-                b = csp[row + xl];
-                len = csp[row + xh + 1] - b;
-            }
+            if (lb2 <= cull2) row_records(csp, row, xl, xh, b, len);
         };
         for (long rb = 0; rb < nrows; rb += 64) {
             uint32_t b = 0, len = 0;
@@ -190,21 +175,13 @@
             if (work && len > 0) n_rows += 1;                     // (per-lane tallies, summed once at the end)
             if (__popcll((long long)todo) > 4) {
                 // many rows (a wide ball: cold start, far query): nearest row first, then drop the rows its hit rules out
-                unsigned long long key = len > 0 ? (unsigned long long)__double_as_longlong(lb2) : ~0ull, mk = key;
-                { unsigned long long o;
-                  o = lane_xor64<32>(mk); mk = o < mk ? o : mk;  o = lane_xor64<16>(mk); mk = o < mk ? o : mk;
-                  o = lane_xor64<8>(mk);  mk = o < mk ? o : mk;  o = lane_xor64<4>(mk);  mk = o < mk ? o : mk;
-                  o = lane_xor64<2>(mk);  mk = o < mk ? o : mk;  o = lane_xor64<1>(mk);  mk = o < mk ? o : mk; }
+                const unsigned long long key = len > 0 ? (unsigned long long)__double_as_longlong(lb2) : ~0ull, mk = gmin<64>(key);
                 const int j = __ffsll((long long)__ballot(len > 0 && key == mk)) - 1;
                 const uint32_t rbv[4] = {(uint32_t)__builtin_amdgcn_readlane((int)b, j), 0u, 0u, 0u};
                 const uint32_t rlv[4] = {(uint32_t)__builtin_amdgcn_readlane((int)len, j), 0u, 0u, 0u};
                 todo &= ~(1ull << j);
                 scan_rows(rbv, rlv);
-                double wb = best;
-                { double o;
-                  o = lane_xor_f64<32>(wb); wb = o < wb ? o : wb;  o = lane_xor_f64<16>(wb); wb = o < wb ? o : wb;
-                  o = lane_xor_f64<8>(wb);  wb = o < wb ? o : wb;  o = lane_xor_f64<4>(wb);  wb = o < wb ? o : wb;
-                  o = lane_xor_f64<2>(wb);  wb = o < wb ? o : wb;  o = lane_xor_f64<1>(wb);  wb = o < wb ? o : wb; }
+                const double wb = gmin<64>(best);
                 if (wb < __builtin_inf()) {
                     const double rbnd = sqrt(wb) * (1.0 + 1e-12) + slack;
                     const double c2 = rbnd * rbnd;
@@ -238,14 +215,7 @@
         // wave-wide lexicographic (d2, original index) minimum: DPP butterfly, every lane ends up with it;
         // the lane that found it keeps the coordinates
         const double lbest = best; const uint32_t lidx = bidx;
-#define SICP_LEXMIN_STEP(J)                                                                       \
-        {                                                                                         \
-            const double od = lane_xor_f64<J>(best);                                              \
-            const uint32_t oi = lane_xor32<J>(bidx);                                              \
-            if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; }                 \
-        }
-        SICP_LEXMIN_STEP(32) SICP_LEXMIN_STEP(16) SICP_LEXMIN_STEP(8) SICP_LEXMIN_STEP(4) SICP_LEXMIN_STEP(2) SICP_LEXMIN_STEP(1)
-#undef SICP_LEXMIN_STEP
+        lexmin<64>(best, bidx);
         const bool found = bidx != 0xffffffffu;
         const bool winner = found && lbest == best && lidx == bidx;         // exactly one lane (indices are unique)
         // sqrt(best) + margin <= r, tested on the squares (no sqrt, no division).  The relative margin is HALF the one a

@@ -237,6 +237,7 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
     unsigned n_cand = 0, n_rows = 0;
     for (int pass = 0; pass < 4096 && __any(!done); ++pass) {
         int lo[3], hi[3];
+        // ball_block's text (sicp_grid_dev.h), written out: with the call the compiler's schedule cost the steady match 0.3-1.3 % (profiles/ballwalk)
         bool all = true;
         {
             const double c3[3] = {cxq, cyq, czq};
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
                 if (work) { for (int u = 0; u < 4; ++u) n_cand += ok[u] ? 1u : 0u; }
             }
         };
-        // the ball, not its bounding cube (see k_grid_nn); once a hit bounds the answer the ball is the hit's, not the pass's
+        // the ball, not its bounding cube (the ball walk, sicp_grid_dev.h); once a hit bounds the answer the ball is the hit's, not the pass's
         const double r2 = r * r, etol = 1e-6 * G.h;
         double cull2 = __builtin_inf();
         const float inv_ny = 1.0f / (float)ny;
@@ -304,26 +305,10 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
             int xl = lo[0], xh = hi[0];
             lb2 = 0.0;
             if (!all) {
-                const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
-                const double dy = fmax(fmax(yl - etol - cyq, cyq - (yl + G.h + etol)), 0.0);
-                const double dz = fmax(fmax(zl - etol - czq, czq - (zl + G.h + etol)), 0.0);
-                lb2 = fma(dy, dy, dz * dz);
-                const double rem = (FAR ? fmin(r2, cull2) : r2) - lb2;
-                if (rem >= 0.0) {
-                    const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
-                    const double fl = floor((cxq - hw - G.mn[0]) * G.inv_h - 1e-6);
-                    const double fh = floor((cxq + hw - G.mn[0]) * G.inv_h + 1e-6);
-                    const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
-                    const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
-                    xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
-                } else {
-                    xh = xl - 1;
-                }
+                lb2 = row_lb2(G, cy, cz, cyq, czq, etol);
+                row_x_clip(G, cxq, (FAR ? fmin(r2, cull2) : r2) - lb2, etol, xl, xh);
             }
-            if (xh >= xl) {
-                b = cell_start[row + xl];
-                len = cell_start[row + xh + 1] - b;
-            }
+            row_records(cell_start, row, xl, xh, b, len);
         };
         bool far_query = false;                  // (FAR = false) this query needs the other flavour
         // a ball of thousands of rows (a query far from everything, on a grid binned for a dense core): the exact kernel's business --
@@ -380,10 +365,7 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
                     // others' x ranges to the hit's ball
                     const unsigned long long k0 = len[0] > 0 ? (unsigned long long)__double_as_longlong(lb2[0]) : ~0ull;
                     const unsigned long long k1 = len[1] > 0 ? (unsigned long long)__double_as_longlong(lb2[1]) : ~0ull;
-                    unsigned long long mk = k0 < k1 ? k0 : k1;
-                    { unsigned long long o;
-                      if constexpr (GS == 16) { o = lane_xor64<8>(mk);  mk = o < mk ? o : mk; }  o = lane_xor64<4>(mk);  mk = o < mk ? o : mk;
-                      o = lane_xor64<2>(mk);  mk = o < mk ? o : mk;  o = lane_xor64<1>(mk);  mk = o < mk ? o : mk; }
+                    const unsigned long long mk = gmin<GS>(k0 < k1 ? k0 : k1);
                     const unsigned geq = ((unsigned)(__ballot(len[0] > 0 && k0 == mk) >> gbase) & GMASK) |
                                          (((unsigned)(__ballot(len[1] > 0 && k1 == mk) >> gbase) & GMASK) << GS);
                     const int j = (many && geq) ? __ffs((int)geq) - 1 : 0;
@@ -393,12 +375,7 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
                     const uint32_t rlv[2] = {many ? vl : 0u, 0u};
                     if (many) todo &= ~(1u << j);
                     scan_rows(rbv, rlv);
-                    float gb = v1;
-                    { float o;
-                      if constexpr (GS == 16) { o = __uint_as_float(lane_xor32<8>(__float_as_uint(gb)));  gb = o < gb ? o : gb; }
-                      o = __uint_as_float(lane_xor32<4>(__float_as_uint(gb)));  gb = o < gb ? o : gb;
-                      o = __uint_as_float(lane_xor32<2>(__float_as_uint(gb)));  gb = o < gb ? o : gb;
-                      o = __uint_as_float(lane_xor32<1>(__float_as_uint(gb)));  gb = o < gb ? o : gb; }
+                    const float gb = gmin<GS>(v1);
                     if (many && gb < __builtin_inff()) {
                         // gb + T bounds the own-frame squared distance of a cloud point from above, with room for the difference
                         // between the frames on both sides (T = 2 E): nothing beyond it can beat or tie the answer
@@ -428,12 +405,7 @@ __global__ __launch_bounds__(256, FAR ? SICP_NN16F_FAR_OCC : SICP_NN16F_OCC) voi
             }
         }
         // ---- the group's smallest value, and is it alone within T? ----
-        float gmin = v1;
-        { float o;
-          if constexpr (GS == 16) { o = __uint_as_float(lane_xor32<8>(__float_as_uint(gmin)));  gmin = o < gmin ? o : gmin; }
-          o = __uint_as_float(lane_xor32<4>(__float_as_uint(gmin)));  gmin = o < gmin ? o : gmin;
-          o = __uint_as_float(lane_xor32<2>(__float_as_uint(gmin)));  gmin = o < gmin ? o : gmin;
-          o = __uint_as_float(lane_xor32<1>(__float_as_uint(gmin)));  gmin = o < gmin ? o : gmin; }
+        const float gmin = sicp::gmin<GS>(v1);
         const bool found = gmin < __builtin_inff();
         // (rounded UP: the float32 addition may lose up to 6e-8 (gmin + T) -- near the cloud's centre that is a tenth of T -- and a
         // candidate that is within the margin must count as within it: ADVICE r5)

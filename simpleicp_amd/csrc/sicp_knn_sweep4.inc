@@ -31,15 +31,7 @@
         double r = (double)(1.35f * sqrtf((float)dk_est)) + slack;
         if (!(r >= 0.25 * r_first)) r = 0.25 * r_first;
         int lo[3], hi[3];
-        bool all = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double fl = floor((c3[a] - r - G.mn[a]) * G.inv_h - 1e-6);
-            const double fh = floor((c3[a] + r - G.mn[a]) * G.inv_h + 1e-6);
-            lo[a] = fl < 0.0 ? 0 : (fl > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fl);
-            hi[a] = fh < 0.0 ? 0 : (fh > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fh);
-            all = all && (fl <= 0.0) && (fh >= (double)(G.dim[a] - 1));
-        }
+        const bool all = ball_block(G, c3, r, lo, hi);
         const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
         const long nrows = (long)ny * nz;
         bool mine = active && !all && nrows <= 16;                 // this group does the query itself (so far)
@@ -54,24 +46,8 @@
             const int cy = lo[1] + oy, cz = lo[2] + oz;
             const long row = ((long)cz * G.dim[1] + cy) * G.dim[0];
             int xl = lo[0], xh = hi[0];
-            const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
-            const double dy = fmax(fmax(yl - etol - ay, ay - (yl + G.h + etol)), 0.0);
-            const double dz = fmax(fmax(zl - etol - az, az - (zl + G.h + etol)), 0.0);
-            const double rem = r2 - fma(dy, dy, dz * dz);
-            if (rem >= 0.0) {
-                const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
-                const double fl = floor((ax - hw - G.mn[0]) * G.inv_h - 1e-6);
-                const double fh = floor((ax + hw - G.mn[0]) * G.inv_h + 1e-6);
-                const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
-                const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
-                xl = tl > xl ? tl : xl; xh = th < xh ? th : xh;
-            } else {
-                xh = xl - 1;
-            }
-            if (xh >= xl) {
-                rbeg = cell_start[row + xl];
-                rlen = cell_start[row + xh + 1] - rbeg;
-            }
+            row_x_clip(G, ax, r2 - row_lb2(G, cy, cz, ay, az, etol), etol, xl, xh);
+            row_records(cell_start, row, xl, xh, rbeg, rlen);
         }
         // ---- sweep: the group's non-empty rows one after the other, 16 records at a time; survivors compacted into its LDS ----
         unsigned todo = (unsigned)(__ballot(rlen > 0) >> gbase) & 0xffffu;

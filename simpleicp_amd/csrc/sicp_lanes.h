@@ -1,4 +1,6 @@
-// sicp_lanes.h -- register-speed cross-lane moves for wave64 on gfx950 (device code only).
+// sicp_lanes.h -- register-speed cross-lane moves for wave64 on gfx950, and what every kernel builds from them (device code only):
+// lane_xor* (the exchange), the sums and the prefix sum of a wave, the minima of a wave or of a sub-wave group of lanes (gmin, and
+// lexmin: the lexicographic (d2, index) minimum every search ends with), block_sum_u32, and the grid barrier.
 //
 // __shfl* compiles to ds_bpermute (the LDS crossbar): ~250 cycles per step in a dependent chain.  A fixed
 // lane ^ J exchange needs no crossbar: DPP quad_perm for J = 1, 2; J = 4 = row_half_mirror (i^7) then quad
@@ -9,6 +11,7 @@
 #define SICP_LANES_H
 
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace sicp {
 
@@ -43,6 +46,48 @@ template <int J>
 __device__ __forceinline__ double lane_xor_f64(double v)
 {
     return __longlong_as_double((long long)lane_xor64<J>((unsigned long long)__double_as_longlong(v)));
+}
+
+// the same exchange by the value's type: what gmin is written over
+template <int J> __device__ __forceinline__ unsigned long long lane_xor(unsigned long long v) { return lane_xor64<J>(v); }
+template <int J> __device__ __forceinline__ double lane_xor(double v) { return lane_xor_f64<J>(v); }
+template <int J> __device__ __forceinline__ float lane_xor(float v) { return __uint_as_float(lane_xor32<J>(__float_as_uint(v))); }
+
+// Minimum of v over the SPAN lanes lane ^ (SPAN - 1 .. 0): SPAN = 64 is the wave, 16 and 8 are the groups that share a wave in the
+// many-queries kernels (a group is within one DPP row).  Butterfly, widest step first; every lane of the span ends up with the
+// minimum.  A plain comparison, not fmin: the callers' values are never NaN, and wmin_d (sicp_grid_dev.h) is the fmin form.
+template <int J, class T>
+__device__ __forceinline__ T gmin_step(T v) { const T o = lane_xor<J>(v); return o < v ? o : v; }
+template <int SPAN, class T>
+__device__ __forceinline__ T gmin(T v)
+{
+    static_assert(SPAN == 64 || SPAN == 16 || SPAN == 8, "the wave, or a group of 16 or 8 lanes");
+    if constexpr (SPAN == 64) { v = gmin_step<32>(v); v = gmin_step<16>(v); }
+    if constexpr (SPAN >= 16) v = gmin_step<8>(v);
+    v = gmin_step<4>(v); v = gmin_step<2>(v); v = gmin_step<1>(v);
+    return v;
+}
+
+// Lexicographic (d2, original index) minimum over the SPAN lanes, the order every search breaks its ties in: every lane ends up with
+// the smallest pair; the lane that held it finds its own pair unchanged (indices are unique: exactly one lane).  `with`: 32-bit
+// words that travel with the pair (the winner's record position).
+template <int J, class... U>
+__device__ __forceinline__ void lexmin_step(double &d, uint32_t &i, U &...with)
+{
+    const double od = lane_xor_f64<J>(d);
+    const uint32_t oi = lane_xor32<J>(i);
+    const bool take = od < d || (od == d && oi < i);
+    auto carry = [&](uint32_t &w) { const uint32_t ow = lane_xor32<J>(w); if (take) w = ow; };     // (every lane takes part in the exchange)
+    (carry(with), ...);
+    if (take) { d = od; i = oi; }
+}
+template <int SPAN, class... U>
+__device__ __forceinline__ void lexmin(double &d, uint32_t &i, U &...with)
+{
+    static_assert(SPAN == 64 || SPAN == 16 || SPAN == 8, "the wave, or a group of 16 or 8 lanes");
+    if constexpr (SPAN == 64) { lexmin_step<32>(d, i, with...); lexmin_step<16>(d, i, with...); }
+    if constexpr (SPAN >= 16) lexmin_step<8>(d, i, with...);
+    lexmin_step<4>(d, i, with...); lexmin_step<2>(d, i, with...); lexmin_step<1>(d, i, with...);
 }
 
 // neither NaN nor an infinity

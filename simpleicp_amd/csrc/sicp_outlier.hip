@@ -119,8 +119,8 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ol_compact(const uint8_t *__restri
 
 // ---- the radius filter -----------------------------------------------------------------------------------------------------------
 // OL_GS lanes per candidate.  The ball's box of cells is walked row by row ((cy, cz) rows are contiguous in the cell order): the
-// lanes of a group fetch the record ranges of OL_GS rows at once, culled to the ball along x as k_grid_nn culls its own, then take
-// the records of one row after the other, two per lane and step.  A candidate leaves as soon as its count reaches cap.
+// lanes of a group fetch the record ranges of OL_GS rows at once, culled to the ball along x (row_lb2, row_x_clip: sicp_grid_dev.h),
+// then take the records of one row after the other, two per lane and step.  A candidate leaves as soon as its count reaches cap.
 // pos: where candidate q's results go (null: q); order: the candidates in cell order (the grid is a multiple of 8 blocks then).
 __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restrict__ qx, const double *__restrict__ qy,
                                                          const double *__restrict__ qz, const uint32_t *__restrict__ order,
@@ -149,6 +149,7 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restric
         const double rr = r + (1e-9 * r + 1e-15 * (fabs(ax) + fabs(ay) + fabs(az) + r));
         const double rr2 = rr * rr, etol = 1e-6 * G.h;
         int lo[3], hi[3];
+        // ball_block's text (sicp_grid_dev.h) without `all`, written out: measured with the three search kernels that keep theirs (profiles/ballwalk)
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const double fl = floor((c3[a] - rr - G.mn[a]) * G.inv_h - 1e-6);
@@ -166,21 +167,11 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restric
                 const int oz = rw / ny, oy = rw - oz * ny;
                 const int cy = lo[1] + oy, cz = lo[2] + oz;
                 const long row = ((long)cz * G.dim[1] + cy) * G.dim[0];
-                const double yl = G.mn[1] + (double)cy * G.h, zl = G.mn[2] + (double)cz * G.h;
-                const double dy = fmax(fmax(yl - etol - ay, ay - (yl + G.h + etol)), 0.0);
-                const double dz = fmax(fmax(zl - etol - az, az - (zl + G.h + etol)), 0.0);
-                const double rem = rr2 - fma(dy, dy, dz * dz);
-                if (rem >= 0.0) {
-                    const double hw = (rem < 1e-30 ? 1e-15 : (double)(sqrtf((float)rem) * 1.000001f)) + etol;
-                    const double fl = floor((ax - hw - G.mn[0]) * G.inv_h - 1e-6);
-                    const double fh = floor((ax + hw - G.mn[0]) * G.inv_h + 1e-6);
-                    const int tl = fl < 0.0 ? 0 : (fl > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fl);
-                    const int th = fh < 0.0 ? 0 : (fh > (double)(G.dim[0] - 1) ? G.dim[0] - 1 : (int)fh);
-                    const int xl = tl > lo[0] ? tl : lo[0], xh = th < hi[0] ? th : hi[0];
-                    if (xh >= xl) {
-                        b = cell_start[row + xl];
-                        len = cell_start[row + xh + 1] - b;
-                    }
+                const double rem = rr2 - row_lb2(G, cy, cz, ay, az, etol);
+                if (rem >= 0.0) {                              // (row_x_clip's own test, here too: the compiler's allocation, two VGPRs)
+                    int xl = lo[0], xh = hi[0];
+                    row_x_clip(G, ax, rem, etol, xl, xh);
+                    row_records(cell_start, row, xl, xh, b, len);
                 }
             }
             unsigned todo = (unsigned)(__ballot(len > 0) >> gbase) & ((1u << OL_GS) - 1u);
