@@ -36,6 +36,7 @@ def _small_H(rng, scale=1.0):
 
 class Model:
     """What the library should hold, and the checks of every operation against the oracle on it."""
+    SIZES = (6000, 20_000, 20_001)        # points of an uploaded cloud (tests/fuzz_operators.py takes smaller ones)
 
     def __init__(self, ctx, rng):
         from simpleicp_amd import _lib
@@ -51,7 +52,7 @@ class Model:
     # ---- operations ----
     def upload(self, slot):
         rng, L = self.rng, self.L
-        n = int(rng.choice([6000, 20_000, 20_001]))
+        n = int(rng.choice(self.SIZES))
         if slot == L.FIX or self.F is None:
             P = _surface(rng, n)
         else:
