@@ -1,6 +1,7 @@
 // sicp_icp.cpp -- the ICP iteration: setup, the device-chained loop, the host-side solver road, state and uncertainties, and the
 // operator-by-operator exports (CorrPts.*, estimate_parameters).  Split from sicp_api.cpp (round 5).
 #include "sicp_host.h"
+#include <map>
 
 namespace sicph {
 
@@ -854,11 +855,35 @@ int iterate_host_lm(sicp_ctx *c, const sicp_iter_params *P, sicp_iter_result *R)
 
 }  // namespace sicph
 
+// Kernels that WAIT on the device -- the one-launch rejection and minimisation meet at grid barriers sized by what the whole device
+// holds (resident_blocks), a match launched early polls the ticket of a tail that must still find a CU and a queue of its own
+// ("The tail -> match hand-over") -- are written for a device nobody else is on.  Contexts of one process on ONE device,
+// used from several threads, are somebody else to each other: the calls that may launch such a kernel take turns per device and
+// hold the turn until they return (they are synchronous).  tests/test_gpu_threads.py: without it a prelaunched run beside two
+// one-launch runs ended in "a device-wide barrier ... timed out".  A context with an exchange takes no turn: its calls wait for
+// their peers, and a peer that is a thread of this process on this device would wait for the turn in its turn -- ranks are one per
+// device, where there is nobody to take turns with.
+namespace {
+std::mutex &device_wait_mutex(int device)
+{
+    static std::mutex table_mu;
+    static std::map<int, std::mutex> table;               // (a map's nodes stay where they are)
+    std::lock_guard<std::mutex> g(table_mu);
+    return table[device];
+}
+std::unique_lock<std::mutex> device_wait_turn(const sicp_ctx *c)
+{
+    const bool waits = c->Q > REJECT_MAX_Q || (c->chain_prelaunch && c->stream2 != nullptr && c->Q <= PRELAUNCH_MAX_Q);
+    return waits && !c->collective() ? std::unique_lock<std::mutex>(device_wait_mutex(c->device)) : std::unique_lock<std::mutex>();
+}
+}  // namespace
+
 SICP_EXPORT int sicp_icp_iterate(sicp_ctx *c, const sicp_iter_params *P, sicp_iter_result *R)
 {
     if (!c || !P || !R) return fail(SICP_ERR_INVALID, "null argument");
     CHK(check_iter_args(c, P));
     HIPCHK(hipSetDevice(c->device));
+    const auto turn = device_wait_turn(c);
     if (!device_tail(c)) return iterate_host_lm(c, P, R);
     std::memset(R, 0, sizeof *R);
     int64_t done = 0;
@@ -873,6 +898,7 @@ SICP_EXPORT int sicp_icp_run(sicp_ctx *c, const sicp_iter_params *P0, int64_t ma
     if (max_iterations <= 0) return SICP_OK;
     CHK(check_iter_args(c, P0));
     HIPCHK(hipSetDevice(c->device));
+    const auto turn = device_wait_turn(c);
     if (device_tail(c)) {
         // (a failing iteration's entry carries the estimate it started from: the tail kernel records it)
         return run_device_tail(c, P0, max_iterations, run_min_change(min_change), results, iterations_out);
@@ -1030,6 +1056,7 @@ SICP_EXPORT int sicp_corr_reject_distances(sicp_ctx *c, double *median_out, doub
 {
     CHK(check_corr(c));
     HIPCHK(hipSetDevice(c->device));
+    const auto turn = device_wait_turn(c);
     const long Q = c->Q;
     // the selection kernels read the candidates' mask and write the survivors' into distinct buffers
     HIPCHK(hipMemcpyAsync(c->flag.p, c->keep.p, (size_t)Q, hipMemcpyDeviceToDevice, c->stream));
@@ -1060,6 +1087,7 @@ SICP_EXPORT int sicp_estimate_parameters(sicp_ctx *c, const sicp_iter_params *P,
     for (int j = 0; j < 6; ++j)
         if (std::isnan(P->obs_weight[j]) || P->obs_weight[j] < 0) return fail(SICP_ERR_INVALID, "obs_weight[%d] must be >= 0", j);
     HIPCHK(hipSetDevice(c->device));
+    const auto turn = device_wait_turn(c);
     const long Q = c->Q;
     std::memset(R, 0, sizeof *R);
     if (pc2_xyz) {
