@@ -103,6 +103,10 @@ KEYPOINTS_EXPORTS = ["sicp_keypoints_version", "sicp_keypoints"]
 KEYPOINTS_VERSION = 1
 KEYPOINTS_MAX_K = 128
 
+# include/simpleicp_hip_cluster.h: DBSCAN labels, the same kind of companion
+CLUSTER_EXPORTS = ["sicp_cluster_version", "sicp_cluster"]
+CLUSTER_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -174,6 +178,11 @@ class KeypointStats(_Stats):
     _fields_ = [(name, C.c_int64) for name in ("n_points", "n_salient", "n_keypoints", "n_small", "n_clipped_salient", "n_clipped_nms")]
 
 
+class ClusterStats(_Stats):
+    """struct sicp_cluster_stats (contract (U)): 56 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_core", "n_border", "n_noise", "n_clusters", "largest_label", "largest_size")]
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -242,6 +251,8 @@ FEATURES = {
         "sicp_match_consistency": [_vp, _vp, _vp, _i64, _dbl, _dbl, _vp, _vp, C.POINTER(ConsistencyStats)]}),
     "keypoints": _Feature(KEYPOINTS_EXPORTS, "simpleicp_hip_keypoints.h", "keypoint", KEYPOINTS_VERSION, {
         "sicp_keypoints": [_vp, _cint, _cint, _dbl, _cint, _dbl, _dbl, _dbl, _i64, _vp, _vp, _vp, C.POINTER(KeypointStats)]}),
+    "cluster": _Feature(CLUSTER_EXPORTS, "simpleicp_hip_cluster.h", "cluster", CLUSTER_VERSION, {
+        "sicp_cluster": [_vp, _cint, _dbl, _i64, _vp, _vp, C.POINTER(ClusterStats)]}),
 }
 
 _lib = None
@@ -413,6 +424,7 @@ posefit_version = partial(_feature_version, "posefit")
 robust_version = partial(_feature_version, "robust")
 consistency_version = partial(_feature_version, "consistency")
 keypoints_version = partial(_feature_version, "keypoints")
+cluster_version = partial(_feature_version, "cluster")
 
 
 def select_positions(m, Q):
@@ -811,6 +823,21 @@ class Context:
             eig = np.empty((n, 3), np.float64) if want_saliency else None
         self._chk(self._L.sicp_keypoints(self._h, slot, *args, _ptr(keep), _ptr(sal), _ptr(eig), C.byref(st)))
         return (keep[:n].view(np.bool_), sal, eig, st) if host else st
+
+    # -- DBSCAN labels (contract (U)) --
+    def cluster(self, slot, radius, min_points, labels_ptr=None, core_ptr=None):
+        """sicp_cluster: the DBSCAN labels of the slot -- a point with at least min_points points of the slot, itself included,
+        strictly within radius is core; clusters are the connected components of the core points, labelled 0, 1, ... in the order
+        of their lowest core index; a point that is not core takes the smallest label among its core neighbours; -1: noise.
+        Returns ((n,) int32 labels, (n,) bool core flags, ClusterStats); with labels_ptr (device memory, n int32) the labels are
+        left there, the core bytes at core_ptr if given (n bytes), and the ClusterStats alone is returned."""
+        cluster_version()
+        n = self.size(slot)
+        st = ClusterStats()
+        host = labels_ptr is None
+        labels, core = (np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.uint8)) if host else (labels_ptr, core_ptr)
+        self._chk(self._L.sicp_cluster(self._h, slot, float(radius), int(min_points), _ptr(labels), _ptr(core), C.byref(st)))
+        return (labels[:n], core[:n].view(np.bool_), st) if host else st
 
     # -- descriptor matching and RANSAC poses (contracts (M) and (R)) --
     def feature_match(self, query, target, nq=None, nt=None, dim=None, idx_ptr=None, d2_ptr=None, want_d2=True):

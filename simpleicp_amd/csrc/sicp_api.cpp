@@ -255,6 +255,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FSCAN")) c->fscan_variant = !std::strcmp(e, "inline") ? 1 : 0;
     if (const char *e = std::getenv("SICP_FSCAN_CAP")) c->fscan_cap = std::atol(e);
     if (const char *e = std::getenv("SICP_OUTLIER_CHUNK")) c->outlier_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_CLUSTER_CHUNK")) c->cluster_chunk = std::atol(e) > 0 ? std::atol(e) : (1L << 22);
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_KEYPOINT_CHUNK")) c->keypoint_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
@@ -310,6 +311,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->ol_d.release(); c->ol_part.release(); c->ol_cnt.release();
     c->fp_nrm.release(); c->fp_out.release(); c->fp_cnt.release();
     c->kp_sal.release(); c->kp_eig.release();
+    c->cl_parent.release(); c->cl_root.release(); c->cl_rank.release(); c->cl_size.release(); c->cl_labels.release();
     c->gl_key.release(); c->gl_q.release(); c->gl_t.release(); c->gl_d2.release(); c->gl_idx.release(); c->gl_tri.release();
     c->gl_src.release(); c->gl_dst.release(); c->gl_pose.release();
     c->pf_in.release(); c->pf_state.release(); c->pf_part.release(); c->pf_part2.release(); c->pf_cnt.release();

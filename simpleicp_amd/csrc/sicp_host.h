@@ -330,6 +330,12 @@ struct sicp_ctx {
     // their way out in cand_keep), the staging buffers of the eigenvalues
     DevBuf<double> kp_sal, kp_eig;
     long keypoint_chunk = 0;       // SICP_KEYPOINT_CHUNK: points per search of sicp_keypoints (0: chosen per call)
+    // DBSCAN labels (sicp_cluster.hip): the union-find's parent words, every point's root (0xffffffff: none), the roots' ranks
+    // followed by the scan's block sums, the clusters' sizes, the staged labels (the core bytes are staged in cand_keep, the capped
+    // counts land in ol_cnt)
+    DevBuf<uint32_t> cl_parent, cl_root, cl_rank, cl_size;
+    DevBuf<int32_t> cl_labels;
+    long cluster_chunk = 1L << 22; // SICP_CLUSTER_CHUNK: points per launch of sicp_cluster's ball walks
     // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
     // the call's arrays
     DevBuf<unsigned long long> gl_key;
@@ -404,6 +410,16 @@ inline GridSearch bound_search(GridSearch S, const Grid &sub, double *d2, int64_
     S.coarse = nullptr; S.cell_box = nullptr; S.idx_base = 0; S.d2 = d2; S.idx = idx; S.p2 = p2; S.work = nullptr; S.flags = NN_APPROX;
     return S;
 }
+namespace sicp {
+// the radius filter's ball walk for the units that count the same balls (sicp_outlier.hip): the grid level a ball of `radius` is
+// walked on -- the slot's own grid, built if there is none --, refused with the radius filter's message where the ball's box of
+// cells exceeds SICP_OUTLIER_MAX_BOX_CELLS; and k_ball_count enqueued over cnt candidates whose columns lie qpad apart at q
+// (keep = count >= cap, cnt_out = min(count, cap), *kept_total += the kept; null: not counted)
+int ball_level(sicp_ctx *c, int slot, double radius, GridLevel *lv);
+int ball_count_enqueue(sicp_ctx *c, const double *q, long qpad, const uint32_t *order, const int64_t *pos, const GridLevel &lv, long cnt,
+                       double radius, unsigned cap, uint8_t *keep, uint32_t *cnt_out, unsigned long long *kept_total);
+}  // namespace sicp
+
 namespace sicph {
 
 // The filtered many-queries search (sicp_gridf.hip) of S.Q queries, ties and all: see filtered_search (sicp_search.cpp).  What its two

@@ -49,6 +49,7 @@ __device__ __forceinline__ double lane_xor_f64(double v)
 }
 
 // the same exchange by the value's type: what gmin is written over
+template <int J> __device__ __forceinline__ unsigned lane_xor(unsigned v) { return lane_xor32<J>(v); }
 template <int J> __device__ __forceinline__ unsigned long long lane_xor(unsigned long long v) { return lane_xor64<J>(v); }
 template <int J> __device__ __forceinline__ double lane_xor(double v) { return lane_xor_f64<J>(v); }
 template <int J> __device__ __forceinline__ float lane_xor(float v) { return __uint_as_float(lane_xor32<J>(__float_as_uint(v))); }

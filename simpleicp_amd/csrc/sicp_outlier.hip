@@ -204,7 +204,7 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restric
         }
     }
     const unsigned long long kb = __ballot(active && sub == 0 && kept);
-    if (lane == 0 && kb) atomicAdd(kept_total, (unsigned long long)__popcll((long long)kb));
+    if (lane == 0 && kb && kept_total) atomicAdd(kept_total, (unsigned long long)__popcll((long long)kb));   // (null: the caller counts for itself)
     if (work) {
         n_cand = wsum_u64(n_cand); n_rows = wsum_u64(n_rows);
         if (lane == 0) { atomicAdd(work, n_cand); atomicAdd(work + 1, n_rows); }
@@ -270,6 +270,38 @@ int ol_level(sicp_ctx *c, int slot, double radius, GridLevel *lv, int64_t ext[3]
 }
 
 }  // namespace
+
+namespace sicp {
+
+// The radius filter's walk, for the units that count the same balls (sicp_cluster.hip; declared in sicp_host.h).
+// ball_level: the grid level a ball of `radius` is walked on, refused where its box of cells exceeds SICP_OUTLIER_MAX_BOX_CELLS.
+int ball_level(sicp_ctx *c, int slot, double radius, GridLevel *lv)
+{
+    int64_t ext[3]; long cells = 0;
+    CHK(ol_level(c, slot, radius, lv, ext, &cells));
+    if (cells > SICP_OUTLIER_MAX_BOX_CELLS)
+        return fail(SICP_ERR_INVALID, "radius %g spans a box of %lld x %lld x %lld = %lld grid cells (cell size %g): at most %d -- choose a "
+                    "smaller radius", radius, (long long)ext[0], (long long)ext[1], (long long)ext[2], (long long)cells, lv->g.h,
+                    SICP_OUTLIER_MAX_BOX_CELLS);
+    return SICP_OK;
+}
+
+// ball_count_enqueue: k_ball_count over the cnt candidates whose columns lie at q, q + qpad, q + 2 qpad (order: null, or the
+// candidates in cell order; pos: null, or where each candidate's results go): keep = count >= cap, cnt_out = min(count, cap),
+// *kept_total += the kept (one atomic per wave that kept any, all on that one word; null: not counted).
+int ball_count_enqueue(sicp_ctx *c, const double *q, long qpad, const uint32_t *order, const int64_t *pos, const GridLevel &lv, long cnt,
+                       double radius, unsigned cap, uint8_t *keep, uint32_t *cnt_out, unsigned long long *kept_total)
+{
+    unsigned g = cdiv(cnt, OL_BLOCK / OL_GS);
+    if (order) g = (g + 7u) & ~7u;
+    hipLaunchKernelGGL(k_ball_count, dim3(g), dim3(OL_BLOCK), 0, c->stream, q, q + qpad, q + 2 * qpad, order, pos, lv.cell_start,
+                       (const double4 *)lv.rec, cnt, lv.g, radius, radius * radius, cap, keep, cnt_out, kept_total,
+                       c->count_work ? c->match_work.p : nullptr);
+    HIPCHK(hipGetLastError());
+    return SICP_OK;
+}
+
+}  // namespace sicp
 
 SICP_EXPORT int sicp_outlier_version(void) { return SICP_OUTLIER_VERSION; }
 
@@ -358,12 +390,8 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
     if (min_points < 0) return fail(SICP_ERR_INVALID, "min_points must be >= 0");
     HIPCHK(hipSetDevice(c->device));
     return op_run(c, [&]() -> int {
-        GridLevel lv; int64_t ext[3]; long cells = 0;
-        CHK(ol_level(c, slot, radius, &lv, ext, &cells));
-        if (cells > SICP_OUTLIER_MAX_BOX_CELLS)
-            return fail(SICP_ERR_INVALID, "radius %g spans a box of %lld x %lld x %lld = %lld grid cells (cell size %g): at most %d -- choose a "
-                        "smaller radius", radius, (long long)ext[0], (long long)ext[1], (long long)ext[2], (long long)cells, lv.g.h,
-                        SICP_OUTLIER_MAX_BOX_CELLS);
+        GridLevel lv;
+        CHK(ball_level(c, slot, radius, &lv));
         Candidates K;
         CHK(take_candidates(c, slot, rows, m, mask, ol_compact_mask, &K));
         const long N = K.positions;
@@ -373,7 +401,6 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
             HIPCHK(hipMemsetAsync(c->cand_keep.p, 0, (size_t)N, c->stream));
             HIPCHK(hipMemsetAsync(c->ol_cnt.p, 0, (size_t)N * sizeof(uint32_t), c->stream));
         }
-        const double r2 = radius * radius;
         const unsigned cap = (unsigned)std::min<int64_t>(min_points, (1LL << 31) - 1) + 1u;      // counts stay below 2^31
         const long chunk = c->outlier_chunk > 0 ? c->outlier_chunk : (1L << 22);
         CHK(c->kq.reserve((size_t)3 * round_up(std::min(chunk, std::max<long>(K.count, 1)), QPAD)));
@@ -385,13 +412,9 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
                 CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, 2.0 * lv.g.h, 1L << 22, c->k_order));
                 order = c->k_order.p;
             }
-            unsigned g = cdiv(cnt, OL_BLOCK / OL_GS);
-            if (order) g = (g + 7u) & ~7u;
-            hipLaunchKernelGGL(k_ball_count, dim3(g), dim3(OL_BLOCK), 0, c->stream, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, order,
-                               K.by_position ? K.d_rows + lo : nullptr, lv.cell_start, (const double4 *)lv.rec, cnt, lv.g, radius, r2, cap,
-                               K.by_position ? c->cand_keep.p : c->cand_keep.p + lo, K.by_position ? c->ol_cnt.p : c->ol_cnt.p + lo,
-                               c->cand_small.p + OL_KEPT, c->count_work ? c->match_work.p : nullptr);
-            HIPCHK(hipGetLastError());
+            CHK(ball_count_enqueue(c, c->kq.p, qpad, order, K.by_position ? K.d_rows + lo : nullptr, lv, cnt, radius, cap,
+                                   K.by_position ? c->cand_keep.p : c->cand_keep.p + lo, K.by_position ? c->ol_cnt.p : c->ol_cnt.p + lo,
+                                   c->cand_small.p + OL_KEPT));
         }
         CHK(counters_fetch(c));
         CHK(ol_deliver(c, keep_out, c->cand_keep.p, (size_t)N));

@@ -1,5 +1,6 @@
 """FPFH descriptors: 33 floats per point, the local shape descriptor a global registration matches clouds by -- and ISS keypoints,
-the points worth describing (``keypoint_keep``; contract (I), DESIGN.md section 22, include/simpleicp_hip_keypoints.h).
+the points worth describing (``keypoint_keep``; contract (I), DESIGN.md section 22, include/simpleicp_hip_keypoints.h) -- and DBSCAN
+labels, the points that belong together (``cluster_labels``; contract (U), DESIGN.md section 23, include/simpleicp_hip_cluster.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -236,3 +237,64 @@ def _keypoints_on_device(X, a, return_saliency):
                        eig_ptr=None if eig is None else eig.data_ptr())
     keep = keep.view(torch.bool)
     return (keep, sal, eig, _lib._stats_dict(st)) if return_saliency else keep
+
+
+# ---- DBSCAN labels (contract (U)) ----
+
+_NO_CLUSTERS = dict(n_points=0, n_core=0, n_border=0, n_noise=0, n_clusters=0, largest_label=0, largest_size=0)
+
+
+def cluster_arguments(radius, min_points=10):
+    """(radius as a float, min_points as an int), checked: ValueError naming the keyword."""
+    try:
+        r = float(radius)
+        ok = not isinstance(radius, (bool, str, bytes)) and math.isfinite(r) and r > 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"radius must be a finite number > 0, not {radius!r}")
+    if isinstance(min_points, (bool, float, str, bytes)) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) < 2**63:
+        raise ValueError(f"min_points must be an integer >= 1, not {min_points!r}")
+    return r, int(min_points)
+
+
+def cluster_labels(X, radius, min_points=10, return_core=False, return_info=False):
+    """The DBSCAN labels of X as an int32 vector (n,) (contract (U)): a point with at least ``min_points``
+    points of X, itself included, strictly closer than ``radius`` is a core point; the clusters are the connected components of the
+    core points, labelled 0, 1, 2, ... in the order of their first core point; a point that is not core takes the smallest label
+    among its core neighbours' clusters; every other point is noise, -1.  Where no pair of points lies at exactly ``radius`` these
+    are ``sklearn.cluster.DBSCAN(eps=radius, min_samples=min_points).fit(X).labels_``.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any
+    strides; ingest and stream rule are run_tensors').  A tensor gives a torch.int32 tensor on its device, anything else numpy.
+    ``return_core``: also the (n,) bool core flags; ``return_info``: also the call's record as a dict (n_points, n_core, n_border,
+    n_noise, n_clusters, largest_label, largest_size -- of equal sizes the lowest label; no cluster: -1 and 0).  The results come
+    as (labels[, core][, info]).  The library's fixed slot holds X afterwards."""
+    from .tensors import _is_device_tensor
+    r, mp = cluster_arguments(radius, min_points)
+    for name, v in (("return_core", return_core), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, not {v!r}")
+
+    def answer(labels, core, info):
+        out = (labels,) + ((core,) if return_core else ()) + ((info,) if return_info else ())
+        return out if len(out) > 1 else labels
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        return answer(*_cluster_on_device(X, r, mp, bool(return_core)))
+    X, n = _host_points(X)
+    if n == 0:
+        return answer(np.zeros(0, np.int32), np.zeros(0, bool), dict(_NO_CLUSTERS))
+    ctx = _host_opening("cluster_labels", "cluster the clouds", X, ("cluster", "clustering"))
+    labels, core, st = ctx.cluster(_lib.FIX, r, mp)
+    return answer(labels, core, _lib._stats_dict(st))
+
+
+def _cluster_on_device(X, r, mp, return_core):
+    import torch
+    from .tensors import _keep_opening
+    ctx, n, _, core = _keep_opening("cluster_labels", X, None, needs=("cluster", "clustering"))
+    labels = torch.empty(n, dtype=torch.int32, device=X.device)
+    if ctx is None:
+        return labels, core, dict(_NO_CLUSTERS)
+    st = ctx.cluster(_lib.FIX, r, mp, labels_ptr=labels.data_ptr(), core_ptr=core.data_ptr() if return_core else None)
+    return labels, core.view(torch.bool), _lib._stats_dict(st)

@@ -57,6 +57,7 @@ def voxel_arguments(voxel_size, origin=None, exc=ValueError):
 class PointCloud(pd.DataFrame):
     last_outlier_stats = None             # select_statistical_inliers leaves its statistics here (a dict)
     last_keypoint_stats = None            # select_keypoints leaves its record here (a dict)
+    last_cluster_stats = None             # select_largest_cluster / select_clusters leave their record here (a dict)
 
     def __init__(self, *args, **kwargs) -> None:
         kwargs.pop("remapping", None)     # accepted and ignored, like the reference (pointcloud.py:25)
@@ -348,6 +349,47 @@ class PointCloud(pd.DataFrame):
         self._upload(ctx, _lib.FIX)
         keep, _, _ = ctx.outlier_radius(_lib.FIX, r, int(min_points), rows=None if len(cur) == self._num_points else cur)
         self._set_idx_selected(cur[keep])
+
+    def _cluster_selected(self, radius, min_points, ctx):
+        """(selected indices, their DBSCAN labels as a cloud of their own) -- (indices, None) when nothing is selected; the record
+        is left in ``last_cluster_stats``."""
+        from .features import cluster_arguments
+        try:
+            r, mp = cluster_arguments(radius, min_points)
+        except ValueError as e:
+            raise PointCloudException(str(e)) from None
+        cur = self.idx_selected
+        if len(cur) == 0:
+            return cur, None
+        ctx = ctx or backend.get_context()
+        self._upload(ctx, _lib.FIX, rows=None if len(cur) == self._num_points else cur)
+        labels, _, st = ctx.cluster(_lib.FIX, r, mp)
+        self.last_cluster_stats = _lib._stats_dict(st)
+        return cur, np.asarray(labels)
+
+    def select_largest_cluster(self, radius: float, min_points: int = 10, _ctx=None) -> None:
+        """Keeps, among the selected points, the largest DBSCAN cluster of the SELECTED points taken as a cloud of their own --
+        the selected rows are uploaded, the points that are not selected play no part -- and deselects the rest (contract (U),
+        DESIGN.md section 23; ``radius`` and ``min_points`` are ``cluster_labels``'s).  Of equally large clusters the one with the
+        lowest label stays; without any cluster nothing stays selected.  The record of the call is left in ``last_cluster_stats``.
+        Not in the reference; composes with select_in_range, select_voxels and select_n_points."""
+        cur, labels = self._cluster_selected(radius, min_points, _ctx)
+        if labels is None:
+            return
+        self._set_idx_selected(cur[labels == self.last_cluster_stats["largest_label"]] if self.last_cluster_stats["n_clusters"] else cur[:0])
+
+    def select_clusters(self, radius: float, min_points: int = 10, min_size: int = 1, _ctx=None) -> None:
+        """Keeps, among the selected points, those in a DBSCAN cluster (of the SELECTED points taken as a cloud of their own) with
+        at least ``min_size`` members, core and border, and deselects the rest -- noise always goes (contract (U), DESIGN.md section
+        23).  The record of the call is left in ``last_cluster_stats``.  Not in the reference; composes with select_in_range,
+        select_voxels and select_n_points."""
+        if isinstance(min_size, (bool, float, str, bytes)) or not isinstance(min_size, (int, np.integer)) or min_size < 1:
+            raise PointCloudException("min_size must be an integer >= 1.")
+        cur, labels = self._cluster_selected(radius, min_points, _ctx)
+        if labels is None:
+            return
+        sizes = np.bincount(labels[labels >= 0], minlength=1)
+        self._set_idx_selected(cur[(labels >= 0) & (sizes[np.maximum(labels, 0)] >= int(min_size))])
 
     def fpfh(self, neighbors: int = 32, radius=None) -> np.ndarray:
         """The (n, 33) float32 FPFH descriptors of ALL points (contract (F)): ``fpfh_features(self,
