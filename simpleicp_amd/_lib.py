@@ -107,6 +107,11 @@ KEYPOINTS_MAX_K = 128
 CLUSTER_EXPORTS = ["sicp_cluster_version", "sicp_cluster"]
 CLUSTER_VERSION = 1
 
+# include/simpleicp_hip_plane.h: planes of a cloud scored by their inliers and refitted on them, the same kind of companion
+PLANE_EXPORTS = ["sicp_plane_version", "sicp_plane_triplets", "sicp_plane_refit"]
+PLANE_VERSION = 1
+PLANE_MAX_ROUNDS = 16
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -183,6 +188,16 @@ class ClusterStats(_Stats):
     _fields_ = [(name, C.c_int64) for name in ("n_points", "n_core", "n_border", "n_noise", "n_clusters", "largest_label", "largest_size")]
 
 
+class PlaneStats(_Stats):
+    """struct sicp_plane_stats (contract (P)): 48 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_candidates", "n_hypotheses", "n_void", "best", "best_inliers")]
+
+
+class PlaneRefitStats(_Stats):
+    """struct sicp_plane_refit_stats (contract (Q)): 40 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_planes", "n_void", "n_improved", "best", "best_inliers")]
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -253,6 +268,9 @@ FEATURES = {
         "sicp_keypoints": [_vp, _cint, _cint, _dbl, _cint, _dbl, _dbl, _dbl, _i64, _vp, _vp, _vp, C.POINTER(KeypointStats)]}),
     "cluster": _Feature(CLUSTER_EXPORTS, "simpleicp_hip_cluster.h", "cluster", CLUSTER_VERSION, {
         "sicp_cluster": [_vp, _cint, _dbl, _i64, _vp, _vp, C.POINTER(ClusterStats)]}),
+    "plane": _Feature(PLANE_EXPORTS, "simpleicp_hip_plane.h", "plane", PLANE_VERSION, {
+        "sicp_plane_triplets": [_vp, _vp, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, C.POINTER(PlaneStats)],
+        "sicp_plane_refit": [_vp, _vp, _i64, _vp, _vp, _i64, _dbl, _cint, _vp, _vp, _vp, C.POINTER(PlaneRefitStats)]}),
 }
 
 _lib = None
@@ -385,6 +403,19 @@ def _pose_call_arrays(src, dst, poses):
     return s, d, p, np.empty((b, 12), np.float64), np.empty(b, np.int32)
 
 
+def _cloud_rows(X, mask):
+    """Host form of plane_triplets / plane_refit: the (n, 3) float64 rows and the (n,) uint8 mask (None: every row), checked."""
+    x = _f64(X)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError("X must be (n, 3)")
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0).view(np.uint8)
+        if m.shape != (x.shape[0],):
+            raise ValueError(f"mask must have shape ({x.shape[0]},), not {m.shape}")
+    return x, m
+
+
 def device_count():
     n = C.c_int(0)
     load().sicp_device_count(C.byref(n))
@@ -425,6 +456,7 @@ robust_version = partial(_feature_version, "robust")
 consistency_version = partial(_feature_version, "consistency")
 keypoints_version = partial(_feature_version, "keypoints")
 cluster_version = partial(_feature_version, "cluster")
+plane_version = partial(_feature_version, "plane")
 
 
 def select_positions(m, Q):
@@ -838,6 +870,54 @@ class Context:
         labels, core = (np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.uint8)) if host else (labels_ptr, core_ptr)
         self._chk(self._L.sicp_cluster(self._h, slot, float(radius), int(min_points), _ptr(labels), _ptr(core), C.byref(st)))
         return (labels[:n], core[:n].view(np.bool_), st) if host else st
+
+    # -- planes of a cloud (contracts (P) and (Q)) --
+    def plane_triplets(self, X, triples, max_distance, mask=None, n=None, h=None, planes_ptr=None, inliers_ptr=None, want_planes=True):
+        """sicp_plane_triplets: one plane per triple of rows of X (unit normal and d: contract (P)), scored by the candidate rows
+        -- mask != 0; None: all -- strictly within max_distance of it.  Host form: an (n, 3) float64 array, an (n,) mask or None
+        and (h, 3) int32 triples; returns ((h, 4) float64 planes or None, (h,) int32 inliers: -1 void, PlaneStats).  Pointer form:
+        X, mask (or None) and triples are addresses (ints) of host or device memory, n and h given; the inliers are left at
+        inliers_ptr (h int32), the planes at planes_ptr if given (h * 4 doubles), and the PlaneStats alone is returned."""
+        plane_version()
+        st = PlaneStats()
+        host = inliers_ptr is None
+        x, m, tri, planes, inl = X, mask, triples, planes_ptr, inliers_ptr
+        if host:
+            x, m = _cloud_rows(X, mask)
+            tri = np.ascontiguousarray(triples, dtype=np.int32)
+            if tri.ndim != 2 or tri.shape[1] != 3:
+                raise ValueError("triples must be (h, 3)")
+            n, h = x.shape[0], tri.shape[0]
+            planes = np.empty((h, 4), np.float64) if want_planes else None
+            inl = np.empty(h, np.int32)
+        self._chk(self._L.sicp_plane_triplets(self._h, _ptr(x), int(n), _ptr(m), _ptr(tri), int(h), float(max_distance), _ptr(planes),
+                                              _ptr(inl), C.byref(st)))
+        return (planes, inl, st) if host else st
+
+    def plane_refit(self, X, planes, max_distance, rounds, mask=None, n=None, b=None, planes_ptr=None, inliers_ptr=None, keep_ptr=None,
+                    want_keep=False):
+        """sicp_plane_refit: every plane refitted on its own inliers among the candidate rows of X in `rounds` rounds (contract
+        (Q)); what leaves is the plane with the most inliers among the one given and every round's.  Host form: an (n, 3) float64
+        array, an (n,) mask or None and (b, 4) float64 planes; returns ((b, 4) float64 planes, (b,) int32 inliers: -1 void, the
+        (n,) bool inlier mask of the output plane -- want_keep, b == 1 -- or None, PlaneRefitStats).  Pointer form: X, mask (or
+        None) and planes are addresses (ints) of host or device memory, n and b given; the planes are left at planes_ptr (b * 4
+        doubles), the inliers at inliers_ptr (b int32), the mask's bytes at keep_ptr if given (n bytes), and the PlaneRefitStats
+        alone is returned."""
+        plane_version()
+        st = PlaneRefitStats()
+        host = inliers_ptr is None
+        x, m, p, out, inl, keep = X, mask, planes, planes_ptr, inliers_ptr, keep_ptr
+        if host:
+            x, m = _cloud_rows(X, mask)
+            p = _f64(planes)
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise ValueError("planes must be (b, 4)")
+            n, b = x.shape[0], p.shape[0]
+            out, inl = np.empty((b, 4), np.float64), np.empty(b, np.int32)
+            keep = np.empty(max(n, 1), np.uint8) if want_keep else None
+        self._chk(self._L.sicp_plane_refit(self._h, _ptr(x), int(n), _ptr(m), _ptr(p), int(b), float(max_distance), int(rounds), _ptr(out),
+                                           _ptr(inl), _ptr(keep), C.byref(st)))
+        return (out, inl, None if keep is None else keep[:n].view(np.bool_), st) if host else st
 
     # -- descriptor matching and RANSAC poses (contracts (M) and (R)) --
     def feature_match(self, query, target, nq=None, nt=None, dim=None, idx_ptr=None, d2_ptr=None, want_d2=True):

@@ -259,6 +259,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_KEYPOINT_CHUNK")) c->keypoint_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_PLANE_SPAN")) c->plane_span = std::atol(e) > 0 ? std::atol(e) : 0;
     if (const char *e = std::getenv("SICP_ROBUST")) c->robust_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
     if (const char *e = std::getenv("SICP_CONSISTENCY")) c->consistency_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
     // SICP_SOLVE_TRACE: per-iteration traces on stderr -- any value: the tail's cycle counters; "host": the host's enqueue timings too;
@@ -316,6 +317,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->gl_src.release(); c->gl_dst.release(); c->gl_pose.release();
     c->pf_in.release(); c->pf_state.release(); c->pf_part.release(); c->pf_part2.release(); c->pf_cnt.release();
     c->rb_state.release(); c->rb_scale.release();
+    c->pl_plane.release(); c->pl_state.release(); c->pl_mask.release(); c->pl_keep.release();
     c->cs_bits.release(); c->cs_front.release(); c->cs_work.release(); c->cs_core.release(); c->cs_state.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);

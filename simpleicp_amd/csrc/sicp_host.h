@@ -336,6 +336,12 @@ struct sicp_ctx {
     DevBuf<uint32_t> cl_parent, cl_root, cl_rank, cl_size;
     DevBuf<int32_t> cl_labels;
     long cluster_chunk = 1L << 22; // SICP_CLUSTER_CHUNK: points per launch of sicp_cluster's ball walks
+    // planes of a cloud (sicp_plane.hip): the hypotheses' planes where the caller takes none, the refitted planes' states between
+    // the launches, the staged mask and keep bytes (the rows are staged in gl_src, the triples in gl_tri, the planes that come in
+    // in pf_in, the outputs in gl_pose / gl_idx; the spans' partial sums and counts lie in pf_part / pf_part2 / pf_cnt)
+    DevBuf<double> pl_plane, pl_state;
+    DevBuf<uint8_t> pl_mask, pl_keep;
+    long plane_span = 0;           // SICP_PLANE_SPAN: rows a workgroup of sicp_plane_triplets' scoring kernel takes (0: chosen per call)
     // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
     // the call's arrays
     DevBuf<unsigned long long> gl_key;

@@ -1,6 +1,8 @@
 """FPFH descriptors: 33 floats per point, the local shape descriptor a global registration matches clouds by -- and ISS keypoints,
 the points worth describing (``keypoint_keep``; contract (I), DESIGN.md section 22, include/simpleicp_hip_keypoints.h) -- and DBSCAN
-labels, the points that belong together (``cluster_labels``; contract (U), DESIGN.md section 23, include/simpleicp_hip_cluster.h).
+labels, the points that belong together (``cluster_labels``; contract (U), DESIGN.md section 23, include/simpleicp_hip_cluster.h)
+-- and the dominant plane, what goes before the clusters on a scene with a ground (``segment_plane``, ``segment_planes``; contracts
+(P) and (Q), DESIGN.md section 24, include/simpleicp_hip_plane.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -298,3 +300,202 @@ def _cluster_on_device(X, r, mp, return_core):
         return labels, core, dict(_NO_CLUSTERS)
     st = ctx.cluster(_lib.FIX, r, mp, labels_ptr=labels.data_ptr(), core_ptr=core.data_ptr() if return_core else None)
     return labels, core.view(torch.bool), _lib._stats_dict(st)
+
+
+# ---- planes of a cloud (contracts (P) and (Q)) ----
+
+
+class PlaneResult:
+    """What ``segment_plane`` returns.  ``plane``: (4,) float64, the unit normal and d -- a point x lies on it where
+    ``normal . x + d == 0``; ``inliers``: the (n,) bool mask of the candidate rows strictly within ``max_distance`` of it (numpy,
+    or a tensor on the input's device); ``n_inliers``: their number; ``info`` (``return_info=True``; else None): the two calls'
+    records as dicts, ``{"hypotheses": {n_points, n_candidates, n_hypotheses, n_void, best, best_inliers}, "refit": {n_planes,
+    n_void, n_improved, best, best_inliers}}``."""
+
+    def __init__(self, plane, inliers, n_inliers, info=None):
+        self.plane, self.inliers, self.n_inliers, self.info = plane, inliers, int(n_inliers), info
+
+    def __repr__(self):
+        return f"PlaneResult(plane={self.plane!r}, n_inliers={self.n_inliers})"
+
+
+def _seed_of(seed):
+    """A seed of np.random.default_rng: an integer >= 0, or a sequence of them (segment_planes' [seed, j])."""
+    if isinstance(seed, (list, tuple)):
+        if not seed:
+            raise ValueError("seed must not be empty")
+        return [_int_in("seed", s, 0, 2**63 - 1) for s in seed]
+    return _int_in("seed", seed, 0, 2**63 - 1)
+
+
+def plane_arguments(max_distance, hypotheses=1024, seed=0, triples=None, refine=3):
+    """(max_distance, hypotheses, seed, triples as (h, 3) int32 or None, refine), checked: TypeError / ValueError.  ``refine`` is
+    the number of rounds of the refit, 1 .. 16: the refit is what forms the inlier mask, so there is no ``refine=0``."""
+    if isinstance(max_distance, (bool, str, bytes)) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
+        raise TypeError(f"max_distance must be a number, not {max_distance!r}")
+    d = float(max_distance)
+    if not math.isfinite(d) or not d > 0.0:
+        raise ValueError(f"max_distance must be finite and > 0, not {max_distance!r}")
+    h = _int_in("hypotheses", hypotheses, 1, 2**31 - 1)
+    s = _seed_of(seed)
+    r = _int_in("refine", refine, 1, _lib.PLANE_MAX_ROUNDS)
+    tri = None
+    if triples is not None:
+        tri = np.asarray(triples)
+        if tri.dtype.kind not in "iu":
+            raise TypeError(f"triples must be integers, not {tri.dtype}")
+        if tri.ndim != 2 or tri.shape[1] != 3 or tri.shape[0] < 1:
+            raise ValueError(f"triples must have shape (h, 3) with h >= 1, not {tri.shape}")
+        if tri.size and (tri.min() < -2**31 or tri.max() >= 2**31):
+            raise ValueError("triples must fit int32")
+        tri = np.ascontiguousarray(tri, dtype=np.int32)
+    return d, h, s, tri, r
+
+
+def plane_triples(n, mask, hypotheses, seed):
+    """The triples ``segment_plane`` draws, on the host: ``np.random.default_rng(seed).integers(0, n, (hypotheses, 3),
+    dtype=np.int32)`` without a mask; with one ``integers(0, k, ...)`` mapped through the ascending indices of the k candidate
+    rows (for a tensor mask ``torch.nonzero`` on its device: only the 3 * hypotheses indices move)."""
+    rng = np.random.default_rng(seed)
+    if mask is None:
+        return rng.integers(0, n, (hypotheses, 3), dtype=np.int32)
+    if type(mask).__module__.startswith("torch"):
+        import torch
+        rows = torch.nonzero(mask).squeeze(1)
+        at = rng.integers(0, rows.numel(), (hypotheses, 3), dtype=np.int32)
+        picked = rows[torch.as_tensor(at.ravel().astype(np.int64), device=rows.device)].cpu().numpy()
+        return np.ascontiguousarray(picked.reshape(hypotheses, 3), dtype=np.int32)
+    rows = np.flatnonzero(mask)
+    return np.ascontiguousarray(rows[rng.integers(0, len(rows), (hypotheses, 3), dtype=np.int32)], dtype=np.int32)
+
+
+def _plane_rows(X, mask):
+    """(on_device, the rows as the entries read them -- float64, contiguous --, the mask as contiguous bool or None, n, k):
+    the cloud and the mask of a plane call, checked; k is the number of candidate rows."""
+    from .pointcloud import PointCloud
+    from .tensors import _check_cloud, _is_device_tensor
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        import torch
+        _check_cloud("X", X, backend.default_device())
+        n = X.shape[0]
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
+                raise TypeError("mask must be a bool or uint8 torch.Tensor of shape (n,)")
+            if mask.device != X.device:
+                raise ValueError(f"mask is on {mask.device}, X on {X.device}")
+            mask = (mask != 0).contiguous()
+        rows, on_device = X.to(torch.float64).contiguous(), True
+    else:
+        rows = np.ascontiguousarray(X.X if isinstance(X, PointCloud) else X, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != 3:
+            raise ValueError("X must be a PointCloud, an (n, 3) array or a CUDA tensor")
+        n, on_device = rows.shape[0], False
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype.kind not in "bui" or mask.shape != (n,):
+                raise TypeError(f"mask must be a bool or integer array of shape ({n},)")
+            mask = np.ascontiguousarray(mask != 0)
+    if n >= 2**31:
+        raise ValueError("X must have fewer than 2^31 rows")
+    k = n if mask is None else int(mask.sum())
+    if k < 3:
+        raise ValueError(f"a plane needs at least 3 candidate rows, not {k}")
+    return on_device, rows, mask, n, k
+
+
+def _plane_context(who, ctx=None):
+    if dist.is_distributed():
+        from .icp import SimpleICPException
+        raise SimpleICPException(f"{who} does not run in a torch.distributed job: segment the clouds with one process first")
+    ctx = ctx or backend.get_context()
+    if not hasattr(ctx, "plane_triplets") or not hasattr(ctx, "plane_refit"):
+        raise _lib.BackendError("this backend has no plane segmentation")
+    dist.detach(ctx)
+    return ctx
+
+
+def _segment_plane(ctx, on_device, rows, mask, n, d, h, seed, tri, rounds, return_info):
+    """segment_plane behind its checks; None when no hypothesis is valid."""
+    if tri is None:
+        tri = plane_triples(n, mask, h, seed)
+    if on_device:
+        import torch
+        from .tensors import _wait_for_torch
+        m8 = None if mask is None else mask.view(torch.uint8)
+        keep = torch.empty(n, dtype=torch.uint8, device=rows.device)
+        _wait_for_torch(ctx, rows.device)             # (the float64 copy, the mask's bytes and torch.nonzero come first)
+        mp = None if m8 is None else m8.data_ptr()
+        planes, inl = np.empty((len(tri), 4), np.float64), np.empty(len(tri), np.int32)
+        st = _lib._stats_dict(ctx.plane_triplets(rows.data_ptr(), tri.ctypes.data, d, mask=mp, n=n, h=len(tri), planes_ptr=planes.ctypes.data,
+                                                 inliers_ptr=inl.ctypes.data))
+    else:
+        planes, inl, st = ctx.plane_triplets(rows, tri, d, mask=mask)
+        st = _lib._stats_dict(st)
+    if st["best"] < 0:
+        return None
+    start = np.ascontiguousarray(planes[st["best"]:st["best"] + 1], dtype=np.float64)
+    if on_device:
+        out, cnt = np.empty((1, 4), np.float64), np.empty(1, np.int32)
+        st2 = ctx.plane_refit(rows.data_ptr(), start.ctypes.data, d, rounds, mask=mp, n=n, b=1, planes_ptr=out.ctypes.data,
+                              inliers_ptr=cnt.ctypes.data, keep_ptr=keep.data_ptr())
+        keep = keep.view(torch.bool)
+    else:
+        out, cnt, keep, st2 = ctx.plane_refit(rows, start, d, rounds, mask=mask, want_keep=True)
+    info = {"hypotheses": st, "refit": _lib._stats_dict(st2)} if return_info else None
+    return PlaneResult(np.array(out[0], dtype=np.float64), keep, int(cnt[0]), info)
+
+
+def segment_plane(X, max_distance, *, hypotheses=1024, seed=0, triples=None, refine=3, mask=None, return_info=False):
+    """The dominant plane of X -- ground, floor, table, wall -- by RANSAC (contracts (P) and (Q)): every
+    triple of points gives one plane, a plane's score is the number of candidate rows strictly within ``max_distance`` of it, and
+    the best plane is refitted on its own inliers in ``refine`` rounds (the least-squares plane of the inliers; what comes back
+    never has fewer inliers than the best hypothesis).  ``X[~segment_plane(X, d).inliers]`` is the cloud without it: what
+    ``cluster_labels`` takes apart into objects.  Open3D's ``segment_plane``, reproducible bit for bit.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any strides;
+    float32 is widened exactly, the rows stay on the device; the stream rule is run_tensors').  ``mask`` (n,): only the rows it
+    marks are candidates -- they alone count and define planes; bool / integer array, or a bool / uint8 tensor on X's device.
+    ``triples``: (h, 3) integers; None: drawn on the host from ``seed`` (``plane_triples``; a repeated index is simply a void
+    hypothesis).  ``refine``: rounds of the refit, 1 .. 16 -- the refit forms the inlier mask, so 0 is refused with ValueError.
+    Returns a ``PlaneResult``; ValueError when no hypothesis is valid (fewer than three candidates, or all triples degenerate)."""
+    d, h, s, tri, r = plane_arguments(max_distance, hypotheses, seed, triples, refine)
+    if not isinstance(return_info, (bool, np.bool_)):
+        raise TypeError(f"return_info must be True or False, not {return_info!r}")
+    on_device, rows, mask, n, _ = _plane_rows(X, mask)
+    res = _segment_plane(_plane_context("segment_plane"), on_device, rows, mask, n, d, h, s, tri, r, bool(return_info))
+    if res is None:
+        raise ValueError("no hypothesis is valid: every triple is degenerate, repeats a row or names a row that is no candidate")
+    return res
+
+
+def segment_planes(X, max_distance, *, min_inliers, max_planes=4, hypotheses=1024, seed=0, refine=3):
+    """The planes of X, peeled off one after the other: round j is ``segment_plane`` on the rows no plane has taken yet
+    (``mask = labels == -1``) with ``seed = [seed, j]``; it stops after ``max_planes`` planes, when a plane has fewer than
+    ``min_inliers`` inliers (that plane is dropped), when fewer than three rows are left, or when no hypothesis is valid.
+    ``min_inliers`` has no default: it is what tells a plane from clutter in the caller's scene.
+
+    Returns ``(labels, planes)``: (n,) int32 -- -1, or 0, 1, ... in the order of extraction; numpy, or a tensor on X's device --
+    and the (k, 4) float64 planes."""
+    d, h, s, _, r = plane_arguments(max_distance, hypotheses, seed, None, refine)
+    if isinstance(s, list):
+        raise TypeError("seed must be one integer: round j draws from [seed, j]")
+    most = _int_in("max_planes", max_planes, 1, 2**31 - 1)
+    least = _int_in("min_inliers", min_inliers, 1, 2**31 - 1)
+    on_device, rows, _, n, _ = _plane_rows(X, None)
+    ctx = _plane_context("segment_planes")
+    if on_device:
+        import torch
+        labels = torch.full((n,), -1, dtype=torch.int32, device=rows.device)
+    else:
+        labels = np.full(n, -1, np.int32)
+    planes = []
+    for j in range(most):
+        left = labels == -1
+        if int(left.sum()) < 3:
+            break
+        res = _segment_plane(ctx, on_device, rows, left, n, d, h, [s, j], None, r, False)
+        if res is None or res.n_inliers < least:
+            break
+        labels[res.inliers] = j
+        planes.append(res.plane)
+    return labels, np.array(planes, dtype=np.float64).reshape(-1, 4)

@@ -57,6 +57,7 @@ def voxel_arguments(voxel_size, origin=None, exc=ValueError):
 class PointCloud(pd.DataFrame):
     last_outlier_stats = None             # select_statistical_inliers leaves its statistics here (a dict)
     last_keypoint_stats = None            # select_keypoints leaves its record here (a dict)
+    last_plane = None                     # select_plane leaves its PlaneResult here (inliers over the whole cloud)
     last_cluster_stats = None             # select_largest_cluster / select_clusters leave their record here (a dict)
 
     def __init__(self, *args, **kwargs) -> None:
@@ -390,6 +391,36 @@ class PointCloud(pd.DataFrame):
             return
         sizes = np.bincount(labels[labels >= 0], minlength=1)
         self._set_idx_selected(cur[(labels >= 0) & (sizes[np.maximum(labels, 0)] >= int(min_size))])
+
+    def select_plane(self, max_distance: float, invert: bool = False, _ctx=None, **kw) -> None:
+        """Keeps, among the selected points, the inliers of the dominant plane of the SELECTED points -- the selection goes in as
+        ``segment_plane``'s mask over the whole cloud, so the points that are not selected neither count nor define a plane --
+        and deselects the rest (contracts (P) and (Q); ``max_distance`` and the keywords ``hypotheses``,
+        ``seed``, ``triples``, ``refine`` are ``segment_plane``'s).  ``invert=True``: keeps the complement instead, the selected
+        points off the plane -- the call before ``select_largest_cluster`` on a scene with a ground.  The ``PlaneResult`` of the
+        call is left in ``last_plane``.  Not in the reference; composes with select_in_range, select_voxels and select_n_points."""
+        from . import features
+        if not isinstance(invert, (bool, np.bool_)):
+            raise PointCloudException(f"invert must be True or False, not {invert!r}")
+        unknown = set(kw) - {"hypotheses", "seed", "triples", "refine"}
+        if unknown:
+            raise PointCloudException(f"select_plane takes no keyword {sorted(unknown)[0]!r}")
+        try:
+            d, h, s, tri, r = features.plane_arguments(max_distance, **kw)
+        except (TypeError, ValueError) as e:
+            raise PointCloudException(str(e)) from None
+        selected = np.ascontiguousarray(self["selected"].to_numpy(), dtype=bool)
+        if not selected.any():
+            return
+        try:
+            on_device, rows, mask, n, _ = features._plane_rows(self, selected)
+            res = features._segment_plane(features._plane_context("select_plane", _ctx), on_device, rows, mask, n, d, h, s, tri, r, True)
+        except ValueError as e:
+            raise PointCloudException(str(e)) from None
+        if res is None:
+            raise PointCloudException("no hypothesis is valid: the selected points give no plane")
+        self.last_plane = res
+        self._set_idx_selected(np.flatnonzero(selected & ~res.inliers if invert else res.inliers))
 
     def fpfh(self, neighbors: int = 32, radius=None) -> np.ndarray:
         """The (n, 33) float32 FPFH descriptors of ALL points (contract (F)): ``fpfh_features(self,
