@@ -1,7 +1,7 @@
 // sicp_cluster.hip -- DBSCAN labels of a cloud (include/simpleicp_hip_cluster.h; contract (U)).
 //
 // Core flags: the radius filter's k_ball_count (sicp_outlier.hip, through ball_count_enqueue) with cap = min_points.  Union: k_ball_union
-// walks every core point's ball with CL_GS lanes and unites it with the core hits of lower index in a lock-free union-find
+// walks every core point's ball (ball_walk: sicp_ball_dev.h) and unites it with the core hits of lower index in a lock-free union-find
 // (uf_find / uf_union: a root is only ever hooked under a smaller root, so a component's root ends up its lowest core index whatever
 // the order of arrival).  k_cl_flatten leaves every core point's root and the block sums of the root flags; k_ball_border gives a
 // point that is not core the smallest root among its core hits; k_cl_scan_sums / k_cl_apply rank the roots in index order (the
@@ -9,14 +9,13 @@
 // No kernel waits for another wave or workgroup: the only loops over memory another wave writes are uf_find's walk towards a root
 // (parents only ever decrease) and uf_union's retry after a failed compare-and-swap (another lane's succeeded).  Integer atomics only.
 #include "sicp_host.h"
-#include "sicp_grid_dev.h"
+#include "sicp_ball_dev.h"
 #include "../../include/simpleicp_hip_cluster.h"
 
 namespace sicp {
 namespace {
 
 constexpr int CL_BLOCK = 256;
-constexpr int CL_GS = 16;                          // lanes per point of the two walks (k_ball_count's OL_GS: a group is one DPP row)
 constexpr int CL_PER = 4;                          // consecutive points per thread of k_cl_flatten / k_cl_apply
 constexpr int CL_SPAN = CL_BLOCK * CL_PER;         // points per workgroup of the rank scan
 constexpr int CL_RUN = 16;                         // consecutive rows of 64 points per wave of k_cl_labels
@@ -67,86 +66,17 @@ __global__ __launch_bounds__(CL_BLOCK) void k_cl_fill(uint32_t *__restrict__ par
     for (long e = (long)blockIdx.x * CL_BLOCK + threadIdx.x; e < n; e += stride) parent[e] = (uint32_t)e;
 }
 
-// ---- the ball walk ----------------------------------------------------------------------------------------------------------------
-// k_ball_count's walk (sicp_outlier.hip) without its early exit: the CL_GS lanes of a group fetch the record ranges of CL_GS rows of
-// the ball's box at once, culled to the ball along x (row_lb2, row_x_clip, row_records: sicp_grid_dev.h), then take the records of
-// one row after the other, two per lane and step.  hit(h0, j0, h1, j1), called by all lanes of the group together: is the lane's
-// record a neighbour (d2 < r2, contract (D)), and its original index.
-template <class Hit>
-__device__ __forceinline__ void ball_walk(const uint32_t *__restrict__ cell_start, const double4 *__restrict__ rec, const GridGeom &G,
-                                          double ax, double ay, double az, double r, double r2, int sub, int gbase, Hit &&hit)
-{
-    const double c3[3] = {ax, ay, az};
-    // (the margins of the ball that is culled with: k_ball_count's)
-    const double rr = r + (1e-9 * r + 1e-15 * (fabs(ax) + fabs(ay) + fabs(az) + r));
-    const double rr2 = rr * rr, etol = 1e-6 * G.h;
-    int lo[3], hi[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double fl = floor((c3[a] - rr - G.mn[a]) * G.inv_h - 1e-6);
-        const double fh = floor((c3[a] + rr - G.mn[a]) * G.inv_h + 1e-6);
-        lo[a] = fl < 0.0 ? 0 : (fl > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fl);
-        hi[a] = fh < 0.0 ? 0 : (fh > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fh);
-    }
-    const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
-    const int nrows = ny * nz;                                 // (the host bounds the box: SICP_OUTLIER_MAX_BOX_CELLS)
-    for (int rb = 0; rb < nrows; rb += CL_GS) {
-        uint32_t b = 0, len = 0;
-        const int rw = rb + sub;
-        if (rw < nrows) {
-            const int oz = rw / ny, oy = rw - oz * ny;
-            const int cy = lo[1] + oy, cz = lo[2] + oz;
-            const long row = ((long)cz * G.dim[1] + cy) * G.dim[0];
-            const double rem = rr2 - row_lb2(G, cy, cz, ay, az, etol);
-            if (rem >= 0.0) {
-                int xl = lo[0], xh = hi[0];
-                row_x_clip(G, ax, rem, etol, xl, xh);
-                row_records(cell_start, row, xl, xh, b, len);
-            }
-        }
-        unsigned todo = (unsigned)(__ballot(len > 0) >> gbase) & ((1u << CL_GS) - 1u);
-        while (todo) {
-            const int j = __ffs((int)todo) - 1;
-            todo &= todo - 1u;
-            const uint32_t bj = (uint32_t)__shfl((int)b, gbase + j), lj = (uint32_t)__shfl((int)len, gbase + j);
-            for (uint32_t o = 0; o < lj; o += 2 * CL_GS) {
-                const uint32_t i0 = o + (uint32_t)sub, i1 = i0 + CL_GS;
-                const bool ok0 = i0 < lj, ok1 = i1 < lj;
-                const double4 P0 = rec[ok0 ? bj + i0 : bj], P1 = rec[ok1 ? bj + i1 : bj];
-                const double dx0 = P0.x - ax, dy0 = P0.y - ay, dz0 = P0.z - az;
-                const double dx1 = P1.x - ax, dy1 = P1.y - ay, dz1 = P1.z - az;
-                const bool h0 = ok0 && fma(dz0, dz0, fma(dy0, dy0, dx0 * dx0)) < r2;
-                const bool h1 = ok1 && fma(dz1, dz1, fma(dy1, dy1, dx1 * dx1)) < r2;
-                hit(h0, (uint32_t)__double_as_longlong(P0.w), h1, (uint32_t)__double_as_longlong(P1.w));
-            }
-        }
-    }
-}
-
-// which point a group of CL_GS lanes takes: slot s of the launch (order: the chunk's points in cell order, one contiguous eighth of
-// them per XCD -- the grid is a multiple of 8 blocks then; k_ball_count's rule); -1: none
-__device__ __forceinline__ long group_point(const uint32_t *__restrict__ order, long Q)
-{
-    long blk = blockIdx.x;
-    if (order) {
-        const long per_xcd = gridDim.x >> 3;
-        blk = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    }
-    const long slot = blk * (CL_BLOCK / CL_GS) + (threadIdx.x / CL_GS);
-    if (slot >= Q) return -1;
-    return order ? (long)order[slot] : slot;
-}
-
+// ---- the two walks (ball_group_point, ball_walk: sicp_ball_dev.h; neither ever has enough: the visitors answer 1) ------------
 // Every core point i of the chunk [lo, lo + Q) is united with its core neighbours j < i (each edge is seen once, from its higher
 // end).  ri: the root of i as far as the group knows; a hit that is that root, or whose root is, costs no write.
-__global__ __launch_bounds__(CL_BLOCK) void k_ball_union(const double *__restrict__ qx, const double *__restrict__ qy,
-                                                         const double *__restrict__ qz, const uint32_t *__restrict__ order,
-                                                         const uint32_t *__restrict__ cell_start, const double4 *__restrict__ rec,
-                                                         const uint8_t *__restrict__ core, uint32_t *parent, long Q, long lo, GridGeom G,
-                                                         double r, double r2)
+__global__ __launch_bounds__(BALL_BLOCK) void k_ball_union(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                           const double *__restrict__ qz, const uint32_t *__restrict__ order,
+                                                           const uint32_t *__restrict__ cell_start, const double4 *__restrict__ rec,
+                                                           const uint8_t *__restrict__ core, uint32_t *parent, long Q, long lo, GridGeom G,
+                                                           double r, double r2)
 {
-    const int lane = threadIdx.x & 63, sub = lane & (CL_GS - 1), gbase = lane & ~(CL_GS - 1);
-    const long q = group_point(order, Q);
+    const int lane = threadIdx.x & 63, sub = lane & (BALL_GS - 1), gbase = lane & ~(BALL_GS - 1);
+    const long q = ball_group_point(order, Q);
     if (q < 0) return;
     const uint32_t i = (uint32_t)(lo + q);
     if (!core[i]) return;
@@ -161,7 +91,8 @@ __global__ __launch_bounds__(CL_BLOCK) void k_ball_union(const double *__restric
             const uint32_t rj = uf_find(parent, j1);
             if (rj != mine) mine = uf_union(parent, mine, rj);
         }
-        ri = gmin<CL_GS>(mine);                                    // (every lane's root is one of i's set: the smallest is the newest)
+        ri = gmin<BALL_GS>(mine);                                  // (every lane's root is one of i's set: the smallest is the newest)
+        return 1u;
     });
 }
 
@@ -187,14 +118,14 @@ __global__ __launch_bounds__(CL_BLOCK) void k_cl_flatten(const uint8_t *__restri
 }
 
 // A point of the chunk that is not core takes the smallest root among its core neighbours (root order is label order); none: noise.
-__global__ __launch_bounds__(CL_BLOCK) void k_ball_border(const double *__restrict__ qx, const double *__restrict__ qy,
-                                                          const double *__restrict__ qz, const uint32_t *__restrict__ order,
-                                                          const uint32_t *__restrict__ cell_start, const double4 *__restrict__ rec,
-                                                          const uint8_t *__restrict__ core, uint32_t *root, long Q, long lo, GridGeom G,
-                                                          double r, double r2)
+__global__ __launch_bounds__(BALL_BLOCK) void k_ball_border(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                            const double *__restrict__ qz, const uint32_t *__restrict__ order,
+                                                            const uint32_t *__restrict__ cell_start, const double4 *__restrict__ rec,
+                                                            const uint8_t *__restrict__ core, uint32_t *root, long Q, long lo, GridGeom G,
+                                                            double r, double r2)
 {
-    const int lane = threadIdx.x & 63, sub = lane & (CL_GS - 1), gbase = lane & ~(CL_GS - 1);
-    const long q = group_point(order, Q);
+    const int lane = threadIdx.x & 63, sub = lane & (BALL_GS - 1), gbase = lane & ~(BALL_GS - 1);
+    const long q = ball_group_point(order, Q);
     if (q < 0) return;
     const long i = lo + q;
     if (core[i]) return;
@@ -203,8 +134,9 @@ __global__ __launch_bounds__(CL_BLOCK) void k_ball_border(const double *__restri
         // (root[j] of a core point was written by k_cl_flatten; this kernel writes the others' words only)
         if (h0 && core[j0]) { const uint32_t rj = root[j0]; best = rj < best ? rj : best; }
         if (h1 && core[j1]) { const uint32_t rj = root[j1]; best = rj < best ? rj : best; }
+        return 1u;
     });
-    best = gmin<CL_GS>(best);
+    best = gmin<BALL_GS>(best);
     if (sub == 0) root[i] = best;
 }
 
@@ -330,32 +262,6 @@ namespace {
 
 static_assert(CL_BEST < CAND_WORDS, "the record's counters fit the ctx's counter words");
 
-// one of the three walks over the cloud, a chunk at a time: the chunk's columns gathered, its cell order built from SICP_ORDER_MIN_Q
-// points on; a cloud that fits one chunk keeps both for the walks that follow
-struct ChunkWalk {
-    sicp_ctx *c; int slot; long n, chunk; double order_h;
-    bool kept = false;
-    const uint32_t *order = nullptr;
-    int enter(long lo, long cnt)
-    {
-        if (kept) return SICP_OK;
-        rows_gather(c, slot, nullptr, lo, cnt);
-        order = nullptr;
-        if (c->order_min_q > 0 && cnt >= c->order_min_q) {
-            const long qpad = round_up(cnt, QPAD);
-            CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, order_h, 1L << 22, c->k_order));
-            order = c->k_order.p;
-        }
-        kept = n <= chunk;
-        return SICP_OK;
-    }
-    unsigned grid(long cnt) const
-    {
-        const unsigned g = cdiv(cnt, CL_BLOCK / CL_GS);
-        return order ? (g + 7u) & ~7u : g;
-    }
-};
-
 }  // namespace
 
 SICP_EXPORT int sicp_cluster_version(void) { return SICP_CLUSTER_VERSION; }
@@ -387,34 +293,32 @@ SICP_EXPORT int sicp_cluster(sicp_ctx *c, int slot, double radius, int64_t min_p
         unsigned long long *counters = c->cand_small.p;
         const double r2 = radius * radius;
         const unsigned cap = (unsigned)std::min<int64_t>(min_points, 1LL << 31);       // counts stay below 2^31
-        const long chunk = c->cluster_chunk;
-        CHK(c->kq.reserve((size_t)3 * round_up(std::min(chunk, n), QPAD)));
-        ChunkWalk W{c, slot, n, chunk, 2.0 * lv.g.h};
+        BallChunks W{c, slot, lv, nullptr, n, c->cluster_chunk};
+        CHK(W.reserve());
         const dim3 flat(std::min(cdiv(n, CL_BLOCK), (unsigned)CL_MAX_BLOCKS));
         // core flags
-        for (long lo = 0; lo < n; lo += chunk) {
-            const long cnt = std::min(chunk, n - lo);
+        for (long lo = 0; lo < n; lo += W.chunk) {
+            const long cnt = std::min(W.chunk, n - lo);
             CHK(W.enter(lo, cnt));
             // (no count from the kernel: its one atomic per wave on one word costs more than the walk where most points are core)
-            CHK(ball_count_enqueue(c, c->kq.p, round_up(cnt, QPAD), W.order, nullptr, lv, cnt, radius, cap, core + lo, c->ol_cnt.p + lo,
-                                   nullptr));
+            CHK(ball_count_enqueue(W, nullptr, cnt, radius, cap, core + lo, c->ol_cnt.p + lo, nullptr));
         }
         // unions
         hipLaunchKernelGGL(k_cl_fill, flat, dim3(CL_BLOCK), 0, c->stream, parent, n);
-        for (long lo = 0; lo < n; lo += chunk) {
-            const long cnt = std::min(chunk, n - lo), qpad = round_up(cnt, QPAD);
+        for (long lo = 0; lo < n; lo += W.chunk) {
+            const long cnt = std::min(W.chunk, n - lo);
             CHK(W.enter(lo, cnt));
-            hipLaunchKernelGGL(k_ball_union, dim3(W.grid(cnt)), dim3(CL_BLOCK), 0, c->stream, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad,
-                               W.order, lv.cell_start, (const double4 *)lv.rec, core, parent, cnt, lo, lv.g, radius, r2);
+            hipLaunchKernelGGL(k_ball_union, dim3(W.grid(cnt)), dim3(BALL_BLOCK), 0, c->stream, W.qx(), W.qy(), W.qz(), W.order, lv.cell_start,
+                               (const double4 *)lv.rec, core, parent, cnt, lo, lv.g, radius, r2);
             HIPCHK(hipGetLastError());
         }
         hipLaunchKernelGGL(k_cl_flatten, dim3((unsigned)nb), dim3(CL_BLOCK), 0, c->stream, core, parent, root, n, sums);
         // borders
-        for (long lo = 0; lo < n; lo += chunk) {
-            const long cnt = std::min(chunk, n - lo), qpad = round_up(cnt, QPAD);
+        for (long lo = 0; lo < n; lo += W.chunk) {
+            const long cnt = std::min(W.chunk, n - lo);
             CHK(W.enter(lo, cnt));
-            hipLaunchKernelGGL(k_ball_border, dim3(W.grid(cnt)), dim3(CL_BLOCK), 0, c->stream, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad,
-                               W.order, lv.cell_start, (const double4 *)lv.rec, core, root, cnt, lo, lv.g, radius, r2);
+            hipLaunchKernelGGL(k_ball_border, dim3(W.grid(cnt)), dim3(BALL_BLOCK), 0, c->stream, W.qx(), W.qy(), W.qz(), W.order, lv.cell_start,
+                               (const double4 *)lv.rec, core, root, cnt, lo, lv.g, radius, r2);
             HIPCHK(hipGetLastError());
         }
         // ranks, labels, record

@@ -3,9 +3,10 @@
 //   * the BALL WALK's geometry -- ball_block, row_lb2, row_x_clip, row_records: which cells a ball touches, row by row, with the
 //     margins that make every search exact.  The rows' three functions are the one text of it: k_grid_nn / _wait / _batch
 //     (sicp_grid_nn_one.inc), k_grid_nn16, k_grid_knn_sweep, k_grid_knn_sweep4 / _list (sicp_grid.hip, sicp_knn_sweep4.inc),
-//     k_grid_nn16f (sicp_gridf.hip) and k_ball_count (sicp_outlier.hip) call them.  ball_block is called by the two sweeps; the
-//     one-wave search, k_grid_nn16, k_grid_knn, k_grid_nn16f and k_ball_count keep its text written out, each with the register or
-//     the time the call cost it (profiles/ballwalk/README.md): a change to the block's margins is made HERE and in those five.
+//     k_grid_nn16f (sicp_gridf.hip) and ball_walk (sicp_ball_dev.h: k_ball_count, k_ball_union, k_ball_border) call them.
+//     ball_block is called by the two sweeps; the one-wave search, k_grid_nn16, k_grid_knn, k_grid_nn16f and ball_walk keep its
+//     text written out, each with the register or the time the call cost it (profiles/ballwalk/README.md): a change to the
+//     block's margins is made HERE and in those five.
 //     row_split turns a row number into (y, z);
 //   * the cells' tight boxes (box_lb2, box_trim_row);
 //   * the transform contract (xf), the match epilogue (post_match), wmin_d, okey.

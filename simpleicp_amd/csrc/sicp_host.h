@@ -416,16 +416,6 @@ inline GridSearch bound_search(GridSearch S, const Grid &sub, double *d2, int64_
     S.coarse = nullptr; S.cell_box = nullptr; S.idx_base = 0; S.d2 = d2; S.idx = idx; S.p2 = p2; S.work = nullptr; S.flags = NN_APPROX;
     return S;
 }
-namespace sicp {
-// the radius filter's ball walk for the units that count the same balls (sicp_outlier.hip): the grid level a ball of `radius` is
-// walked on -- the slot's own grid, built if there is none --, refused with the radius filter's message where the ball's box of
-// cells exceeds SICP_OUTLIER_MAX_BOX_CELLS; and k_ball_count enqueued over cnt candidates whose columns lie qpad apart at q
-// (keep = count >= cap, cnt_out = min(count, cap), *kept_total += the kept; null: not counted)
-int ball_level(sicp_ctx *c, int slot, double radius, GridLevel *lv);
-int ball_count_enqueue(sicp_ctx *c, const double *q, long qpad, const uint32_t *order, const int64_t *pos, const GridLevel &lv, long cnt,
-                       double radius, unsigned cap, uint8_t *keep, uint32_t *cnt_out, unsigned long long *kept_total);
-}  // namespace sicp
-
 namespace sicph {
 
 // The filtered many-queries search (sicp_gridf.hip) of S.Q queries, ties and all: see filtered_search (sicp_search.cpp).  What its two
@@ -442,6 +432,31 @@ struct FilteredSearch {
     int redo_flags;
 };
 int filtered_search(sicp_ctx *c, const FilteredSearch &F);
+
+// The ball operators' host side (sicp_outlier.hip; the radius filter and sicp_cluster.hip walk the same balls with the kernels of
+// sicp_ball_dev.h).  ball_level: the grid level a ball of `radius` is walked on -- the slot's own grid, built if there is none --,
+// refused with the radius filter's message where the ball's box of cells exceeds SICP_OUTLIER_MAX_BOX_CELLS.
+int ball_level(sicp_ctx *c, int slot, double radius, GridLevel *lv);
+// A walk over n rows of the slot, `chunk` of them per launch: enter(lo, cnt) gathers rows d_rows[lo, lo + cnt) (null: rows lo, lo + 1,
+// ...) as columns in c->kq, qpad apart, and from SICP_ORDER_MIN_Q rows on builds their cell order (cells of twice the level's size,
+// at most 1 << 22 of them); a job that fits one chunk keeps both for the walks that follow.  reserve(): c->kq for the largest chunk.
+// grid(cnt): a ball kernel's workgroups over the chunk -- the one place that knows the groups per block and the round-up to 8 blocks.
+struct BallChunks {
+    sicp_ctx *c; int slot; const GridLevel &lv; const int64_t *d_rows; long n, chunk;
+    bool kept = false;
+    long qpad = 0;
+    const uint32_t *order = nullptr;
+    int reserve();
+    int enter(long lo, long cnt);
+    unsigned grid(long cnt) const;
+    const double *qx() const { return c->kq.p; }
+    const double *qy() const { return c->kq.p + qpad; }
+    const double *qz() const { return c->kq.p + 2 * qpad; }
+};
+// k_ball_count enqueued over the cnt candidates of the chunk W stands in: keep = count >= cap, cnt_out = min(count, cap) (at pos[q],
+// null: at q), *kept_total += the kept (null: not counted)
+int ball_count_enqueue(const BallChunks &W, const int64_t *pos, long cnt, double radius, unsigned cap, uint8_t *keep, uint32_t *cnt_out,
+                       unsigned long long *kept_total);
 
 struct Timed {
     sicp_ctx *c; EventPair ev; bool on;

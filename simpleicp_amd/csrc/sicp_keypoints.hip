@@ -4,7 +4,7 @@
 // chunk's ranked (chunk, k) lists.  Pass 1 (k_iss_saliency): a wave owns 64 consecutive points of the chunk; for each of them the
 // lanes load that point's list row, gather the coordinates and form the three means and the six centred sums by xor-butterflies --
 // the adjacent-pair tree of the contract --, lane p keeps point p's numbers; then all 64 lanes run jacobi3, each on its own point.
-// The salient points' rows are collected on the way (a ballot and one atomic per 64 points, as k_ol_compact collects a mask's).
+// The salient points' rows are collected on the way (wave_append: one atomic per 64 points, as k_ol_compact collects a mask's).
 // Pass 2 (k_iss_nms) searches only those rows, with k_n: one wave per salient row, lanes over the ranks, each reads its
 // neighbour's saliency, one ballot decides the row.  Integer atomics count the record; no floating-point atomic takes part.
 #include "sicp_host.h"
@@ -22,10 +22,7 @@ enum { KP_SALIENT = 0, KP_KEYPOINTS = 1, KP_SMALL = 2, KP_CLIP_S = 3, KP_CLIP_N 
 
 __device__ __forceinline__ double kp_first(double v)
 {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    return __longlong_as_double((long long)first_lane_u64((unsigned long long)__double_as_longlong(v)));
 }
 
 // The adjacent-pair tree over the terms of lanes 0 .. span-1 (span a power of two, the same in every lane; all 64 lanes call):
@@ -125,14 +122,8 @@ __global__ __launch_bounds__(KP_BLOCK) void k_iss_saliency(const double *__restr
         }
         n_small += (unsigned long long)__popcll((long long)__ballot(valid && small));
         n_clip += (unsigned long long)__popcll((long long)__ballot(valid && mine_clip));
-        const unsigned long long b = __ballot(salient);
-        if (b != 0ull) {
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(st + KP_SALIENT, (unsigned long long)__popcll((long long)b));
-            at = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(at >> 32)) << 32) |
-                 (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)at);
-            if (salient) rows[at + (unsigned long long)__popcll((long long)(b & ((1ull << lane) - 1ull)))] = i;
-        }
+        const unsigned long long at = wave_append(st + KP_SALIENT, salient);
+        if (salient) rows[at] = i;
     }
     if (lane == 0) {
         if (n_small) atomicAdd(st + KP_SMALL, n_small);

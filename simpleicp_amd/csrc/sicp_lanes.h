@@ -1,6 +1,6 @@
 // sicp_lanes.h -- register-speed cross-lane moves for wave64 on gfx950, and what every kernel builds from them (device code only):
 // lane_xor* (the exchange), the sums and the prefix sum of a wave, the minima of a wave or of a sub-wave group of lanes (gmin, and
-// lexmin: the lexicographic (d2, index) minimum every search ends with), block_sum_u32, and the grid barrier.
+// lexmin: the lexicographic (d2, index) minimum every search ends with), wave_append, block_sum_u32, and the grid barrier.
 //
 // __shfl* compiles to ds_bpermute (the LDS crossbar): ~250 cycles per step in a dependent chain.  A fixed
 // lane ^ J exchange needs no crossbar: DPP quad_perm for J = 1, 2; J = 4 = row_half_mirror (i^7) then quad
@@ -139,6 +139,26 @@ __device__ __forceinline__ unsigned wsum_u32(unsigned v)
     v += lane_xor32<2>(v);
     v += lane_xor32<1>(v);
     return v;
+}
+
+// the first active lane's 64-bit value, in every lane (two 32-bit reads)
+__device__ __forceinline__ unsigned long long first_lane_u64(unsigned long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// Wave-aggregated append to a list whose length is *cursor: the lanes with `set` get consecutive positions, in lane order, for one
+// atomic per wave; a lane without `set` gets a position that is not its own.  Called by all 64 lanes together (lane 0 adds).
+__device__ __forceinline__ unsigned long long wave_append(unsigned long long *cursor, bool set)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = __ballot(set);
+    if (b == 0ull) return 0ull;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(cursor, (unsigned long long)__popcll((long long)b));
+    return first_lane_u64(base) + (unsigned long long)__popcll((long long)(b & ((1ull << lane) - 1ull)));
 }
 
 // sum of v over a workgroup of WAVES waves (wave sums through LDS): thread 0 gets the total, the others their wave's sum.

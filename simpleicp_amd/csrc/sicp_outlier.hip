@@ -4,10 +4,10 @@
 // order) a chunk at a time, k_ol_mean turns a chunk's ranked (chunk, k) squared distances into d_i at the candidate's POSITION;
 // two trees over all positions (k_ol_partials / k_ol_fold: contract (E)'s adjacent-pair tree of one term, sicp_pairtree.h) give mean
 // and std, k_ol_verdict writes the bytes and counts them.
-// Radius filter: k_ball_count walks the grid rows of a candidate's ball with OL_GS lanes, counts d2 < r^2 and leaves at
+// Radius filter: k_ball_count walks the grid rows of a candidate's ball (ball_walk: sicp_ball_dev.h), counts d2 < r^2 and leaves at
 // min_points + 1.  Integer atomics count; no floating-point atomic takes part.
 #include "sicp_host.h"
-#include "sicp_grid_dev.h"
+#include "sicp_ball_dev.h"
 #include "sicp_pairtree.h"
 #include "../../include/simpleicp_hip_outlier.h"
 
@@ -15,7 +15,6 @@ namespace sicp {
 namespace {
 
 constexpr int OL_BLOCK = 256;
-constexpr int OL_GS = 16;                          // lanes per candidate of k_ball_count (k_grid_nn16's share of a wave; the group talks through ballots and ds_bpermute)
 constexpr int OL_MAX_BLOCKS = 4096;
 
 // st: [0] mean [1] std [2] threshold.  SQ false: term = d (non-candidates hold +0.0 there); true: (d - mean)^2 of the candidates
@@ -101,100 +100,39 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ol_verdict(const double *__restric
 __global__ __launch_bounds__(OL_BLOCK) void k_ol_compact(const uint8_t *__restrict__ mask, long n, int64_t *__restrict__ rows,
                                                          unsigned long long *__restrict__ cnt)
 {
-    const int lane = threadIdx.x & 63;
     const long stride = (long)gridDim.x * OL_BLOCK;
     const long rounds = (n + stride - 1) / stride;             // (every lane of a wave takes every round: the ballot is wave-wide)
     for (long r = 0; r < rounds; ++r) {
         const long e = r * stride + (long)blockIdx.x * OL_BLOCK + threadIdx.x;
         const bool set = e < n && mask[e] != 0;
-        const unsigned long long b = __ballot(set);
-        if (b == 0ull) continue;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(cnt, (unsigned long long)__popcll((long long)b));
-        base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32)) << 32) |
-               (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);      // (lane 0 is active: every lane is)
-        if (set) rows[base + (unsigned long long)__popcll((long long)(b & ((1ull << lane) - 1ull)))] = e;
+        const unsigned long long at = wave_append(cnt, set);
+        if (set) rows[at] = e;
     }
 }
 
 // ---- the radius filter -----------------------------------------------------------------------------------------------------------
-// OL_GS lanes per candidate.  The ball's box of cells is walked row by row ((cy, cz) rows are contiguous in the cell order): the
-// lanes of a group fetch the record ranges of OL_GS rows at once, culled to the ball along x (row_lb2, row_x_clip: sicp_grid_dev.h),
-// then take the records of one row after the other, two per lane and step.  A candidate leaves as soon as its count reaches cap.
-// pos: where candidate q's results go (null: q); order: the candidates in cell order (the grid is a multiple of 8 blocks then).
-__global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restrict__ qx, const double *__restrict__ qy,
-                                                         const double *__restrict__ qz, const uint32_t *__restrict__ order,
-                                                         const int64_t *__restrict__ pos, const uint32_t *__restrict__ cell_start,
-                                                         const double4 *__restrict__ rec, long Q, GridGeom G, double r, double r2,
-                                                         unsigned cap, uint8_t *__restrict__ keep, uint32_t *__restrict__ cnt_out,
-                                                         unsigned long long *__restrict__ kept_total, unsigned long long *__restrict__ work)
+// BALL_GS lanes per candidate (ball_group_point, ball_walk: sicp_ball_dev.h).  A candidate leaves as soon as its count reaches cap.
+// pos: where candidate q's results go (null: q); order: the candidates in cell order.
+__global__ __launch_bounds__(BALL_BLOCK) void k_ball_count(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                           const double *__restrict__ qz, const uint32_t *__restrict__ order,
+                                                           const int64_t *__restrict__ pos, const uint32_t *__restrict__ cell_start,
+                                                           const double4 *__restrict__ rec, long Q, GridGeom G, double r, double r2,
+                                                           unsigned cap, uint8_t *__restrict__ keep, uint32_t *__restrict__ cnt_out,
+                                                           unsigned long long *__restrict__ kept_total, unsigned long long *__restrict__ work)
 {
-    constexpr int GPB = OL_BLOCK / OL_GS;
-    const int lane = threadIdx.x & 63, sub = lane & (OL_GS - 1), gbase = lane & ~(OL_GS - 1);
-    long blk = blockIdx.x;
-    if (order) {                                               // one contiguous eighth of the ordered candidates per XCD
-        const long per_xcd = gridDim.x >> 3;
-        blk = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    }
-    const long slot = blk * GPB + (threadIdx.x / OL_GS);
-    const bool active = slot < Q;
+    const int lane = threadIdx.x & 63, sub = lane & (BALL_GS - 1), gbase = lane & ~(BALL_GS - 1);
+    const long q = ball_group_point(order, Q);
+    const bool active = q >= 0;                                // (a group without a candidate still takes part in the wave's ballot below)
     bool kept = false;
-    unsigned long long n_cand = 0, n_rows = 0;
+    BallTally tally;
     if (active) {
-        const long q = order ? (long)order[slot] : slot;
-        const double ax = qx[q], ay = qy[q], az = qz[q];
-        const double c3[3] = {ax, ay, az};
-        // d2 < r2 implies |difference| < r along every axis up to the rounding of the difference itself: the ball that is culled with
-        // is wider by that, and by the rounding of c - rr
-        const double rr = r + (1e-9 * r + 1e-15 * (fabs(ax) + fabs(ay) + fabs(az) + r));
-        const double rr2 = rr * rr, etol = 1e-6 * G.h;
-        int lo[3], hi[3];
-        // ball_block's text (sicp_grid_dev.h) without `all`, written out: measured with the three search kernels that keep theirs (profiles/ballwalk)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double fl = floor((c3[a] - rr - G.mn[a]) * G.inv_h - 1e-6);
-            const double fh = floor((c3[a] + rr - G.mn[a]) * G.inv_h + 1e-6);
-            lo[a] = fl < 0.0 ? 0 : (fl > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fl);
-            hi[a] = fh < 0.0 ? 0 : (fh > (double)(G.dim[a] - 1) ? G.dim[a] - 1 : (int)fh);
-        }
-        const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
-        const int nrows = ny * nz;                             // (the host bounds the box: SICP_OUTLIER_MAX_BOX_CELLS)
         unsigned count = 0;
-        for (int rb = 0; rb < nrows && count < cap; rb += OL_GS) {
-            uint32_t b = 0, len = 0;
-            const int rw = rb + sub;
-            if (rw < nrows) {
-                const int oz = rw / ny, oy = rw - oz * ny;
-                const int cy = lo[1] + oy, cz = lo[2] + oz;
-                const long row = ((long)cz * G.dim[1] + cy) * G.dim[0];
-                const double rem = rr2 - row_lb2(G, cy, cz, ay, az, etol);
-                if (rem >= 0.0) {                              // (row_x_clip's own test, here too: the compiler's allocation, two VGPRs)
-                    int xl = lo[0], xh = hi[0];
-                    row_x_clip(G, ax, rem, etol, xl, xh);
-                    row_records(cell_start, row, xl, xh, b, len);
-                }
-            }
-            unsigned todo = (unsigned)(__ballot(len > 0) >> gbase) & ((1u << OL_GS) - 1u);
-            if (work) n_rows += len > 0 ? 1 : 0;
-            while (todo && count < cap) {
-                const int j = __ffs((int)todo) - 1;
-                todo &= todo - 1u;
-                const uint32_t bj = (uint32_t)__shfl((int)b, gbase + j), lj = (uint32_t)__shfl((int)len, gbase + j);
-                for (uint32_t o = 0; o < lj && count < cap; o += 2 * OL_GS) {
-                    const uint32_t i0 = o + (uint32_t)sub, i1 = i0 + OL_GS;
-                    const bool ok0 = i0 < lj, ok1 = i1 < lj;
-                    const double4 P0 = rec[ok0 ? bj + i0 : bj], P1 = rec[ok1 ? bj + i1 : bj];
-                    const double dx0 = P0.x - ax, dy0 = P0.y - ay, dz0 = P0.z - az;
-                    const double dx1 = P1.x - ax, dy1 = P1.y - ay, dz1 = P1.z - az;
-                    const bool h0 = ok0 && fma(dz0, dz0, fma(dy0, dy0, dx0 * dx0)) < r2;
-                    const bool h1 = ok1 && fma(dz1, dz1, fma(dy1, dy1, dx1 * dx1)) < r2;
-                    const unsigned m0 = (unsigned)(__ballot(h0) >> gbase) & ((1u << OL_GS) - 1u);
-                    const unsigned m1 = (unsigned)(__ballot(h1) >> gbase) & ((1u << OL_GS) - 1u);
-                    count += (unsigned)__popc(m0) + (unsigned)__popc(m1);
-                    if (work) n_cand += (ok0 ? 1 : 0) + (ok1 ? 1 : 0);
-                }
-            }
-        }
+        ball_walk(cell_start, rec, G, qx[q], qy[q], qz[q], r, r2, sub, gbase, [&](bool h0, uint32_t, bool h1, uint32_t) {
+            const unsigned m0 = (unsigned)(__ballot(h0) >> gbase) & ((1u << BALL_GS) - 1u);
+            const unsigned m1 = (unsigned)(__ballot(h1) >> gbase) & ((1u << BALL_GS) - 1u);
+            count += (unsigned)__popc(m0) + (unsigned)__popc(m1);
+            return count < cap ? cap - count : 0u;
+        }, work != nullptr, tally);
         if (count > cap) count = cap;
         kept = count >= cap;                                   // count_i > min_points
         if (sub == 0) {
@@ -206,7 +144,7 @@ __global__ __launch_bounds__(OL_BLOCK) void k_ball_count(const double *__restric
     const unsigned long long kb = __ballot(active && sub == 0 && kept);
     if (lane == 0 && kb && kept_total) atomicAdd(kept_total, (unsigned long long)__popcll((long long)kb));   // (null: the caller counts for itself)
     if (work) {
-        n_cand = wsum_u64(n_cand); n_rows = wsum_u64(n_rows);
+        const unsigned long long n_cand = wsum_u64(tally.cand), n_rows = wsum_u64(tally.rows);
         if (lane == 0) { atomicAdd(work, n_cand); atomicAdd(work + 1, n_rows); }
     }
 }
@@ -271,7 +209,7 @@ int ol_level(sicp_ctx *c, int slot, double radius, GridLevel *lv, int64_t ext[3]
 
 }  // namespace
 
-namespace sicp {
+namespace sicph {
 
 // The radius filter's walk, for the units that count the same balls (sicp_cluster.hip; declared in sicp_host.h).
 // ball_level: the grid level a ball of `radius` is walked on, refused where its box of cells exceeds SICP_OUTLIER_MAX_BOX_CELLS.
@@ -286,22 +224,46 @@ int ball_level(sicp_ctx *c, int slot, double radius, GridLevel *lv)
     return SICP_OK;
 }
 
-// ball_count_enqueue: k_ball_count over the cnt candidates whose columns lie at q, q + qpad, q + 2 qpad (order: null, or the
-// candidates in cell order; pos: null, or where each candidate's results go): keep = count >= cap, cnt_out = min(count, cap),
-// *kept_total += the kept (one atomic per wave that kept any, all on that one word; null: not counted).
-int ball_count_enqueue(sicp_ctx *c, const double *q, long qpad, const uint32_t *order, const int64_t *pos, const GridLevel &lv, long cnt,
-                       double radius, unsigned cap, uint8_t *keep, uint32_t *cnt_out, unsigned long long *kept_total)
+int BallChunks::reserve()
 {
-    unsigned g = cdiv(cnt, OL_BLOCK / OL_GS);
-    if (order) g = (g + 7u) & ~7u;
-    hipLaunchKernelGGL(k_ball_count, dim3(g), dim3(OL_BLOCK), 0, c->stream, q, q + qpad, q + 2 * qpad, order, pos, lv.cell_start,
-                       (const double4 *)lv.rec, cnt, lv.g, radius, radius * radius, cap, keep, cnt_out, kept_total,
+    return c->kq.reserve((size_t)3 * round_up(std::min(chunk, std::max<long>(n, 1)), QPAD));
+}
+
+int BallChunks::enter(long lo, long cnt)
+{
+    if (kept) return SICP_OK;
+    qpad = round_up(cnt, QPAD);
+    rows_gather(c, slot, d_rows, lo, cnt);
+    order = nullptr;
+    if (c->order_min_q > 0 && cnt >= c->order_min_q) {
+        CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, 2.0 * lv.g.h, 1L << 22, c->k_order));
+        order = c->k_order.p;
+    }
+    kept = n <= chunk;
+    return SICP_OK;
+}
+
+unsigned BallChunks::grid(long cnt) const
+{
+    const unsigned g = cdiv(cnt, BALL_BLOCK / BALL_GS);
+    return order ? (g + 7u) & ~7u : g;                             // (ball_group_point: an eighth of the ordered points per XCD)
+}
+
+// ball_count_enqueue: k_ball_count over the cnt candidates of the chunk W stands in (pos: null, or where each candidate's results
+// go): keep = count >= cap, cnt_out = min(count, cap), *kept_total += the kept (one atomic per wave that kept any, all on that one
+// word; null: not counted).
+int ball_count_enqueue(const BallChunks &W, const int64_t *pos, long cnt, double radius, unsigned cap, uint8_t *keep, uint32_t *cnt_out,
+                       unsigned long long *kept_total)
+{
+    sicp_ctx *c = W.c;
+    hipLaunchKernelGGL(k_ball_count, dim3(W.grid(cnt)), dim3(BALL_BLOCK), 0, c->stream, W.qx(), W.qy(), W.qz(), W.order, pos,
+                       W.lv.cell_start, (const double4 *)W.lv.rec, cnt, W.lv.g, radius, radius * radius, cap, keep, cnt_out, kept_total,
                        c->count_work ? c->match_work.p : nullptr);
     HIPCHK(hipGetLastError());
     return SICP_OK;
 }
 
-}  // namespace sicp
+}  // namespace sicph
 
 SICP_EXPORT int sicp_outlier_version(void) { return SICP_OUTLIER_VERSION; }
 
@@ -402,17 +364,12 @@ SICP_EXPORT int sicp_outlier_radius(sicp_ctx *c, int slot, const int64_t *rows, 
             HIPCHK(hipMemsetAsync(c->ol_cnt.p, 0, (size_t)N * sizeof(uint32_t), c->stream));
         }
         const unsigned cap = (unsigned)std::min<int64_t>(min_points, (1LL << 31) - 1) + 1u;      // counts stay below 2^31
-        const long chunk = c->outlier_chunk > 0 ? c->outlier_chunk : (1L << 22);
-        CHK(c->kq.reserve((size_t)3 * round_up(std::min(chunk, std::max<long>(K.count, 1)), QPAD)));
-        for (long lo = 0; lo < K.count; lo += chunk) {
-            const long cnt = std::min(chunk, K.count - lo), qpad = round_up(cnt, QPAD);
-            rows_gather(c, slot, K.d_rows, lo, cnt);
-            const uint32_t *order = nullptr;
-            if (c->order_min_q > 0 && cnt >= c->order_min_q) {
-                CHK(points_order_build(c, c->kq.p, c->kq.p + qpad, c->kq.p + 2 * qpad, cnt, 2.0 * lv.g.h, 1L << 22, c->k_order));
-                order = c->k_order.p;
-            }
-            CHK(ball_count_enqueue(c, c->kq.p, qpad, order, K.by_position ? K.d_rows + lo : nullptr, lv, cnt, radius, cap,
+        BallChunks W{c, slot, lv, K.d_rows, K.count, c->outlier_chunk > 0 ? c->outlier_chunk : (1L << 22)};
+        CHK(W.reserve());
+        for (long lo = 0; lo < K.count; lo += W.chunk) {
+            const long cnt = std::min(W.chunk, K.count - lo);
+            CHK(W.enter(lo, cnt));
+            CHK(ball_count_enqueue(W, K.by_position ? K.d_rows + lo : nullptr, cnt, radius, cap,
                                    K.by_position ? c->cand_keep.p : c->cand_keep.p + lo, K.by_position ? c->ol_cnt.p : c->ol_cnt.p + lo,
                                    c->cand_small.p + OL_KEPT));
         }

@@ -1,12 +1,16 @@
 """Every kernel that walks a ball over the dense cell table, on the inputs where the walk's shared geometry (sicp_grid_dev.h:
 ball_block, row_lb2, row_x_clip, row_records) can go wrong -- the clamps and the growth to the whole grid, the 1e-6 margins at cell
 faces, a row exactly one radius away, grids of one cell or one layer, ties -- against a NumPy brute force that evaluates the
-arithmetic contract exactly ((d2, index) ties to the lowest index).  Distances and indices must be EQUAL."""
+arithmetic contract exactly ((d2, index) ties to the lowest index).  Distances and indices must be EQUAL.  The two walks of
+sicp_cluster (k_ball_union, k_ball_border) run on the radius filter's clouds: labels, core bytes and record must be EQUAL to
+DBSCAN on the brute force's relation."""
 import os
 from fractions import Fraction
 
 import numpy as np
 import pytest
+
+import cluster_ref
 
 CASES = ["outside_near", "outside_far", "faces", "row_edge", "one_cell", "flat", "three_points", "lattice_ties"]
 # walker -> (environment of its context, entry, k).  k-NN walkers take min(k, n): the entry rejects k > n, so the clouds of 3 and of
@@ -28,7 +32,10 @@ WALKERS = {
     "knn_sweep4_k2": (dict(_GRID, SICP_KNN_SWEEP="1", SICP_KNN_GROUP="4", SICP_KNN_BATCH="3"), "knn", 2),
     "knn_sweep4_k17": (dict(_GRID, SICP_KNN_SWEEP="1", SICP_KNN_GROUP="4", SICP_KNN_BATCH="3"), "knn", 17),
     "ball_count": (_GRID, "radius", 0),
+    "cluster": (_GRID, "cluster", 0),
 }
+LATTICE = ("row_edge", "lattice_ties")
+LATTICE_WIDE = 0.3125              # a radius between the lattice's spacing (0.25: neighbours exactly on the sphere) and its face diagonal
 MATCH_KERNEL = {"nn_wave": "k_grid_nn", "nn16": "k_grid_nn16", "nn16f_near": "k_grid_nn16f", "nn16f_far": "k_grid_nn16f",
                 "nn16_g8": "k_grid_nn16", "nn16f_near_g8": "k_grid_nn16f", "nn16f_far_g8": "k_grid_nn16f"}
 
@@ -73,6 +80,35 @@ def brute_count(P, rows, r):
         edge = np.flatnonzero((D <= r2 * (1.0 + 1e-12)) & ~sure)
         out[j] = int(sure.sum()) + sum(1 for i in edge if _d2_contract(P[i], P[row]) < r2)
     return out
+
+
+def brute_relation(P, r):
+    """(n, n) bool: j is a neighbour of i iff the contract's d2 < r * r (i itself included), by brute_count's rule: plain NumPy
+    distances decide, the exact value only the pairs within 1e-12 relative of r * r (d2 is symmetric in every bit: each once)"""
+    r2, n = r * r, len(P)
+    A = np.zeros((n, n), bool)
+    for i in range(n):
+        D = _plain_d2(P, P[i])
+        A[i] = D < r2 * (1.0 - 1e-12)
+        for j in np.flatnonzero((D <= r2 * (1.0 + 1e-12)) & ~A[i]):
+            if j > i:
+                A[i, j] = A[j, i] = _d2_contract(P[j], P[i]) < r2
+    return A
+
+
+def cluster_runs(case, PQ, r):
+    """[(radius, relation, [min_points])] of the cluster walker: the radius filter's radius and, on the lattices, LATTICE_WIDE;
+    min_points 1 (the labels are the relation's components, ranked by lowest index), the 75th percentile of the counts, and at
+    LATTICE_WIDE 7 (an interior point has 7 neighbours, itself included: core; a face point 6: border; edges and corners: noise)"""
+    runs = []
+    for rad in (r, LATTICE_WIDE) if case in LATTICE else (r,):
+        key = ("relation", case, PQ.tobytes(), rad)
+        if key not in _REF:
+            _REF[key] = brute_relation(PQ, rad)
+        A = _REF[key]
+        mps = {1, max(1, int(np.percentile(A.sum(axis=1), 75)))} | ({7} if rad == LATTICE_WIDE else set())
+        runs.append((rad, A, sorted(mps)))
+    return runs
 
 
 # ---- the cases ------------------------------------------------------------------------------------------------------------------------
@@ -210,6 +246,37 @@ def test_brute_force_has_one_answer_per_case(case):
         assert (d2[:, 0] == d2[:, 1]).sum() >= 16 and (d2[:, 0] == d2[:, 7]).sum() >= 4
 
 
+def test_cluster_cases_reach_both_walks():
+    """No GPU: on the stand-in grid, the cluster walker's settings give k_ball_union and k_ball_border work in every case -- core
+    and border points everywhere, noise and more than one cluster in most -- and the lattices have their pairs exactly on the
+    sphere, which must not unite."""
+    with_noise = several = 0
+    for case in CASES:
+        P = _cloud(case)
+        PQ = np.concatenate((P, _queries(case, P, *_stand_in_grid(P))))
+        assert len(PQ) < 2000
+        for rad, A, mps in cluster_runs(case, PQ, _radius(case, P)):
+            assert np.array_equal(A, A.T) and A.diagonal().all()
+            for mp in mps:
+                ref = cluster_ref.cluster(PQ, rad, mp, A)
+                print(case, rad, mp, cluster_ref.record(ref))
+                if mp == 1:
+                    assert ref["core"].all() and ref["n_clusters"] >= 1
+            if case in LATTICE and rad == 0.25:
+                on_sphere = sum(int((_plain_d2(PQ, q) == rad * rad).sum()) for q in PQ)      # (ordered pairs: each from both ends)
+                one = cluster_ref.cluster(PQ, rad, 1, A)
+                assert on_sphere > 9000 and one["n_clusters"] > 1600, (on_sphere, one["n_clusters"])
+            elif case in LATTICE:
+                seven = cluster_ref.cluster(PQ, rad, 7, A)
+                assert seven["n_core"] > 0 and seven["n_border"] > 0 and seven["n_noise"] > 0, cluster_ref.record(seven)
+            else:
+                ref = cluster_ref.cluster(PQ, rad, mps[-1], A)       # (the 75th percentile)
+                assert ref["n_core"] >= 1 and ref["n_border"] >= 1, (case, cluster_ref.record(ref))
+                with_noise += ref["n_noise"] > 0
+                several += ref["n_clusters"] > 1
+    assert with_noise >= 4 and several >= 3, (with_noise, several)
+
+
 # ---- the walkers ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def contexts():
@@ -282,8 +349,25 @@ def test_ball_walk_equals_brute_force(contexts, walker, case):
         c.upload(_lib.MOV, PQ)
         while c.outlier_radius_cells(_lib.MOV, r)[3] > _lib.OUTLIER_MAX_BOX_CELLS:
             r *= 0.5                                               # (the entry bounds the box a ball may span)
-        keep, cnt, kept = c.outlier_radius(_lib.MOV, r, len(PQ), rows=rows)
-        want = _reference("count", case, PQ, rows, 0, r)
-        print(walker, case, "r", r, "count mismatches", int((cnt != want).sum()))
-        assert np.array_equal(cnt.astype(np.int64), want)
-        assert not keep.any() and kept == 0                        # (min_points = n: nobody has more than n neighbours)
+        if entry == "radius":
+            keep, cnt, kept = c.outlier_radius(_lib.MOV, r, len(PQ), rows=rows)
+            want = _reference("count", case, PQ, rows, 0, r)
+            print(walker, case, "r", r, "count mismatches", int((cnt != want).sum()))
+            assert np.array_equal(cnt.astype(np.int64), want)
+            assert not keep.any() and kept == 0                    # (min_points = n: nobody has more than n neighbours)
+            return
+        # the two walks of sicp_cluster over every point of the joined cloud
+        assert len(PQ) < 2000
+        for rad, A, mps in cluster_runs(case, PQ, r):
+            assert c.outlier_radius_cells(_lib.MOV, rad)[3] <= _lib.OUTLIER_MAX_BOX_CELLS
+            for mp in mps:
+                labels, core, st = c.cluster(_lib.MOV, rad, mp)
+                ref = cluster_ref.cluster(PQ, rad, mp, A)
+                print(walker, case, "r", rad, "min_points", mp, "label mismatches", int((labels != ref["labels"]).sum()),
+                      "core mismatches", int((core != ref["core"]).sum()), st.as_dict(), cluster_ref.record(ref))
+                assert np.array_equal(labels, ref["labels"])
+                assert np.array_equal(core, ref["core"])
+                assert st.as_dict() == cluster_ref.record(ref)
+                # ... and the walker agrees with the radius filter's walk on the same cloud
+                keep, _, kept = c.outlier_radius(_lib.MOV, rad, mp - 1)
+                assert np.array_equal(keep, core) and kept == ref["n_core"]
