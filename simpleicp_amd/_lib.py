@@ -112,6 +112,11 @@ PLANE_EXPORTS = ["sicp_plane_version", "sicp_plane_triplets", "sicp_plane_refit"
 PLANE_VERSION = 1
 PLANE_MAX_ROUNDS = 16
 
+# include/simpleicp_hip_farthest.h: farthest point sampling, the same kind of companion
+FARTHEST_EXPORTS = ["sicp_farthest_version", "sicp_farthest"]
+FARTHEST_VERSION = 1
+FARTHEST_ONE_LIMIT = 12288
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -198,6 +203,11 @@ class PlaneRefitStats(_Stats):
     _fields_ = [(name, C.c_int64) for name in ("n_planes", "n_void", "n_improved", "best", "best_inliers")]
 
 
+class FarthestStats(_Stats):
+    """struct sicp_farthest_stats (contract (S)): 32 bytes."""
+    _fields_ = [("n_points", C.c_int64), ("n_candidates", C.c_int64), ("n_selected", C.c_int64), ("cover_d2", C.c_double)]
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -271,6 +281,8 @@ FEATURES = {
     "plane": _Feature(PLANE_EXPORTS, "simpleicp_hip_plane.h", "plane", PLANE_VERSION, {
         "sicp_plane_triplets": [_vp, _vp, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, C.POINTER(PlaneStats)],
         "sicp_plane_refit": [_vp, _vp, _i64, _vp, _vp, _i64, _dbl, _cint, _vp, _vp, _vp, C.POINTER(PlaneRefitStats)]}),
+    "farthest": _Feature(FARTHEST_EXPORTS, "simpleicp_hip_farthest.h", "farthest-point", FARTHEST_VERSION, {
+        "sicp_farthest": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, C.POINTER(FarthestStats)]}),
 }
 
 _lib = None
@@ -457,6 +469,7 @@ consistency_version = partial(_feature_version, "consistency")
 keypoints_version = partial(_feature_version, "keypoints")
 cluster_version = partial(_feature_version, "cluster")
 plane_version = partial(_feature_version, "plane")
+farthest_version = partial(_feature_version, "farthest")
 
 
 def select_positions(m, Q):
@@ -918,6 +931,26 @@ class Context:
         self._chk(self._L.sicp_plane_refit(self._h, _ptr(x), int(n), _ptr(m), _ptr(p), int(b), float(max_distance), int(rounds), _ptr(out),
                                            _ptr(inl), _ptr(keep), C.byref(st)))
         return (out, inl, None if keep is None else keep[:n].view(np.bool_), st) if host else st
+
+    # -- farthest point sampling (contract (S)) --
+    def farthest(self, X, count, start=-1, mask=None, n=None, idx_ptr=None, d2_ptr=None, want_d2=True):
+        """sicp_farthest: `count` rows of X, one after the other, each the candidate row -- mask != 0 (None: all), coordinates
+        finite -- farthest from those already taken (contract (S)); start: the first pick, -1 the lowest candidate.  Host form: an
+        (n, 3) float64 array and an (n,) mask or None; returns ((count,) int64 picks, -1 from n_selected on, (count,) float64 squared
+        distances -- +0.0 from n_selected on; None without want_d2 --, FarthestStats).  Pointer form: X and mask (or None) are
+        addresses (ints) of host or device memory, n given; the picks are left at idx_ptr (count int64), the distances at d2_ptr
+        if given (count doubles), and the FarthestStats alone is returned."""
+        farthest_version()
+        st = FarthestStats()
+        host = idx_ptr is None
+        x, m, idx, d2 = X, mask, idx_ptr, d2_ptr
+        if host:
+            x, m = _cloud_rows(X, mask)
+            n = x.shape[0]
+            idx = np.empty(max(int(count), 1), np.int64)
+            d2 = np.empty(max(int(count), 1), np.float64) if want_d2 else None
+        self._chk(self._L.sicp_farthest(self._h, _ptr(x), _ptr(m), int(n), int(count), int(start), _ptr(idx), _ptr(d2), C.byref(st)))
+        return (idx, d2, st) if host else st
 
     # -- descriptor matching and RANSAC poses (contracts (M) and (R)) --
     def feature_match(self, query, target, nq=None, nt=None, dim=None, idx_ptr=None, d2_ptr=None, want_d2=True):

@@ -4,6 +4,7 @@
 // sicp_ctx_create fails with SICP_ERR_NO_DEVICE.
 #include "sicp_host.h"
 #include "../../include/simpleicp_hip_chain.h"
+#include "../../include/simpleicp_hip_farthest.h"
 
 namespace sicph {
 
@@ -260,6 +261,8 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_KEYPOINT_CHUNK")) c->keypoint_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_PLANE_SPAN")) c->plane_span = std::atol(e) > 0 ? std::atol(e) : 0;
+    if (const char *e = std::getenv("SICP_FARTHEST_ONE_MAX")) c->farthest_one_max = std::min<long>(std::max<long>(std::atol(e), 0), SICP_FARTHEST_ONE_LIMIT);
+    if (const char *e = std::getenv("SICP_FARTHEST_SPAN")) c->farthest_span = std::atol(e) > 0 ? round_up(std::atol(e), 64) : 0;
     if (const char *e = std::getenv("SICP_ROBUST")) c->robust_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
     if (const char *e = std::getenv("SICP_CONSISTENCY")) c->consistency_path = !std::strcmp(e, "sweeps") ? 1 : !std::strcmp(e, "one") ? 2 : 0;
     // SICP_SOLVE_TRACE: per-iteration traces on stderr -- any value: the tail's cycle counters; "host": the host's enqueue timings too;
@@ -318,6 +321,7 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->pf_in.release(); c->pf_state.release(); c->pf_part.release(); c->pf_part2.release(); c->pf_cnt.release();
     c->rb_state.release(); c->rb_scale.release();
     c->pl_plane.release(); c->pl_state.release(); c->pl_mask.release(); c->pl_keep.release();
+    c->fp_m.release(); c->fp_part.release(); c->fp_d2.release(); c->fp_mask.release(); c->fp_idx.release();
     c->cs_bits.release(); c->cs_front.release(); c->cs_work.release(); c->cs_core.release(); c->cs_state.release();
     if (c->h_batch_ring) (void)hipHostFree(c->h_batch_ring);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);

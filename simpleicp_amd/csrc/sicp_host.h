@@ -342,6 +342,15 @@ struct sicp_ctx {
     DevBuf<double> pl_plane, pl_state;
     DevBuf<uint8_t> pl_mask, pl_keep;
     long plane_span = 0;           // SICP_PLANE_SPAN: rows a workgroup of sicp_plane_triplets' scoring kernel takes (0: chosen per call)
+    // farthest point sampling (sicp_farthest.hip): every row's m_i and the workgroups' partial maxima of both parities (the stepped
+    // path), the staged mask, picks and distances (the rows are staged in gl_src)
+    DevBuf<double> fp_m, fp_part, fp_d2;
+    DevBuf<uint8_t> fp_mask;
+    DevBuf<int64_t> fp_idx;
+    long farthest_one_max = 12288; // SICP_FARTHEST_ONE_MAX: the largest n on the single-workgroup path, at most SICP_FARTHEST_ONE_LIMIT (0: never).
+                                   // The default is that limit: measured, 1 024 picks take 1.5 - 2.8 ms there at every n up to it and 3.9 - 4.3 ms
+                                   // stepped, which is its launches (profiles/farthest/)
+    long farthest_span = 0;        // SICP_FARTHEST_SPAN: rows a workgroup of the stepped path takes, whole waves of 64 (0: chosen per call)
     // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
     // the call's arrays
     DevBuf<unsigned long long> gl_key;

@@ -2,7 +2,8 @@
 the points worth describing (``keypoint_keep``; contract (I), DESIGN.md section 22, include/simpleicp_hip_keypoints.h) -- and DBSCAN
 labels, the points that belong together (``cluster_labels``; contract (U), DESIGN.md section 23, include/simpleicp_hip_cluster.h)
 -- and the dominant plane, what goes before the clusters on a scene with a ground (``segment_plane``, ``segment_planes``; contracts
-(P) and (Q), DESIGN.md section 24, include/simpleicp_hip_plane.h).
+(P) and (Q), DESIGN.md section 24, include/simpleicp_hip_plane.h) -- and farthest point sampling, exactly k points evenly spread
+in space (``farthest_points``; contract (S), DESIGN.md section 25, include/simpleicp_hip_farthest.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -369,9 +370,9 @@ def plane_triples(n, mask, hypotheses, seed):
     return np.ascontiguousarray(rows[rng.integers(0, len(rows), (hypotheses, 3), dtype=np.int32)], dtype=np.int32)
 
 
-def _plane_rows(X, mask):
-    """(on_device, the rows as the entries read them -- float64, contiguous --, the mask as contiguous bool or None, n, k):
-    the cloud and the mask of a plane call, checked; k is the number of candidate rows."""
+def _rows_and_mask(X, mask):
+    """(on_device, the rows as the entries read them -- float64, contiguous --, the mask as contiguous bool or None, n): the
+    cloud and the mask of a call over a cloud's rows, checked."""
     from .pointcloud import PointCloud
     from .tensors import _check_cloud, _is_device_tensor
     if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
@@ -397,6 +398,12 @@ def _plane_rows(X, mask):
             mask = np.ascontiguousarray(mask != 0)
     if n >= 2**31:
         raise ValueError("X must have fewer than 2^31 rows")
+    return on_device, rows, mask, n
+
+
+def _plane_rows(X, mask):
+    """_rows_and_mask, and k, the number of candidate rows: a plane needs three."""
+    on_device, rows, mask, n = _rows_and_mask(X, mask)
     k = n if mask is None else int(mask.sum())
     if k < 3:
         raise ValueError(f"a plane needs at least 3 candidate rows, not {k}")
@@ -499,3 +506,72 @@ def segment_planes(X, max_distance, *, min_inliers, max_planes=4, hypotheses=102
         labels[res.inliers] = j
         planes.append(res.plane)
     return labels, np.array(planes, dtype=np.float64).reshape(-1, 4)
+
+
+# ---- farthest point sampling (contract (S)) ----
+
+
+def farthest_arguments(count, start=None):
+    """(count, start as the C entry takes it: a row, or -1 for None), checked: TypeError / ValueError."""
+    c = _int_in("count", count, 1, 2**31 - 1)
+    s = -1 if start is None else _int_in("start", start, 0, 2**31 - 2)
+    return c, s
+
+
+def _farthest_context(who, ctx=None):
+    if dist.is_distributed():
+        from .icp import SimpleICPException
+        raise SimpleICPException(f"{who} does not run in a torch.distributed job: sample the clouds with one process first")
+    ctx = ctx or backend.get_context()
+    if not hasattr(ctx, "farthest"):
+        raise _lib.BackendError("this backend has no farthest point sampling")
+    dist.detach(ctx)
+    return ctx
+
+
+def _farthest(ctx, on_device, rows, mask, n, count, start, want_d2):
+    """farthest_points behind its checks: (picks in pick order, their squared distances or None, the record as a dict)."""
+    m = min(count, n)                               # (no more picks than rows: the result is not padded)
+    if on_device:
+        import torch
+        from .tensors import _wait_for_torch
+        idx = torch.empty(m, dtype=torch.int64, device=rows.device)
+        d2 = torch.empty(m, dtype=torch.float64, device=rows.device) if want_d2 else None
+        m8 = None if mask is None else mask.view(torch.uint8)
+        _wait_for_torch(ctx, rows.device)             # (the float64 copy and the mask's bytes come first)
+        st = ctx.farthest(rows.data_ptr(), m, start, mask=None if m8 is None else m8.data_ptr(), n=n, idx_ptr=idx.data_ptr(),
+                          d2_ptr=None if d2 is None else d2.data_ptr())
+    else:
+        idx, d2, st = ctx.farthest(rows, m, start, mask=mask, want_d2=want_d2)
+    st = _lib._stats_dict(st)
+    k = st["n_selected"]
+    return idx[:k], None if d2 is None else d2[:k], st
+
+
+def farthest_points(X, count, *, start=None, mask=None, return_distances=False, return_info=False):
+    """Farthest point sampling (contract (S)): ``count`` rows of X, evenly spread in space -- the first is
+    ``start`` (None: the lowest candidate row), every further one the candidate row farthest from all rows taken so far, the
+    lowest row among equally far ones.  Open3D's ``farthest_point_down_sample`` and pytorch3d's ``sample_farthest_points``,
+    reproducible bit for bit; ``X[farthest_points(X, 1000)]`` is the sample.  A sequence, not a set: the first k picks are the
+    picks for ``count=k``.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any strides;
+    float32 is widened exactly, the rows stay on the device; the stream rule is run_tensors').  ``mask`` (n,): only the rows it
+    marks are candidates; bool / integer array, or a bool / uint8 tensor on X's device.  A row with a coordinate that is not
+    finite is never a candidate.  Returns the picks in pick order, int64 -- numpy, or a tensor on X's device --, as many as were
+    taken: fewer than ``count`` where the candidates hold fewer distinct points (an exact duplicate of a taken row is never
+    taken) or X has fewer rows, none where ``start`` is no candidate.  ``return_distances=True``: also the (k,) float64 SQUARED
+    distance of every pick to the picks before it (+inf for the first) -- they never increase, entry t is the covering radius
+    of the first t picks.  ``return_info=True``: also the record, ``{n_points, n_candidates, n_selected, cover_d2}``."""
+    c, s = farthest_arguments(count, start)
+    for name, flag in (("return_distances", return_distances), ("return_info", return_info)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise TypeError(f"{name} must be True or False, not {flag!r}")
+    on_device, rows, mask, n = _rows_and_mask(X, mask)
+    if n == 0:
+        raise ValueError("X has no rows")
+    if s >= n:
+        raise ValueError(f"start must be a row of X, 0 .. {n - 1}, not {start!r}")
+    idx, d2, st = _farthest(_farthest_context("farthest_points"), on_device, rows, mask, n, c, s, bool(return_distances))
+    out = (idx,) + ((d2,) if return_distances else ()) + ((st,) if return_info else ())
+    return out[0] if len(out) == 1 else out

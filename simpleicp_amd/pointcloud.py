@@ -58,6 +58,7 @@ class PointCloud(pd.DataFrame):
     last_outlier_stats = None             # select_statistical_inliers leaves its statistics here (a dict)
     last_keypoint_stats = None            # select_keypoints leaves its record here (a dict)
     last_plane = None                     # select_plane leaves its PlaneResult here (inliers over the whole cloud)
+    last_farthest = None                  # select_farthest leaves (picks in pick order, squared distances, record) here
     last_cluster_stats = None             # select_largest_cluster / select_clusters leave their record here (a dict)
 
     def __init__(self, *args, **kwargs) -> None:
@@ -421,6 +422,28 @@ class PointCloud(pd.DataFrame):
             raise PointCloudException("no hypothesis is valid: the selected points give no plane")
         self.last_plane = res
         self._set_idx_selected(np.flatnonzero(selected & ~res.inliers if invert else res.inliers))
+
+    def select_farthest(self, count: int, start=None, _ctx=None) -> None:
+        """Keeps ``count`` of the selected points, evenly spread in space, and deselects the rest: farthest point sampling
+        (contract (S)) with the selection as ``farthest_points``' mask over the whole cloud.  ``start`` is a
+        row of the cloud, the first pick (None: the lowest selected row); a start that is not selected is refused.  Fewer than
+        ``count`` stay where the selected points hold fewer distinct positions.  The picks in pick order, their squared distances
+        and the record of the call are left in ``last_farthest``.  Not in the reference; what ``select_n_points`` is in the order
+        of the file, this is in space; composes with select_in_range, select_voxels and select_plane."""
+        from . import features
+        try:
+            c, s = features.farthest_arguments(count, start)
+        except (TypeError, ValueError) as e:
+            raise PointCloudException(str(e)) from None
+        selected = np.ascontiguousarray(self["selected"].to_numpy(), dtype=bool)
+        if s >= self._num_points or (s >= 0 and not selected[s]):
+            raise PointCloudException(f"start must be a selected point of the cloud, not {start!r}")
+        if not selected.any():
+            return
+        on_device, rows, mask, n = features._rows_and_mask(self, selected)
+        idx, d2, st = features._farthest(features._farthest_context("select_farthest", _ctx), on_device, rows, mask, n, c, s, True)
+        self.last_farthest = (idx, d2, st)
+        self._set_idx_selected(idx)
 
     def fpfh(self, neighbors: int = 32, radius=None) -> np.ndarray:
         """The (n, 33) float32 FPFH descriptors of ALL points (contract (F)): ``fpfh_features(self,
