@@ -117,6 +117,10 @@ FARTHEST_EXPORTS = ["sicp_farthest_version", "sicp_farthest"]
 FARTHEST_VERSION = 1
 FARTHEST_ONE_LIMIT = 12288
 
+# include/simpleicp_hip_orient.h: normals oriented consistently along a spanning forest of the k-NN graph, the same kind of companion
+ORIENT_EXPORTS = ["sicp_orient_version", "sicp_orient"]
+ORIENT_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -208,6 +212,12 @@ class FarthestStats(_Stats):
     _fields_ = [("n_points", C.c_int64), ("n_candidates", C.c_int64), ("n_selected", C.c_int64), ("cover_d2", C.c_double)]
 
 
+class OrientStats(_Stats):
+    """struct sicp_orient_stats (contract (H)): 56 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_void", "n_components", "n_forest_edges", "n_flipped", "n_components_voted",
+                                                "rounds")]
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -283,6 +293,8 @@ FEATURES = {
         "sicp_plane_refit": [_vp, _vp, _i64, _vp, _vp, _i64, _dbl, _cint, _vp, _vp, _vp, C.POINTER(PlaneRefitStats)]}),
     "farthest": _Feature(FARTHEST_EXPORTS, "simpleicp_hip_farthest.h", "farthest-point", FARTHEST_VERSION, {
         "sicp_farthest": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, C.POINTER(FarthestStats)]}),
+    "orient": _Feature(ORIENT_EXPORTS, "simpleicp_hip_orient.h", "normal-orientation", ORIENT_VERSION, {
+        "sicp_orient": [_vp, _cint, _vp, _cint, _vp, _cint, _vp, _vp, C.POINTER(OrientStats)]}),
 }
 
 _lib = None
@@ -470,6 +482,7 @@ keypoints_version = partial(_feature_version, "keypoints")
 cluster_version = partial(_feature_version, "cluster")
 plane_version = partial(_feature_version, "plane")
 farthest_version = partial(_feature_version, "farthest")
+orient_version = partial(_feature_version, "orient")
 
 
 def select_positions(m, Q):
@@ -883,6 +896,31 @@ class Context:
         labels, core = (np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.uint8)) if host else (labels_ptr, core_ptr)
         self._chk(self._L.sicp_cluster(self._h, slot, float(radius), int(min_points), _ptr(labels), _ptr(core), C.byref(st)))
         return (labels[:n], core[:n].view(np.bool_), st) if host else st
+
+    # -- consistent normal orientation (contract (H)) --
+    def orient(self, slot, normals, k, reference=None, away=False, normals_ptr=None, flipped_ptr=None, want_flipped=True):
+        """sicp_orient: the normals of the slot's points, every component of the k-NN graph given one sign -- neighbouring normals
+        agree along the minimum spanning forest under (larger |dot| first, then the smaller indices), the lowest index of a component
+        keeps its sign; reference (three floats): a component is turned as a whole towards it (away: away from it) by the majority
+        of its points.  normals: (n, 3) float32, a numpy array or a device tensor.  Returns ((n, 3) float32 normals, (n,) bool
+        flipped or None, OrientStats); with normals_ptr (host or device memory, n * 3 floats; it may be the normals' own address)
+        the result is left there, the flipped bytes at flipped_ptr if given (n bytes), and the OrientStats alone is returned."""
+        orient_version()
+        n = self.size(slot)
+        if isinstance(normals, np.ndarray) or not hasattr(normals, "data_ptr"):
+            normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if tuple(normals.shape) != (n, 3):
+            raise ValueError("normals must have shape (n, 3), one row per point of the slot")
+        ref = None if reference is None else _f64(reference).reshape(3)
+        st = OrientStats()
+        host = normals_ptr is None
+        out, flipped = normals_ptr, flipped_ptr
+        if host:
+            out = np.empty((n, 3), np.float32)
+            flipped = np.empty(max(n, 1), np.uint8) if want_flipped else None
+        self._chk(self._L.sicp_orient(self._h, slot, _ptr(normals), int(k), _ptr(ref), 1 if away else 0, _ptr(out), _ptr(flipped),
+                                      C.byref(st)))
+        return (out, None if flipped is None else flipped[:n].view(np.bool_), st) if host else st
 
     # -- planes of a cloud (contracts (P) and (Q)) --
     def plane_triplets(self, X, triples, max_distance, mask=None, n=None, h=None, planes_ptr=None, inliers_ptr=None, want_planes=True):

@@ -258,6 +258,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_OUTLIER_CHUNK")) c->outlier_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_CLUSTER_CHUNK")) c->cluster_chunk = std::atol(e) > 0 ? std::atol(e) : (1L << 22);
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_ORIENT_CHUNK")) c->orient_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_KEYPOINT_CHUNK")) c->keypoint_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_PLANE_SPAN")) c->plane_span = std::atol(e) > 0 ? std::atol(e) : 0;
@@ -314,6 +315,8 @@ SICP_EXPORT int sicp_ctx_destroy(sicp_ctx *c)
     c->ev_part.release(); c->ev_out.release(); c->ev_cnt.release();
     c->ol_d.release(); c->ol_part.release(); c->ol_cnt.release();
     c->fp_nrm.release(); c->fp_out.release(); c->fp_cnt.release();
+    c->or_nbr.release(); c->or_nrm.release(); c->or_out.release(); c->or_comp.release(); c->or_par.release();
+    c->or_bestc.release(); c->or_beste.release(); c->or_flip.release();
     c->kp_sal.release(); c->kp_eig.release();
     c->cl_parent.release(); c->cl_root.release(); c->cl_rank.release(); c->cl_size.release(); c->cl_labels.release();
     c->gl_key.release(); c->gl_q.release(); c->gl_t.release(); c->gl_d2.release(); c->gl_idx.release(); c->gl_tri.release();

@@ -351,6 +351,15 @@ struct sicp_ctx {
                                    // The default is that limit: measured, 1 024 picks take 1.5 - 2.8 ms there at every n up to it and 3.9 - 4.3 ms
                                    // stepped, which is its launches (profiles/farthest/)
     long farthest_span = 0;        // SICP_FARTHEST_SPAN: rows a workgroup of the stepped path takes, whole waves of 64 (0: chosen per call)
+    // consistent normal orientation (sicp_orient.hip): the k-NN lists as an (k, n) table, the normals as they came, the staging
+    // buffers of the outputs, every point's root and sign, the union words of the roots, a component's offers (8 bytes of c, 8 of
+    // the edge; behind the rounds its votes and its anchor)
+    DevBuf<int32_t> or_nbr;
+    DevBuf<float> or_nrm, or_out;
+    DevBuf<uint32_t> or_comp, or_par;
+    DevBuf<unsigned long long> or_bestc, or_beste;
+    DevBuf<uint8_t> or_flip;
+    long orient_chunk = 0;         // SICP_ORIENT_CHUNK: points per search of sicp_orient (0: chosen per call)
     // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
     // the call's arrays
     DevBuf<unsigned long long> gl_key;

@@ -3,7 +3,9 @@ the points worth describing (``keypoint_keep``; contract (I), DESIGN.md section 
 labels, the points that belong together (``cluster_labels``; contract (U), DESIGN.md section 23, include/simpleicp_hip_cluster.h)
 -- and the dominant plane, what goes before the clusters on a scene with a ground (``segment_plane``, ``segment_planes``; contracts
 (P) and (Q), DESIGN.md section 24, include/simpleicp_hip_plane.h) -- and farthest point sampling, exactly k points evenly spread
-in space (``farthest_points``; contract (S), DESIGN.md section 25, include/simpleicp_hip_farthest.h).
+in space (``farthest_points``; contract (S), DESIGN.md section 25, include/simpleicp_hip_farthest.h) -- and normals oriented
+consistently, what the descriptor's signs stand on (``orient_normals``; contract (H), DESIGN.md section 26,
+include/simpleicp_hip_orient.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -575,3 +577,119 @@ def farthest_points(X, count, *, start=None, mask=None, return_distances=False, 
     idx, d2, st = _farthest(_farthest_context("farthest_points"), on_device, rows, mask, n, c, s, bool(return_distances))
     out = (idx,) + ((d2,) if return_distances else ()) + ((st,) if return_info else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- consistent normal orientation (contract (H)) ----
+
+_NO_ORIENT = dict(n_points=0, n_void=0, n_components=0, n_forest_edges=0, n_flipped=0, n_components_voted=0, rounds=0)
+
+
+def _count_of(name, v, lo, hi):
+    if isinstance(v, (bool, float, str, bytes)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{name} must be an integer >= {lo} and <= {hi}, not {v!r}")
+    return int(v)
+
+
+def _point_of(name, v):
+    try:
+        r = np.asarray(v, dtype=np.float64)
+        ok = r.shape == (3,) and bool(np.isfinite(r).all())
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name} must be three finite numbers, not {v!r}")
+    return r
+
+
+def orient_arguments(neighbors=16, normal_neighbors=10, viewpoint=None, away_from=None):
+    """(k, normal_neighbors, the vote's reference as three floats or None, away), checked: ValueError naming the keyword."""
+    k = _count_of("neighbors", neighbors, 2, _lib.FPFH_MAX_K)
+    kn = _count_of("normal_neighbors", normal_neighbors, 2, 2**31 - 1)
+    if viewpoint is not None and away_from is not None:
+        raise ValueError("viewpoint and away_from exclude each other: a component is turned towards the one or away from the other")
+    if viewpoint is not None:
+        return k, kn, _point_of("viewpoint", viewpoint), False
+    if away_from is not None:
+        return k, kn, _point_of("away_from", away_from), True
+    return k, kn, None, False
+
+
+def orient_normals(X, normals=None, *, neighbors=16, normal_neighbors=10, viewpoint=None, away_from=None, return_flipped=False,
+                   return_info=False):
+    """The normals of X with consistent signs, (n, 3) float32 (contract (H)): neighbouring normals are made
+    to agree along the minimum spanning forest of the k-NN graph (``neighbors`` = k, the point itself included, 2 .. 128), the
+    edges ordered by how parallel their normals are -- Hoppe's propagation, Open3D's ``orient_normals_consistent_tangent_plane``,
+    reproducible bit for bit.  A normal is only ever negated, never changed.  In every connected component of the graph the
+    lowest-index point keeps its sign; with ``viewpoint`` (three numbers) a component is then turned as a whole so that most of
+    its normals look towards it, with ``away_from`` so that most look away from it (one vote per component, not per point: a
+    grazing angle is one vote among many); a tie leaves it.  The two exclude each other.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any
+    strides; ingest and stream rule are run_tensors').  A tensor gives a torch tensor on its device, anything else numpy.
+    ``normals``: (n, 3), one per point; None: a PointCloud's own nx / ny / nz columns if it has them, else the library's normals
+    from ``normal_neighbors`` points -- as ``fpfh_features`` chooses them.  A normal with a component that is not finite, or all
+    zero, stands alone and stays.  ``return_flipped``: also the (n,) bool mask of the negated normals; ``return_info``: also the
+    call's record as a dict (n_points, n_void, n_components -- void points included --, n_forest_edges, n_flipped,
+    n_components_voted -- the components the vote turned --, rounds).  The results come as (normals[, flipped][, info]).  The
+    library's fixed slot holds X afterwards."""
+    from .pointcloud import PointCloud
+    from .tensors import _is_device_tensor
+    k, kn, ref, away = orient_arguments(neighbors, normal_neighbors, viewpoint, away_from)
+    for name, v in (("return_flipped", return_flipped), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, not {v!r}")
+
+    def answer(out, flipped, info):
+        res = (out,) + ((flipped,) if return_flipped else ()) + ((info,) if return_info else ())
+        return res if len(res) > 1 else out
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        return answer(*_orient_on_device(X, normals, k, kn, ref, away))
+    X, n = _host_points(X)
+    own = None
+    if isinstance(X, PointCloud) and normals is None and all(c in X for c in ("nx", "ny", "nz")):
+        own = np.stack([np.asarray(X[c].to_numpy(), dtype=np.float32) for c in ("nx", "ny", "nz")], axis=1)
+    if normals is not None:
+        own = np.ascontiguousarray(normals, dtype=np.float32)
+        if own.shape != (n, 3):
+            raise ValueError(f"normals must have shape ({n}, 3), not {own.shape}")
+    if n == 0:
+        return answer(np.empty((0, 3), np.float32), np.zeros(0, bool), dict(_NO_ORIENT))
+    _check_counts(n, k, kn, own is None)
+    ctx = _host_opening("orient_normals", "orient the normals", X, ("orient", "normal orientation"))
+    if own is None:
+        own = ctx.estimate_normals(_lib.FIX, np.arange(n, dtype=np.int64), kn)[0]
+    out, flipped, st = ctx.orient(_lib.FIX, own, k, ref, away)
+    return answer(out, flipped, _lib._stats_dict(st))
+
+
+def _orient_on_device(X, normals, k, kn, ref, away):
+    import torch
+    from .tensors import _keep_opening, _wait_for_torch
+    if normals is not None and not isinstance(normals, (torch.Tensor, np.ndarray)):
+        raise ValueError("normals must be a torch.Tensor or a numpy array of shape (n, 3)")
+    if isinstance(X, torch.Tensor) and X.dim() == 2:
+        if normals is not None and tuple(normals.shape) != (X.shape[0], 3):
+            raise ValueError(f"normals must have shape ({X.shape[0]}, 3), not {tuple(normals.shape)}")
+        if X.shape[0] > 0:
+            _check_counts(X.shape[0], k, kn, normals is None)
+    ctx, n, _, flipped = _keep_opening("orient_normals", X, None, needs=("orient", "normal orientation"))
+    dev = X.device
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if ctx is None:
+        return out, flipped, dict(_NO_ORIENT)
+    if normals is None:               # the library's normals of all points, left in device memory: they are oriented in place
+        sel = torch.arange(n, dtype=torch.int64, device=dev)
+        pl = torch.empty(n, dtype=torch.float32, device=dev)
+        nv = out
+    elif isinstance(normals, torch.Tensor):
+        if normals.device != dev:
+            raise ValueError(f"normals is on {normals.device}, X on {dev}")
+        nv = normals.to(torch.float32).contiguous()
+    else:
+        nv = torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32)).to(dev)
+    # what torch queued for this call on its current stream (the index vector, the normals' copy) comes before the library reads it
+    _wait_for_torch(ctx, dev)
+    if normals is None:
+        ctx.estimate_normals_into(_lib.FIX, sel.data_ptr(), n, kn, nv.data_ptr(), pl.data_ptr())
+    st = ctx.orient(_lib.FIX, nv, k, ref, away, normals_ptr=out.data_ptr(), flipped_ptr=flipped.data_ptr())
+    return out, flipped.view(torch.bool), _lib._stats_dict(st)

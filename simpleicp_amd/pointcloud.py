@@ -58,6 +58,7 @@ class PointCloud(pd.DataFrame):
     last_outlier_stats = None             # select_statistical_inliers leaves its statistics here (a dict)
     last_keypoint_stats = None            # select_keypoints leaves its record here (a dict)
     last_plane = None                     # select_plane leaves its PlaneResult here (inliers over the whole cloud)
+    last_orient_stats = None              # orient_normals leaves its record here (a dict)
     last_farthest = None                  # select_farthest leaves (picks in pick order, squared distances, record) here
     last_cluster_stats = None             # select_largest_cluster / select_clusters leave their record here (a dict)
 
@@ -451,6 +452,22 @@ class PointCloud(pd.DataFrame):
         has no pairs of its own: its row holds its neighbours' share alone), the library's normals otherwise.  Not in the reference."""
         from .features import fpfh_features
         return fpfh_features(self, neighbors=neighbors, radius=radius)
+
+    def orient_normals(self, neighbors: int = 16, viewpoint=None, away_from=None) -> None:
+        """Rewrites the nx / ny / nz columns with consistent signs (contract (H)): ``orient_normals(self,
+        neighbors=..., viewpoint=..., away_from=...)`` over ALL points with the cloud's own normals -- a point without one stands
+        alone and stays as it is.  Raises where the cloud has no normals.  The record of the call is left in
+        ``last_orient_stats``.  Not in the reference."""
+        from . import features
+        if not all(c in self for c in ("nx", "ny", "nz")):
+            raise PointCloudException("orient_normals needs the normals of the cloud: call estimate_normals first")
+        try:
+            out, info = features.orient_normals(self, neighbors=neighbors, viewpoint=viewpoint, away_from=away_from, return_info=True)
+        except ValueError as e:
+            raise PointCloudException(str(e)) from None
+        for j, c in enumerate(("nx", "ny", "nz")):
+            self[c] = out[:, j].astype(self[c].to_numpy().dtype, copy=False)
+        self.last_orient_stats = info
 
     # ---- attributes (pointcloud.py:173-203) ---------------------------------------------
     def estimate_normals(self, neighbors: int, _ctx=None, _uploaded=False, _sel=None) -> None:

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib, backend, dist
 from ._lib import _stats_dict
-from .features import _int_in, fpfh_features, keypoint_arguments, keypoint_keep
+from .features import _int_in, fpfh_features, keypoint_arguments, keypoint_keep, orient_arguments, orient_normals
 from .tensors import _is_device_tensor, _wait_for_torch
 
 
@@ -39,14 +39,17 @@ class GlobalResult:
     record of the refit the candidates went through (n_poses, n_void, n_improved, best, best_inliers -- ``best`` a position among
     the unrefined candidates), None without one; ``n_consistent``: the matches the pruning left for the estimator
     (``register_global(..., prune=...)`` only, None without it; ``n_matches`` stays the count before it); ``n_keypoints``: the
-    ``(fixed, movable)`` numbers of keypoints the chain ran on (``register_global(..., keypoints=...)`` only, None without it)."""
+    ``(fixed, movable)`` numbers of keypoints the chain ran on (``register_global(..., keypoints=...)`` only, None without it);
+    ``n_components``: the ``(fixed, movable)`` numbers of components the normals were oriented in
+    (``register_global(..., orient=...)`` only, None without it)."""
 
-    def __init__(self, candidates, stats, n_matches=None, refined=None, n_consistent=None, n_keypoints=None):
+    def __init__(self, candidates, stats, n_matches=None, refined=None, n_consistent=None, n_keypoints=None, n_components=None):
         self.candidates = list(candidates)
         self.stats = dict(stats)
         self.n_matches = n_matches
         self.n_consistent = n_consistent
         self.n_keypoints = n_keypoints
+        self.n_components = n_components
         self.refined = None if refined is None else dict(refined)
         self.H, self.inliers, self.index = self.candidates[0] if self.candidates else (None, -1, -1)
 
@@ -486,6 +489,20 @@ def consistent_matches(src, dst, *, tolerance, min_length=0.0):
     return _consistency(_open_rows("consistent_matches", src, dst, "match_consistency", "match consistency", _consistency_rows), t, l)
 
 
+def _oriented_fpfh(X, neighbors, normal_neighbors, viewpoint, orient):
+    """(the descriptors of X over its estimated normals sent through orient_normals, the number of components): the vote goes
+    towards the viewpoint, or away from the centre of the bounding box."""
+    if viewpoint is not None:
+        vote = dict(viewpoint=viewpoint)
+    elif _is_torch(X):
+        vote = dict(away_from=((X.min(dim=0).values.double() + X.max(dim=0).values.double()) * 0.5).cpu().numpy())
+    else:
+        P = np.asarray(X, dtype=np.float64)
+        vote = dict(away_from=(P.min(axis=0) + P.max(axis=0)) * 0.5)
+    normals, info = orient_normals(X, normal_neighbors=normal_neighbors, return_info=True, **orient, **vote)
+    return fpfh_features(X, normals, neighbors=neighbors), info["n_components"]
+
+
 def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighbors=10, viewpoint_fixed=None, viewpoint_movable=None,
                     mutual=True, **ransac_kwargs):
     """A coarse pose of ``movable`` onto ``fixed`` without an initial guess -- in the direction of ``run()``'s H --: the FPFH
@@ -513,8 +530,26 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     ``n_keypoints = (fixed, movable)`` is their number, fewer than three on a side give the result without a pose, and ``index``
     (and ``triples``) are rows of the keypoint sets (of their matched, of their pruned rows), not of the clouds.
 
+    ``orient=`` (default None: nothing changes, bit for bit), under either method: an int k, or a dict of ``orient_normals``'
+    keywords (``neighbors``).  Each cloud's estimated normals go through ``orient_normals`` before the descriptors.  With
+    ``viewpoint_fixed`` / ``viewpoint_movable`` the viewpoint becomes the VOTE's reference -- every component is turned towards it
+    as a whole -- and ``fpfh_features`` gets no viewpoint; without one the vote is away from the centre of the cloud's bounding
+    box, ``(min + max) * 0.5``: exact and independent of the order of the points, so the chain stays reproducible bit for bit.
+    That centre is a convention, not physics: it is right for a closed surface seen from outside and only consistent elsewhere.
+    ``n_components = (fixed, movable)`` reports the components; more than one means signs that no neighbourhood relates.
+
     Returns ``ransac_pose``'s GlobalResult with ``n_matches`` set; fewer than three matches give a result without a pose.
     ICP stays the caller's: ``run_batch`` over ``candidates`` with ``evaluate_distance=``."""
+    orient = ransac_kwargs.pop("orient", None)
+    if orient is not None:
+        if isinstance(orient, dict):
+            if set(orient) - {"neighbors"}:
+                raise TypeError(f"orient= takes orient_normals' keyword neighbors, not {sorted(set(orient) - {'neighbors'})[0]!r}")
+        elif isinstance(orient, (bool, float, str, bytes)) or not isinstance(orient, (int, np.integer)):
+            raise TypeError(f"orient must be None, an int or a dict of orient_normals' keywords, not {orient!r}")
+        else:
+            orient = dict(neighbors=int(orient))
+        orient_arguments(normal_neighbors=normal_neighbors, **orient)
     keypoints = ransac_kwargs.pop("keypoints", None)
     if keypoints is not None:
         if keypoints is True:
@@ -551,8 +586,14 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
     if _is_torch(fixed) != _is_torch(movable):
         raise TypeError("fixed and movable must both be numpy arrays or both be CUDA torch tensors")
     _refuse_distributed("register_global")
-    f_fix = fpfh_features(fixed, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_fixed)
-    f_mov = fpfh_features(movable, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_movable)
+    n_components = None
+    if orient is None:
+        f_fix = fpfh_features(fixed, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_fixed)
+        f_mov = fpfh_features(movable, neighbors=neighbors, normal_neighbors=normal_neighbors, viewpoint=viewpoint_movable)
+    else:
+        f_fix, c_fix = _oriented_fpfh(fixed, neighbors, normal_neighbors, viewpoint_fixed, orient)
+        f_mov, c_mov = _oriented_fpfh(movable, neighbors, normal_neighbors, viewpoint_movable, orient)
+        n_components = (c_fix, c_mov)
     none = dict(n_poses=0, n_void=0, best=-1, best_inliers=-1) if robust else \
         dict(n_hypotheses=0, n_void=0, n_pruned=0, best=-1, best_inliers=-1)
     n_keypoints = None
@@ -563,13 +604,13 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
         k_fix, k_mov = keypoint_keep(fixed, **keypoints), keypoint_keep(movable, **keypoints)
         n_keypoints = (int(k_fix.sum()), int(k_mov.sum()))
         if min(n_keypoints) < 3:
-            return GlobalResult([], none, 0, n_keypoints=n_keypoints)
+            return GlobalResult([], none, 0, n_keypoints=n_keypoints, n_components=n_components)
         fixed, movable, f_fix, f_mov = fixed[k_fix], movable[k_mov], f_fix[k_fix], f_mov[k_mov]
     idx = match_features(f_mov, f_fix, mutual=bool(mutual))
     keep = idx >= 0
     n_matches = int(keep.sum())
     if n_matches < 3:
-        return GlobalResult([], none, n_matches, n_keypoints=n_keypoints)
+        return GlobalResult([], none, n_matches, n_keypoints=n_keypoints, n_components=n_components)
     if not _is_torch(movable):
         fixed, movable = np.asarray(fixed, dtype=np.float64), np.asarray(movable, dtype=np.float64)
     src, dst, n_consistent = movable[keep], fixed[idx[keep]], None
@@ -579,13 +620,13 @@ def register_global(fixed, movable, *, max_distance, neighbors=32, normal_neighb
         kept = _consistency(rows, *prune).keep
         src, dst, n_consistent = rows.S[kept], rows.D[kept], int(kept.sum())
         if n_consistent < 3:
-            return GlobalResult([], none, n_matches, n_consistent=n_consistent, n_keypoints=n_keypoints)
+            return GlobalResult([], none, n_matches, n_consistent=n_consistent, n_keypoints=n_keypoints, n_components=n_components)
     if robust:
         # the matched rows through sicp_pose_robust from the identity while they are where they are
         rows = _open_rows("register_global", src, dst, "pose_robust", "robust pose fit")
         poses, inl, _, stats = _robust(rows, None, *fit)
         return GlobalResult([(_as_H(poses[0]), int(inl[0]), -1)] if inl[0] >= 0 else [], stats, n_matches, n_consistent=n_consistent,
-                            n_keypoints=n_keypoints)
+                            n_keypoints=n_keypoints, n_components=n_components)
     res = _ransac_pose(src, dst, max_distance, refine=refine, **ransac_kwargs)
-    res.n_matches, res.n_consistent, res.n_keypoints = n_matches, n_consistent, n_keypoints
+    res.n_matches, res.n_consistent, res.n_keypoints, res.n_components = n_matches, n_consistent, n_keypoints, n_components
     return res
