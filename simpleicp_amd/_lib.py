@@ -121,6 +121,10 @@ FARTHEST_ONE_LIMIT = 12288
 ORIENT_EXPORTS = ["sicp_orient_version", "sicp_orient"]
 ORIENT_VERSION = 1
 
+# include/simpleicp_hip_regions.h: smooth regions of a cloud, region growing over the normals, the same kind of companion
+REGIONS_EXPORTS = ["sicp_regions_version", "sicp_regions"]
+REGIONS_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -218,6 +222,12 @@ class OrientStats(_Stats):
                                                 "rounds")]
 
 
+class RegionsStats(_Stats):
+    """struct sicp_regions_stats (contract (J)): 72 bytes."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_void", "n_smooth", "n_border", "n_regions_all", "n_regions", "n_labelled",
+                                                "largest_label", "largest_size")]
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -295,6 +305,8 @@ FEATURES = {
         "sicp_farthest": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, C.POINTER(FarthestStats)]}),
     "orient": _Feature(ORIENT_EXPORTS, "simpleicp_hip_orient.h", "normal-orientation", ORIENT_VERSION, {
         "sicp_orient": [_vp, _cint, _vp, _cint, _vp, _cint, _vp, _vp, C.POINTER(OrientStats)]}),
+    "regions": _Feature(REGIONS_EXPORTS, "simpleicp_hip_regions.h", "smooth-region", REGIONS_VERSION, {
+        "sicp_regions": [_vp, _cint, _vp, _cint, _dbl, _dbl, _cint, _vp, _i64, _vp, C.POINTER(RegionsStats)]}),
 }
 
 _lib = None
@@ -483,6 +495,7 @@ cluster_version = partial(_feature_version, "cluster")
 plane_version = partial(_feature_version, "plane")
 farthest_version = partial(_feature_version, "farthest")
 orient_version = partial(_feature_version, "orient")
+regions_version = partial(_feature_version, "regions")
 
 
 def select_positions(m, Q):
@@ -921,6 +934,33 @@ class Context:
         self._chk(self._L.sicp_orient(self._h, slot, _ptr(normals), int(k), _ptr(ref), 1 if away else 0, _ptr(out), _ptr(flipped),
                                       C.byref(st)))
         return (out, None if flipped is None else flipped[:n].view(np.bool_), st) if host else st
+
+    # -- smooth regions (contract (J)) --
+    def regions(self, slot, normals, k, cos_min, radius=float("inf"), oriented=False, seeds=None, min_size=1, labels_ptr=None):
+        """sicp_regions: the smooth regions of the slot's points -- the connected components of the smooth points (a normal that
+        is not void, seeds[i] != 0) under the edges of the k-NN graph strictly within radius whose normals agree, |dot| >= cos_min
+        (oriented: dot >= cos_min); a point that is not smooth joins the region with the lowest root it has such an edge with;
+        regions of fewer than min_size members are dropped, the others numbered in the order of their lowest index; -1: no
+        region.  normals: (n, 3) float32, seeds: (n,) bytes or None -- numpy arrays or device tensors.  Returns ((n,) int32
+        labels, RegionsStats); with labels_ptr (host or device memory, n int32) the labels are left there and the RegionsStats
+        alone is returned."""
+        regions_version()
+        n = self.size(slot)
+        if isinstance(normals, np.ndarray) or not hasattr(normals, "data_ptr"):
+            normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if tuple(normals.shape) != (n, 3):
+            raise ValueError("normals must have shape (n, 3), one row per point of the slot")
+        if seeds is not None:
+            if isinstance(seeds, np.ndarray) or not hasattr(seeds, "data_ptr"):
+                seeds = np.ascontiguousarray(np.asarray(seeds) != 0).view(np.uint8)
+            if tuple(seeds.shape) != (n,):
+                raise ValueError("seeds must have shape (n,), one byte per point of the slot")
+        st = RegionsStats()
+        host = labels_ptr is None
+        labels = np.empty(max(n, 1), np.int32) if host else labels_ptr
+        self._chk(self._L.sicp_regions(self._h, slot, _ptr(normals), int(k), float(radius), float(cos_min), 1 if oriented else 0,
+                                       _ptr(seeds), int(min_size), _ptr(labels), C.byref(st)))
+        return (labels[:n], st) if host else st
 
     # -- planes of a cloud (contracts (P) and (Q)) --
     def plane_triplets(self, X, triples, max_distance, mask=None, n=None, h=None, planes_ptr=None, inliers_ptr=None, want_planes=True):

@@ -10,55 +10,17 @@
 // (parents only ever decrease) and uf_union's retry after a failed compare-and-swap (another lane's succeeded).  Integer atomics only.
 #include "sicp_host.h"
 #include "sicp_ball_dev.h"
+#include "sicp_union_dev.h"
 #include "../../include/simpleicp_hip_cluster.h"
 
 namespace sicp {
 namespace {
 
-constexpr int CL_BLOCK = 256;
 constexpr int CL_PER = 4;                          // consecutive points per thread of k_cl_flatten / k_cl_apply
 constexpr int CL_SPAN = CL_BLOCK * CL_PER;         // points per workgroup of the rank scan
 constexpr int CL_RUN = 16;                         // consecutive rows of 64 points per wave of k_cl_labels
 constexpr int CL_MAX_BLOCKS = 1024;
 constexpr uint32_t CL_NONE = 0xffffffffu;          // root of a point without a cluster
-
-// ---- the union-find over uint32 parent[n] ---------------------------------------------------------------------------------------
-// Every access while unions are in flight is an agent-scope relaxed atomic: the XCDs' L2s are not coherent, a plain load may be
-// stale.  (Staleness would not even break it -- an old value of parent[x] is still an ancestor of x, and the compare-and-swap is
-// decided where all of them meet -- but it would cost retries.)
-__device__ __forceinline__ uint32_t uf_load(uint32_t *parent, uint32_t x)
-{
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ bool uf_cas(uint32_t *parent, uint32_t x, uint32_t &expected, uint32_t desired)
-{
-    return __hip_atomic_compare_exchange_strong(parent + x, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the root of x; path halving on the way: parent[x] goes from x's parent to its grandparent -- an ancestor of x, nothing else is
-// ever written into a word that is not a root -- and a halving that loses its race is skipped
-__device__ __forceinline__ uint32_t uf_find(uint32_t *parent, uint32_t x)
-{
-    uint32_t p = uf_load(parent, x);
-    while (p != x) {
-        const uint32_t gp = uf_load(parent, p);
-        if (gp != p) { uint32_t e = p; (void)uf_cas(parent, x, e, gp); }
-        x = p; p = gp;
-    }
-    return x;
-}
-// unites the sets of a and b and returns their root: the larger root is hooked under the smaller one, by a compare-and-swap that
-// expects it to be a root still; a failure means another lane hooked it first -- start again from where it hangs now
-__device__ __forceinline__ uint32_t uf_union(uint32_t *parent, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = uf_find(parent, a); b = uf_find(parent, b);
-        if (a == b) return a;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        uint32_t e = a;
-        if (uf_cas(parent, a, e, b)) return b;
-        a = e;
-    }
-}
 
 __global__ __launch_bounds__(CL_BLOCK) void k_cl_fill(uint32_t *__restrict__ parent, long n)
 {
@@ -138,28 +100,6 @@ __global__ __launch_bounds__(BALL_BLOCK) void k_ball_border(const double *__rest
     });
     best = gmin<BALL_GS>(best);
     if (sub == 0) root[i] = best;
-}
-
-// exclusive prefix sum of the nb block sums, in place, by one workgroup; *total = their sum (the number of clusters)
-__global__ __launch_bounds__(CL_BLOCK) void k_cl_scan_sums(uint32_t *__restrict__ sums, long nb, unsigned long long *__restrict__ total)
-{
-    __shared__ uint32_t wtot[CL_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t carry = 0;
-    for (long base = 0; base < nb; base += CL_BLOCK) {
-        const long e = base + threadIdx.x;
-        const uint32_t v = e < nb ? sums[e] : 0u;
-        const uint32_t inc = wscan_u32(v);
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < CL_BLOCK / 64; ++w) { before += w < wave ? wtot[w] : 0u; all += wtot[w]; }
-        if (e < nb) sums[e] = carry + before + inc - v;
-        carry += all;
-        __syncthreads();                                           // (wtot is written again)
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 // rank[i] of every root i: the number of roots below it -- its cluster's label; size[label] = 0 for k_cl_labels to add to

@@ -5,7 +5,8 @@ labels, the points that belong together (``cluster_labels``; contract (U), DESIG
 (P) and (Q), DESIGN.md section 24, include/simpleicp_hip_plane.h) -- and farthest point sampling, exactly k points evenly spread
 in space (``farthest_points``; contract (S), DESIGN.md section 25, include/simpleicp_hip_farthest.h) -- and normals oriented
 consistently, what the descriptor's signs stand on (``orient_normals``; contract (H), DESIGN.md section 26,
-include/simpleicp_hip_orient.h).
+include/simpleicp_hip_orient.h) -- and the smooth regions, every patch whose neighbouring normals agree (``smooth_regions``;
+contract (J), DESIGN.md section 27, include/simpleicp_hip_regions.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -693,3 +694,158 @@ def _orient_on_device(X, normals, k, kn, ref, away):
         ctx.estimate_normals_into(_lib.FIX, sel.data_ptr(), n, kn, nv.data_ptr(), pl.data_ptr())
     st = ctx.orient(_lib.FIX, nv, k, ref, away, normals_ptr=out.data_ptr(), flipped_ptr=flipped.data_ptr())
     return out, flipped.view(torch.bool), _lib._stats_dict(st)
+
+
+# ---- smooth regions (contract (J)) ----
+
+_NO_REGIONS = dict(n_points=0, n_void=0, n_smooth=0, n_border=0, n_regions_all=0, n_regions=0, n_labelled=0, largest_label=0,
+                   largest_size=0)
+
+
+def _number_of(name, v):
+    if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)) or math.isnan(float(v)):
+        raise ValueError(f"{name} must be a number, not {v!r}")
+    return float(v)
+
+
+def regions_arguments(neighbors=16, max_angle=5.0, cos_min=None, radius=None, min_planarity=None, min_size=1, oriented=False,
+                      normal_neighbors=10):
+    """(k, cos_min, radius as a float -- inf: none --, min_planarity or None, min_size, oriented, normal_neighbors), checked:
+    ValueError naming the keyword.  cos_min = math.cos(math.radians(max_angle)) unless it is given itself."""
+    if not isinstance(oriented, (bool, np.bool_)):
+        raise ValueError(f"oriented must be True or False, not {oriented!r}")
+    k = _count_of("neighbors", neighbors, 2, _lib.FPFH_MAX_K)
+    kn = _count_of("normal_neighbors", normal_neighbors, 2, 2**31 - 1)
+    if cos_min is not None:
+        if max_angle is not None and max_angle != 5.0:
+            raise ValueError("cos_min and max_angle exclude each other: the one is the cosine of the other")
+        cm, lo = _number_of("cos_min", cos_min), -1.0 if oriented else 0.0
+        if not lo <= cm <= 1.0:
+            raise ValueError(f"cos_min must be >= {lo:g} and <= 1, not {cos_min!r}")
+    else:
+        a, hi = _number_of("max_angle", max_angle), 180.0 if oriented else 90.0
+        if not 0.0 < a <= hi:
+            raise ValueError(f"max_angle must be > 0 and <= {hi:g} degrees, not {max_angle!r}")
+        cm = math.cos(math.radians(a))
+    try:
+        r = _radius_of("radius", radius)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    mp = None
+    if min_planarity is not None:
+        mp = _number_of("min_planarity", min_planarity)
+    ms = _count_of("min_size", min_size, 1, 2**63 - 1)
+    return k, cm, r, mp, ms, bool(oriented), kn
+
+
+def smooth_regions(X, normals=None, *, neighbors=16, max_angle=5.0, cos_min=None, radius=None, seeds=None, min_planarity=None,
+                   min_size=1, oriented=False, normal_neighbors=10, return_info=False):
+    """The smooth regions of X as an int32 vector (n,) (contract (J)): region growing over the normals,
+    PCL's ``RegionGrowing``.  Two points are joined where one is among the other's ``neighbors`` nearest points (the point itself
+    included, 2 .. 128; with ``radius`` only those strictly closer) and their normals differ by at most ``max_angle`` degrees --
+    unoriented, |dot| >= cos(max_angle), unless ``oriented`` (then ``max_angle`` may go up to 180).  ``cos_min`` gives the cosine
+    itself instead of ``max_angle``.  Every patch of the surface, flat or curved, becomes one region and patches end where the
+    surface creases; regions are numbered 0, 1, 2, ... in the order of their lowest index, -1 is no region.  The result depends
+    on the inputs alone -- no queue order as in PCL.
+
+    ``seeds`` ((n,) bool): only these points pass a label on; a point that is no seed joins the region with the lowest root among
+    the seeds it agrees with and never connects two regions.  ``min_planarity=p`` with the library's own normals
+    (``normals=None``) makes ``seeds = planarity >= p`` (NaN: no seed): PCL's curvature threshold.  Regions of fewer than
+    ``min_size`` members get -1, the others are renumbered.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any
+    strides; ingest and stream rule are run_tensors').  A tensor gives a torch.int32 tensor on its device, anything else numpy;
+    a tensor's rows, normals and seeds never leave the device.  ``normals``: (n, 3), one per point; None: a PointCloud's own
+    nx / ny / nz columns if it has them, else the library's normals from ``normal_neighbors`` points.  A normal with a component
+    that is not finite, or all zero, belongs to no region.  ``return_info``: also the call's record as a dict (n_points, n_void,
+    n_smooth, n_border, n_regions_all, n_regions, n_labelled, largest_label, largest_size -- no region: -1 and 0 -- and cos_min).
+    The library's fixed slot holds X afterwards."""
+    from .pointcloud import PointCloud
+    from .tensors import _is_device_tensor
+    k, cm, r, mp, ms, oriented, kn = regions_arguments(neighbors, max_angle, cos_min, radius, min_planarity, min_size, oriented,
+                                                       normal_neighbors)
+    if not isinstance(return_info, (bool, np.bool_)):
+        raise ValueError(f"return_info must be True or False, not {return_info!r}")
+    if mp is not None and seeds is not None:
+        raise ValueError("min_planarity and seeds exclude each other: min_planarity makes the seeds")
+    if mp is not None and normals is not None:
+        raise ValueError("min_planarity needs the library's own normals (normals=None): given normals come without a planarity")
+
+    def answer(labels, info):
+        return (labels, dict(info, cos_min=cm)) if return_info else labels
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        return answer(*_regions_on_device(X, normals, seeds, k, cm, r, mp, ms, oriented, kn))
+    X, n = _host_points(X)
+    own = None
+    if isinstance(X, PointCloud) and normals is None and mp is None and all(c in X for c in ("nx", "ny", "nz")):
+        own = np.stack([np.asarray(X[c].to_numpy(), dtype=np.float32) for c in ("nx", "ny", "nz")], axis=1)
+    if normals is not None:
+        own = np.ascontiguousarray(normals, dtype=np.float32)
+        if own.shape != (n, 3):
+            raise ValueError(f"normals must have shape ({n}, 3), not {own.shape}")
+    if seeds is not None:
+        seeds = np.ascontiguousarray(np.asarray(seeds) != 0)
+        if seeds.shape != (n,):
+            raise ValueError(f"seeds must have shape ({n},), not {seeds.shape}")
+    if n == 0:
+        return answer(np.zeros(0, np.int32), dict(_NO_REGIONS))
+    _check_counts(n, k, kn, own is None)
+    ctx = _host_opening("smooth_regions", "label the clouds", X, ("regions", "smooth regions"))
+    if own is None:
+        own, pl = ctx.estimate_normals(_lib.FIX, np.arange(n, dtype=np.int64), kn)
+        if mp is not None:
+            with np.errstate(invalid="ignore"):
+                seeds = pl.astype(np.float64) >= mp
+    labels, st = ctx.regions(_lib.FIX, own, k, cm, r, oriented, seeds, ms)
+    return answer(labels, _lib._stats_dict(st))
+
+
+def _regions_on_device(X, normals, seeds, k, cm, r, mp, ms, oriented, kn):
+    import torch
+    from .tensors import _keep_opening, _wait_for_torch
+    if normals is not None and not isinstance(normals, (torch.Tensor, np.ndarray)):
+        raise ValueError("normals must be a torch.Tensor or a numpy array of shape (n, 3)")
+    if seeds is not None and not isinstance(seeds, (torch.Tensor, np.ndarray)):
+        raise ValueError("seeds must be a torch.Tensor or a numpy array of shape (n,)")
+    if isinstance(X, torch.Tensor) and X.dim() == 2:
+        if normals is not None and tuple(normals.shape) != (X.shape[0], 3):
+            raise ValueError(f"normals must have shape ({X.shape[0]}, 3), not {tuple(normals.shape)}")
+        if seeds is not None and tuple(seeds.shape) != (X.shape[0],):
+            raise ValueError(f"seeds must have shape ({X.shape[0]},), not {tuple(seeds.shape)}")
+        if X.shape[0] > 0:
+            _check_counts(X.shape[0], k, kn, normals is None)
+    ctx, n, _, _ = _keep_opening("smooth_regions", X, None, needs=("regions", "smooth regions"))
+    dev = X.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    if ctx is None:
+        return labels, dict(_NO_REGIONS)
+    pl = None
+    if normals is None:               # the library's normals of all points, left in device memory
+        sel = torch.arange(n, dtype=torch.int64, device=dev)
+        nv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        pl = torch.empty(n, dtype=torch.float32, device=dev)
+    elif isinstance(normals, torch.Tensor):
+        if normals.device != dev:
+            raise ValueError(f"normals is on {normals.device}, X on {dev}")
+        nv = normals.to(torch.float32).contiguous()
+    else:
+        nv = torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32)).to(dev)
+    sd = None
+    if isinstance(seeds, torch.Tensor):
+        if seeds.device != dev:
+            raise ValueError(f"seeds is on {seeds.device}, X on {dev}")
+        sd = (seeds != 0).contiguous().view(torch.uint8)
+    elif seeds is not None:
+        sd = torch.from_numpy(np.ascontiguousarray(np.asarray(seeds) != 0).view(np.uint8)).to(dev)
+    # what torch queued for this call on its current stream (the index vector, the copies) comes before the library reads it
+    _wait_for_torch(ctx, dev)
+    if normals is None:
+        ctx.estimate_normals_into(_lib.FIX, sel.data_ptr(), n, kn, nv.data_ptr(), pl.data_ptr())
+        if mp is not None:
+            # the planarity was written on the library's stream: torch's waits for it, and the library's for the comparison
+            ext = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev)
+            torch.cuda.current_stream(dev).wait_stream(ext)
+            sd = (pl.to(torch.float64) >= mp).view(torch.uint8)
+            _wait_for_torch(ctx, dev)
+    st = ctx.regions(_lib.FIX, nv, k, cm, r, oriented, sd, ms, labels_ptr=labels.data_ptr())
+    return labels, _lib._stats_dict(st)

@@ -61,6 +61,7 @@ class PointCloud(pd.DataFrame):
     last_orient_stats = None              # orient_normals leaves its record here (a dict)
     last_farthest = None                  # select_farthest leaves (picks in pick order, squared distances, record) here
     last_cluster_stats = None             # select_largest_cluster / select_clusters leave their record here (a dict)
+    last_region_stats = None              # select_regions / select_largest_region leave their record here (a dict)
 
     def __init__(self, *args, **kwargs) -> None:
         kwargs.pop("remapping", None)     # accepted and ignored, like the reference (pointcloud.py:25)
@@ -393,6 +394,48 @@ class PointCloud(pd.DataFrame):
             return
         sizes = np.bincount(labels[labels >= 0], minlength=1)
         self._set_idx_selected(cur[(labels >= 0) & (sizes[np.maximum(labels, 0)] >= int(min_size))])
+
+    def _regions_selected(self, kw):
+        """(selected indices, their smooth-region labels as a cloud of their own) -- (indices, None) when nothing is selected;
+        the record is left in ``last_region_stats``."""
+        from . import features
+        unknown = set(kw) - {"max_angle", "neighbors", "min_size", "cos_min", "radius", "min_planarity", "oriented", "normal_neighbors"}
+        if unknown:
+            raise PointCloudException(f"select_regions takes no keyword {sorted(unknown)[0]!r}")
+        cur = self.idx_selected
+        own = all(c in self for c in ("nx", "ny", "nz"))
+        try:
+            features.regions_arguments(**kw)
+            if len(cur) == 0:
+                return cur, None
+            X = np.ascontiguousarray(np.stack([self[c].to_numpy()[cur] for c in ("x", "y", "z")], axis=1), dtype=np.float64)
+            N = None
+            if own and kw.get("min_planarity") is None:
+                N = np.stack([np.asarray(self[c].to_numpy()[cur], dtype=np.float32) for c in ("nx", "ny", "nz")], axis=1)
+            labels, info = features.smooth_regions(X, N, return_info=True, **kw)
+        except ValueError as e:
+            raise PointCloudException(str(e)) from None
+        self.last_region_stats = info
+        return cur, np.asarray(labels)
+
+    def select_regions(self, max_angle: float = 5.0, neighbors: int = 16, min_size: int = 1, **kw) -> None:
+        """Keeps, among the selected points, those in a smooth region (of the SELECTED points taken as a cloud of their own) with
+        at least ``min_size`` members, and deselects the rest -- what no region takes always goes (contract (J), DESIGN.md section
+        27; the arguments and the keywords ``cos_min``, ``radius``, ``min_planarity``, ``oriented``, ``normal_neighbors`` are
+        ``smooth_regions``'s).  The cloud's nx / ny / nz columns are the normals where it has them, else the library estimates them.
+        The record of the call is left in ``last_region_stats``.  Not in the reference; composes with select_in_range,
+        select_voxels and select_n_points."""
+        cur, labels = self._regions_selected(dict(kw, max_angle=max_angle, neighbors=neighbors, min_size=min_size))
+        if labels is not None:
+            self._set_idx_selected(cur[labels >= 0])
+
+    def select_largest_region(self, max_angle: float = 5.0, neighbors: int = 16, min_size: int = 1, **kw) -> None:
+        """Keeps, among the selected points, the largest smooth region of the SELECTED points taken as a cloud of their own and
+        deselects the rest (``select_regions``'s arguments).  Of equally large regions the one with the lowest label stays;
+        without any region nothing stays selected.  The record of the call is left in ``last_region_stats``."""
+        cur, labels = self._regions_selected(dict(kw, max_angle=max_angle, neighbors=neighbors, min_size=min_size))
+        if labels is not None:
+            self._set_idx_selected(cur[labels == self.last_region_stats["largest_label"]] if self.last_region_stats["n_regions"] else cur[:0])
 
     def select_plane(self, max_distance: float, invert: bool = False, _ctx=None, **kw) -> None:
         """Keeps, among the selected points, the inliers of the dominant plane of the SELECTED points -- the selection goes in as
