@@ -21,7 +21,7 @@ from .batch import BatchResult, run_batch                        # noqa: E402
 from .tensors import outlier_keep, run_tensors, voxel_keep                     # noqa: E402  (imports torch on its first call only)
 
 from .evaluation import Evaluation, evaluate_registration        # noqa: E402
-from .features import (cluster_labels, farthest_points, fpfh_features, keypoint_keep, orient_normals, segment_plane,   # noqa: E402
+from .features import (cluster_labels, denoise_points, farthest_points, fpfh_features, keypoint_keep, orient_normals, segment_plane,   # noqa: E402
                        segment_planes, smooth_regions, PlaneResult)
 from .registration import (consistent_matches, fit_pose, match_features, ransac_pose, refine_pose, register_global,   # noqa: E402
                            robust_pose, ConsistencyResult, GlobalResult)
@@ -31,4 +31,4 @@ __all__ = ["SimpleICP", "SimpleICPException", "PointCloud", "PointCloudException
            "RigidBodyParameters", "Parameter", "run_batch", "BatchResult", "run_tensors", "voxel_keep", "outlier_keep", "Evaluation",
            "evaluate_registration", "fpfh_features", "keypoint_keep", "match_features", "ransac_pose", "register_global", "GlobalResult", "fit_pose",
            "refine_pose", "robust_pose", "consistent_matches", "ConsistencyResult", "cluster_labels", "segment_plane",
-           "segment_planes", "PlaneResult", "farthest_points", "orient_normals", "smooth_regions"]
+           "segment_planes", "PlaneResult", "farthest_points", "orient_normals", "smooth_regions", "denoise_points"]

@@ -125,6 +125,11 @@ ORIENT_VERSION = 1
 REGIONS_EXPORTS = ["sicp_regions_version", "sicp_regions"]
 REGIONS_VERSION = 1
 
+# include/simpleicp_hip_denoise.h: moving-least-squares smoothing, every point projected onto its neighbourhood's plane, the same
+# kind of companion
+DENOISE_EXPORTS = ["sicp_denoise_version", "sicp_denoise"]
+DENOISE_VERSION = 1
+
 
 class BackendError(RuntimeError):
     """The HIP backend is unavailable or a HIP call failed."""
@@ -228,6 +233,12 @@ class RegionsStats(_Stats):
                                                 "largest_label", "largest_size")]
 
 
+class DenoiseStats(_Stats):
+    """struct sicp_denoise_stats (contract (W)): 40 bytes."""
+    _fields_ = [("n_points", C.c_int64), ("n_small", C.c_int64), ("n_moved", C.c_int64), ("n_clipped", C.c_int64),
+                ("max_displacement", C.c_double)]
+
+
 class IterParams(C.Structure):
     _fields_ = [("x", C.c_double * 6), ("obs", C.c_double * 6), ("obs_weight", C.c_double * 6),
                 ("min_planarity", C.c_double), ("distance_weight", C.c_double), ("max_lm_steps", C.c_int64)]
@@ -307,6 +318,8 @@ FEATURES = {
         "sicp_orient": [_vp, _cint, _vp, _cint, _vp, _cint, _vp, _vp, C.POINTER(OrientStats)]}),
     "regions": _Feature(REGIONS_EXPORTS, "simpleicp_hip_regions.h", "smooth-region", REGIONS_VERSION, {
         "sicp_regions": [_vp, _cint, _vp, _cint, _dbl, _dbl, _cint, _vp, _i64, _vp, C.POINTER(RegionsStats)]}),
+    "denoise": _Feature(DENOISE_EXPORTS, "simpleicp_hip_denoise.h", "denoising", DENOISE_VERSION, {
+        "sicp_denoise": [_vp, _cint, _cint, _dbl, _dbl, _dbl, _i64, _vp, _vp, _vp, C.POINTER(DenoiseStats)]}),
 }
 
 _lib = None
@@ -496,6 +509,7 @@ plane_version = partial(_feature_version, "plane")
 farthest_version = partial(_feature_version, "farthest")
 orient_version = partial(_feature_version, "orient")
 regions_version = partial(_feature_version, "regions")
+denoise_version = partial(_feature_version, "denoise")
 
 
 def select_positions(m, Q):
@@ -961,6 +975,29 @@ class Context:
         self._chk(self._L.sicp_regions(self._h, slot, _ptr(normals), int(k), float(radius), float(cos_min), 1 if oriented else 0,
                                        _ptr(seeds), int(min_size), _ptr(labels), C.byref(st)))
         return (labels[:n], st) if host else st
+
+    # -- moving-least-squares smoothing (contract (W)) --
+    def denoise(self, slot, k, radius=float("inf"), bandwidth=float("inf"), strength=1.0, min_neighbors=3, points_ptr=None,
+                normals_ptr=None, displacement_ptr=None, want_normals=False, want_displacement=False):
+        """sicp_denoise: the slot's points, each projected onto the plane fitted to its k nearest points (the point itself
+        included) strictly within radius (inf = none) -- weights (1 - d2 / bandwidth^2)^2 where positive, else 0 (inf: all 1) --,
+        moved by strength (0 .. 1) times its signed distance g along the plane's normal; a point with fewer than min_neighbors
+        such neighbours stays where it is.  Returns ((n, 3) float64 points, (n, 3) float32 normals or None, (n,) float64
+        displacements g or None, DenoiseStats); with points_ptr (host or device memory, 3 n doubles) the points are left there,
+        the normals at normals_ptr (3 n floats) and the displacements at displacement_ptr (n doubles) if given, and the
+        DenoiseStats alone is returned."""
+        denoise_version()
+        n = self.size(slot)
+        st = DenoiseStats()
+        host = points_ptr is None
+        pts, nrm, disp = points_ptr, normals_ptr, displacement_ptr
+        if host:
+            pts = np.empty((max(n, 1), 3), np.float64)
+            nrm = np.empty((n, 3), np.float32) if want_normals else None
+            disp = np.empty(n, np.float64) if want_displacement else None
+        self._chk(self._L.sicp_denoise(self._h, slot, int(k), float(radius), float(bandwidth), float(strength), int(min_neighbors),
+                                       _ptr(pts), _ptr(nrm), _ptr(disp), C.byref(st)))
+        return (pts[:n], nrm, disp, st) if host else st
 
     # -- planes of a cloud (contracts (P) and (Q)) --
     def plane_triplets(self, X, triples, max_distance, mask=None, n=None, h=None, planes_ptr=None, inliers_ptr=None, want_planes=True):

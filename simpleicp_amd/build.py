@@ -15,7 +15,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libsimpleicp_hip.so"
-SOURCES = [CSRC / "sicp_api.cpp", CSRC / "sicp_clouds.cpp", CSRC / "sicp_search.cpp", CSRC / "sicp_icp.cpp", CSRC / "sicp_comm.cpp", CSRC / "sicp_kernels.hip", CSRC / "sicp_grid.hip", CSRC / "sicp_gridf.hip", CSRC / "sicp_tail.hip", CSRC / "sicp_reject.hip", CSRC / "sicp_lm.hip", CSRC / "sicp_batch.hip", CSRC / "sicp_device.hip", CSRC / "sicp_nangle.hip", CSRC / "sicp_voxel.hip", CSRC / "sicp_eval.hip", CSRC / "sicp_outlier.hip", CSRC / "sicp_fpfh.hip", CSRC / "sicp_global.hip", CSRC / "sicp_posefit.hip", CSRC / "sicp_robust.hip", CSRC / "sicp_consistency.hip", CSRC / "sicp_keypoints.hip", CSRC / "sicp_cluster.hip", CSRC / "sicp_plane.hip", CSRC / "sicp_farthest.hip", CSRC / "sicp_orient.hip", CSRC / "sicp_regions.hip", CSRC / "sicp_io.cpp"]
+SOURCES = [CSRC / "sicp_api.cpp", CSRC / "sicp_clouds.cpp", CSRC / "sicp_search.cpp", CSRC / "sicp_icp.cpp", CSRC / "sicp_comm.cpp", CSRC / "sicp_kernels.hip", CSRC / "sicp_grid.hip", CSRC / "sicp_gridf.hip", CSRC / "sicp_tail.hip", CSRC / "sicp_reject.hip", CSRC / "sicp_lm.hip", CSRC / "sicp_batch.hip", CSRC / "sicp_device.hip", CSRC / "sicp_nangle.hip", CSRC / "sicp_voxel.hip", CSRC / "sicp_eval.hip", CSRC / "sicp_outlier.hip", CSRC / "sicp_fpfh.hip", CSRC / "sicp_global.hip", CSRC / "sicp_posefit.hip", CSRC / "sicp_robust.hip", CSRC / "sicp_consistency.hip", CSRC / "sicp_keypoints.hip", CSRC / "sicp_cluster.hip", CSRC / "sicp_plane.hip", CSRC / "sicp_farthest.hip", CSRC / "sicp_orient.hip", CSRC / "sicp_regions.hip", CSRC / "sicp_denoise.hip", CSRC / "sicp_io.cpp"]
 HEADERS = [CSRC / "sicp_internal.h", CSRC / "sicp_host.h", CSRC / "sicp_lanes.h", CSRC / "sicp_pairtree.h", CSRC / "sicp_horn.h", CSRC / "sicp_pose_dev.h", CSRC / "sicp_solver.h", CSRC / "sicp_normals.h", CSRC / "sicp_grid_dev.h", CSRC / "sicp_ball_dev.h", CSRC / "sicp_union_dev.h", CSRC / "sicp_handover.h",
            CSRC / "sicp_grid_nn_one.inc", CSRC / "sicp_knn_sweep4.inc", CSRC / "sicp_tail_body.inc", PKG.parent / "include" / "simpleicp_hip.h",
            PKG.parent / "include" / "simpleicp_hip_batch.h", PKG.parent / "include" / "simpleicp_hip_device.h",
@@ -26,7 +26,7 @@ HEADERS = [CSRC / "sicp_internal.h", CSRC / "sicp_host.h", CSRC / "sicp_lanes.h"
            PKG.parent / "include" / "simpleicp_hip_consistency.h", PKG.parent / "include" / "simpleicp_hip_keypoints.h",
            PKG.parent / "include" / "simpleicp_hip_cluster.h", PKG.parent / "include" / "simpleicp_hip_plane.h",
            PKG.parent / "include" / "simpleicp_hip_farthest.h", PKG.parent / "include" / "simpleicp_hip_orient.h",
-           PKG.parent / "include" / "simpleicp_hip_regions.h"]
+           PKG.parent / "include" / "simpleicp_hip_regions.h", PKG.parent / "include" / "simpleicp_hip_denoise.h"]
 # -amdgpu-mfma-vgpr-form: MFMA results land in ordinary VGPRs (gfx950's register file is unified), so the VALU work
 # that consumes them (min trees of the matrix-pipe filter, Gram folds) needs no v_accvgpr_read per register
 COMPILE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",

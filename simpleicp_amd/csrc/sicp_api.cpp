@@ -260,6 +260,7 @@ SICP_EXPORT int sicp_ctx_create(int device, sicp_ctx **ctx_out)
     if (const char *e = std::getenv("SICP_FPFH_CHUNK")) c->fpfh_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_ORIENT_CHUNK")) c->orient_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_REGIONS_CHUNK")) c->regions_chunk = std::atol(e);
+    if (const char *e = std::getenv("SICP_DENOISE_CHUNK")) c->denoise_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_KEYPOINT_CHUNK")) c->keypoint_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_MATCH_CHUNK")) c->match_chunk = std::atol(e);
     if (const char *e = std::getenv("SICP_PLANE_SPAN")) c->plane_span = std::atol(e) > 0 ? std::atol(e) : 0;

@@ -363,6 +363,9 @@ struct sicp_ctx {
     // smooth regions (sicp_regions.hip) own no buffer: the lists lie in or_nbr, the staged normals in or_nrm, the staged seed bytes
     // in or_flip, every point's kind byte in cand_keep, and the union, root, rank (+ block sums), size and label words in the cl_ buffers
     long regions_chunk = 0;        // SICP_REGIONS_CHUNK: points per search of sicp_regions (0: chosen per call)
+    // moving-least-squares smoothing (sicp_denoise.hip) owns no buffer either: host outputs are staged in kp_eig (the points), or_out
+    // (the normals) and kp_sal (the displacements)
+    long denoise_chunk = 0;        // SICP_DENOISE_CHUNK: points per search of sicp_denoise (0: chosen per call)
     // descriptor matching and RANSAC poses (sicp_global.hip): the queries' keys (bits(d2) << 32 | row) and the staging buffers of
     // the call's arrays
     DevBuf<unsigned long long> gl_key;

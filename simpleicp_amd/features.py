@@ -6,7 +6,9 @@ labels, the points that belong together (``cluster_labels``; contract (U), DESIG
 in space (``farthest_points``; contract (S), DESIGN.md section 25, include/simpleicp_hip_farthest.h) -- and normals oriented
 consistently, what the descriptor's signs stand on (``orient_normals``; contract (H), DESIGN.md section 26,
 include/simpleicp_hip_orient.h) -- and the smooth regions, every patch whose neighbouring normals agree (``smooth_regions``;
-contract (J), DESIGN.md section 27, include/simpleicp_hip_regions.h).
+contract (J), DESIGN.md section 27, include/simpleicp_hip_regions.h) -- and moving-least-squares smoothing, the coordinates
+themselves improved before any of these reads them (``denoise_points``; contract (W), DESIGN.md section 28,
+include/simpleicp_hip_denoise.h).
 
 Contract (F), DESIGN.md section 17 (include/simpleicp_hip_fpfh.h): every point's k nearest points from the library's own search,
 a normal per point, two passes over those lists -- all on the GPU, reproducible bit for bit.  What follows the descriptor is
@@ -849,3 +851,86 @@ def _regions_on_device(X, normals, seeds, k, cm, r, mp, ms, oriented, kn):
             _wait_for_torch(ctx, dev)
     st = ctx.regions(_lib.FIX, nv, k, cm, r, oriented, sd, ms, labels_ptr=labels.data_ptr())
     return labels, _lib._stats_dict(st)
+
+
+# ---- moving-least-squares smoothing (contract (W)) ----
+
+_NO_DENOISE = dict(n_points=0, n_small=0, n_moved=0, n_clipped=0, max_displacement=0.0)
+
+
+def denoise_arguments(neighbors=16, radius=None, bandwidth=None, strength=1.0, min_neighbors=3, rounds=1):
+    """(k, radius as a float -- inf: none --, bandwidth likewise, strength, min_neighbors, rounds), checked: ValueError naming the
+    keyword."""
+    k = _count_of("neighbors", neighbors, 2, _lib.KEYPOINTS_MAX_K)
+    try:
+        r, b = _radius_of("radius", radius), _radius_of("bandwidth", bandwidth)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    s = _number_of("strength", strength)
+    if not 0.0 <= s <= 1.0:
+        raise ValueError(f"strength must be >= 0 and <= 1, not {strength!r}")
+    return k, r, b, s, _count_of("min_neighbors", min_neighbors, 1, 2**62), _count_of("rounds", rounds, 1, 2**31 - 1)
+
+
+def denoise_points(X, *, neighbors=16, radius=None, bandwidth=None, strength=1.0, min_neighbors=3, rounds=1, return_normals=False,
+                   return_displacement=False, return_info=False):
+    """X smoothed by moving least squares at order 0/1 as an (n, 3) float64 array (contract (W)): every point
+    is projected onto the plane fitted to its ``neighbors`` nearest points (the point itself included, 2 .. 128; with ``radius``
+    only those strictly closer) -- PCL's ``MovingLeastSquares`` without a polynomial, CloudCompare's "MLS smooth".  The plane goes
+    through the weighted mean of the support, its normal is the eigenvector of the smallest eigenvalue of the weighted covariance;
+    ``bandwidth=b`` weighs a neighbour at squared distance d2 by (1 - d2 / b^2)^2 where that is positive, else 0 (None: all 1).
+    The point moves by ``strength`` (0 .. 1) times its signed distance along the normal; one with fewer than ``min_neighbors``
+    counted neighbours stays where it is.  All points are projected from the input positions, none sees another's output: the
+    result depends on the inputs alone, bit for bit.  ``rounds`` > 1 feeds each round's output to the next as a cloud of its own.
+
+    X: an (n, 3) array, a PointCloud (all its points, whatever is selected) or a CUDA torch tensor (float32 / float64, any
+    strides; ingest and stream rule are run_tensors').  A tensor gives a torch tensor on its device, anything else numpy; a
+    tensor's rows never leave the device.  The result is always float64: on a georeferenced cloud a float32 store would swallow
+    the displacement.  ``return_normals``: also the planes' (n, 3) float32 normals (largest component positive; zeros where the
+    point stayed for want of neighbours); ``return_displacement``: also the (n,) float64 signed displacements, out = x - g *
+    normal; ``return_info``: also the call's record as a dict (n_points, n_small, n_moved, n_clipped -- the balls that held more
+    points than ``neighbors`` --, max_displacement, and rounds) -- all three those of the last round.  The results come as
+    (points[, normals][, displacement][, info]).  The library's fixed slot holds the last round's input afterwards."""
+    from .tensors import _is_device_tensor
+    a = denoise_arguments(neighbors, radius, bandwidth, strength, min_neighbors, rounds)
+    for name, v in (("return_normals", return_normals), ("return_displacement", return_displacement), ("return_info", return_info)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, not {v!r}")
+
+    def answer(points, normals, displacement, info):
+        out = ((points,) + ((normals,) if return_normals else ()) + ((displacement,) if return_displacement else ())
+               + ((dict(info, rounds=a[5]),) if return_info else ()))
+        return out if len(out) > 1 else points
+    if _is_device_tensor(X) or type(X).__module__.startswith("torch"):
+        return answer(*_denoise_on_device(X, a, bool(return_normals), bool(return_displacement)))
+    X, n = _host_points(X)
+    if n == 0:
+        return answer(np.empty((0, 3), np.float64), np.empty((0, 3), np.float32), np.empty(0, np.float64), dict(_NO_DENOISE))
+    if a[0] > n:
+        raise ValueError(f"neighbors ({a[0]}) exceeds the number of points ({n})")
+    for r in range(a[5]):
+        last = r == a[5] - 1
+        ctx = _host_opening("denoise_points", "smooth the clouds", X, ("denoise", "denoising"))
+        X, nrm, disp, st = ctx.denoise(_lib.FIX, *a[:5], want_normals=last and bool(return_normals),
+                                       want_displacement=last and bool(return_displacement))
+    return answer(X, nrm, disp, _lib._stats_dict(st))
+
+
+def _denoise_on_device(X, a, return_normals, return_displacement):
+    import torch
+    from .tensors import _keep_opening
+    if isinstance(X, torch.Tensor) and X.dim() == 2 and 0 < X.shape[0] < a[0]:
+        raise ValueError(f"neighbors ({a[0]}) exceeds the number of points ({X.shape[0]})")
+    for r in range(a[5]):
+        last = r == a[5] - 1
+        ctx, n, _, _ = _keep_opening("denoise_points", X, None, needs=("denoise", "denoising"))
+        dev = X.device
+        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if last and return_normals else None
+        disp = torch.empty(n, dtype=torch.float64, device=dev) if last and return_displacement else None
+        if ctx is None:
+            return out, nrm, disp, dict(_NO_DENOISE)
+        st = ctx.denoise(_lib.FIX, *a[:5], points_ptr=out.data_ptr(), normals_ptr=None if nrm is None else nrm.data_ptr(),
+                         displacement_ptr=None if disp is None else disp.data_ptr())
+        X = out                       # (the call returned complete: the next round reads what this one wrote)
+    return out, nrm, disp, _lib._stats_dict(st)

@@ -62,6 +62,7 @@ class PointCloud(pd.DataFrame):
     last_farthest = None                  # select_farthest leaves (picks in pick order, squared distances, record) here
     last_cluster_stats = None             # select_largest_cluster / select_clusters leave their record here (a dict)
     last_region_stats = None              # select_regions / select_largest_region leave their record here (a dict)
+    last_denoise_stats = None             # denoise leaves its record here (a dict)
 
     def __init__(self, *args, **kwargs) -> None:
         kwargs.pop("remapping", None)     # accepted and ignored, like the reference (pointcloud.py:25)
@@ -436,6 +437,34 @@ class PointCloud(pd.DataFrame):
         cur, labels = self._regions_selected(dict(kw, max_angle=max_angle, neighbors=neighbors, min_size=min_size))
         if labels is not None:
             self._set_idx_selected(cur[labels == self.last_region_stats["largest_label"]] if self.last_region_stats["n_regions"] else cur[:0])
+
+    def denoise(self, neighbors: int = 16, **kw) -> None:
+        """Rewrites the x / y / z of the selected points, smoothed by moving least squares as a cloud of their own -- each
+        projected onto the plane fitted to its ``neighbors`` nearest selected points; the points that are not selected play no
+        part and stay as they are (contract (W); the keywords ``radius``, ``bandwidth``, ``strength``,
+        ``min_neighbors``, ``rounds`` are ``denoise_points``'s).  The nx / ny / nz / planarity columns, if present, are left
+        alone: they describe the coordinates as they were, estimate them again where they matter.  The record of the call is
+        left in ``last_denoise_stats``.  Not in the reference; composes with select_in_range, select_voxels and
+        select_n_points."""
+        from . import features
+        unknown = set(kw) - {"radius", "bandwidth", "strength", "min_neighbors", "rounds"}
+        if unknown:
+            raise PointCloudException(f"denoise takes no keyword {sorted(unknown)[0]!r}")
+        cur = self.idx_selected
+        try:
+            a = features.denoise_arguments(neighbors=neighbors, **kw)
+            if len(cur) == 0:
+                self.last_denoise_stats = dict(features._NO_DENOISE, rounds=a[5])
+                return
+            X = np.ascontiguousarray(np.stack([self[c].to_numpy()[cur] for c in _XYZ], axis=1), dtype=np.float64)
+            P, info = features.denoise_points(X, neighbors=neighbors, return_info=True, **kw)
+        except ValueError as e:
+            raise PointCloudException(str(e)) from None
+        self.last_denoise_stats = info
+        for axis, name in enumerate(_XYZ):
+            col = np.array(self[name].to_numpy(), dtype=np.float64)   # (a copy: the frame's own column is not written in place)
+            col[cur] = P[:, axis]
+            self._adopt_column(name, col)
 
     def select_plane(self, max_distance: float, invert: bool = False, _ctx=None, **kw) -> None:
         """Keeps, among the selected points, the inliers of the dominant plane of the SELECTED points -- the selection goes in as
